@@ -21,9 +21,22 @@ pepper) sharded over the ranks, each rank solving B / N of them one after the
 other, ONE gather of all reconstructions at the end; the clock covers solves
 and gather (strong scaling).
 
-The timed region of K steps is repeated `--reps` times (default 5, each
-bracketed by barrier + synchronize, max over ranks); the line reports the
-median.  Rank 0 prints one JSON line.
+The timed region of K steps is repeated `--reps` times (default 1, with
+`--full` 5; each bracketed by barrier + synchronize, max over ranks); the line
+reports the median.  Rank 0 prints one JSON line.
+
+A plain run does only what that line's headline needs: set-up, the tuner's plan
+pass, W warm-up steps, the timed steps, the line.  `--full` adds what the
+headline does not need: the bit-identical replay of the timed schedule through
+the one-iteration kernel (exit code 4 if it differs), that kernel's own rate,
+the finite check, the CPU baselines and BASELINE config 4.
+
+`--dump-outputs DIR` writes, after the timed steps, what they computed: the
+reconstruction a caller of the solver receives (x * x_scale, float32; every
+volume of the run in volume order) as DIR/x.npy -- every voxel up to
+DUMP_VOXELS of them, beyond that the same seeded sample of DUMP_VOXELS on every
+run.  The inputs are seeded too, so two builds can be compared output for
+output.
 """
 import argparse
 import ctypes
@@ -42,6 +55,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0      # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
 BYTES_PER_VOXEL = 44        # 11 float32 words: read xbar,x,b,p[3]; write p[3],x,xbar
 PMC_TABLE = os.path.join("profiles", "pmc_by_config.json")
+DUMP_VOXELS = 1 << 22       # --dump-outputs: at most 16 MB of float32
 
 
 class HipEvents(object):
@@ -118,6 +132,29 @@ def cpu_baseline_c(sample_n, iters):
     c_oracle.primal_dual_denoise(b, vol.shape, "TV", "L2", 0.03, iters, 16.0)
     dt = time.time() - t0
     return iters / dt, c_oracle.threads()
+
+
+def dump_indices(total, seed=0):
+    """Which of `total` output voxels --dump-outputs writes: all of them up to
+    DUMP_VOXELS, beyond that a fixed seeded sample (sorted, no repeats)."""
+    if total <= DUMP_VOXELS:
+        return np.arange(total)
+    rng = np.random.default_rng(seed)
+    return np.unique(rng.integers(0, total, DUMP_VOXELS))
+
+
+def dump_outputs(directory, volumes):
+    """DIR/x.npy from the reconstructions a caller receives (1-D tensors of
+    equal length, in volume order), sampled as dump_indices says."""
+    import torch
+    n = volumes[0].numel()
+    idx = dump_indices(n * len(volumes))
+    parts = []
+    for v, vol in enumerate(volumes):
+        sel = idx[(idx >= v * n) & (idx < (v + 1) * n)] - v * n
+        parts.append(vol[torch.from_numpy(sel).to(vol.device)].cpu())
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "x.npy"), torch.cat(parts).numpy())
 
 
 def config4_line(n, runs=3, cpu_sample=64):
@@ -253,9 +290,18 @@ def parse_args(argv):
                     help="copy the final iterate back into x after an odd number "
                          "of multi-iteration launches instead of letting x and "
                          "its scratch volume trade storage (A/B runs)")
-    ap.add_argument("--reps", type=int, default=5,
+    ap.add_argument("--reps", type=int, default=None,
                     help="repetitions of the timed K-step region (median is "
-                         "reported)")
+                         "reported; default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not "
+                         "need: five repetitions, the bit-identical replay, "
+                         "the one-iteration kernel's rate, the CPU baselines, "
+                         "BASELINE config 4 (the --no-* options drop parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the reconstruction "
+                         "they computed to DIR/x.npy (float32; a fixed seeded "
+                         "sample of %d voxels beyond that size)" % DUMP_VOXELS)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--data", default=None, choices=["L2", "L1"])
     ap.add_argument("--batch", type=int, default=0,
@@ -405,7 +451,8 @@ def main(argv=None):
          for _ in range(2)]
     w = (1.0, 1.0, 1.0)
     lmbda = 1.0 / alpha
-    reps = max(1, args.reps)
+    reps = max(1, args.reps if args.reps is not None else
+               (5 if args.full else 1))
     flags = ops.PD_REG_TV | (ops.PD_DATA_L1 if data == "L1"
                              else ops.PD_DATA_L2)
     state = {"slot": 0}
@@ -498,7 +545,11 @@ def main(argv=None):
             g0 = time.perf_counter()
             bucket = gather_results(ops.scale(x, scales[0]))
             gather_ms = (time.perf_counter() - g0) * 1e3
+            if rank == 0 and args.dump_outputs:
+                dump_outputs(args.dump_outputs, bucket)
             del bucket
+        elif args.dump_outputs:
+            dump_outputs(args.dump_outputs, [ops.scale(x, scales[0])])
     else:
         # config 5: each rank solves its share of the batch, volume after
         # volume (args.steps iterations each), then ONE gather; the clock
@@ -529,6 +580,8 @@ def main(argv=None):
             g0 = time.perf_counter()
             if world > 1:
                 bucket = gather_results(results)
+                if r == reps - 1:
+                    share = bucket          # rank 0: every rank's results
                 del bucket
             gathers.append((time.perf_counter() - g0) * 1e3)
             fence()
@@ -537,6 +590,15 @@ def main(argv=None):
                 kms = ev.elapsed_ms(e0, em) / triples
             rep_kernel_ms.append(kms)
         gather_ms = median(gathers) if world > 1 else None
+        if rank == 0 and args.dump_outputs:
+            if world == 1:
+                share = [results]
+            # volume i is the (i // world)-th of rank i % world
+            dump_outputs(args.dump_outputs,
+                         [share[i % world][(i // world) * nvox:
+                                           (i // world + 1) * nvox]
+                          for i in range(args.batch)])
+        share = None
 
     tmed = median(rep_s)
     kernel_ms = median(rep_kernel_ms)
@@ -560,7 +622,7 @@ def main(argv=None):
     # (primal_dual_solver.py:242-256 per iteration).  Every rank checks its own
     # volume; in --batch mode the last volume of the rank's share.
     verify = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         a = state["slot"]
         timed = (x.clone(), xbar[a].clone(), p[a].clone())
         launches_k = ops.pd_fusedk_launches(3)
@@ -609,7 +671,7 @@ def main(argv=None):
 
     # for reference: the one-iteration-per-pass kernel on the same state
     single = None
-    if world == 1 and args.steps >= 2 and not args.batch:
+    if args.full and world == 1 and args.steps >= 2 and not args.batch:
         _lib.set_param("pd2_enable", 0)
         _lib.set_param("pdk_enable", 0)
         try:
@@ -633,7 +695,7 @@ def main(argv=None):
             _lib.set_param("pd2_enable", 1)
             _lib.set_param("pdk_enable", 1)
 
-    finite = bool(torch.isfinite(x).all().item())
+    finite = bool(torch.isfinite(x).all().item()) if args.full else None
     joined = torch.ones(1, dtype=torch.int64, device="cpu" if on_host else dev)
     if world > 1:
         dist.all_reduce(joined)
@@ -679,6 +741,7 @@ def main(argv=None):
                 "kernel_config": None if plan is None else {
                     "waves": plan[0], "tiles_x": plan[1], "zchunk": plan[2],
                     "pinned": bool(pinned)},
+                "full": args.full,
                 "timed_repetitions": reps,
                 "repetition_ms": [t * 1e3 for t in rep_s],
                 "statistic": "median of the repetitions (each: barrier + "
@@ -715,7 +778,8 @@ def main(argv=None):
                 "avg_launch_ms_repetitions": rep_kernel_ms,
                 "single_pass_reference": single},
         }
-        if world == 1 and not args.no_cpu_baseline and not args.batch:
+        if args.full and world == 1 and not args.no_cpu_baseline and \
+                not args.batch:
             sn = args.cpu_sample or n
             its = cpu_baseline(sn, 2)
             out["cpu_baseline"] = {
@@ -737,7 +801,8 @@ def main(argv=None):
                               "volume, 6 iterations after 1 warm-up" % sn}
             except Exception as e:             # no gcc on the box: say so
                 out["cpu_baseline_compiled"] = {"error": str(e)}
-        if world == 1 and not args.batch and not args.no_config4 and n >= 64:
+        if args.full and world == 1 and not args.batch and \
+                not args.no_config4 and n >= 64:
             # (the solver state of the headline run is no longer needed)
             del p[:], xbar[:], inputs[:]
             torch.cuda.empty_cache()

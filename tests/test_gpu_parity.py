@@ -3610,3 +3610,46 @@ def test_admm_with_the_one_pass_outer_step_is_bit_identical(nsol, monkeypatch, i
         outs.append(s.get_x())
         assert (L.LAST_FORM[0] == "lanczos-in-blur") == (iter_max == 10)
     assert np.array_equal(outs[0], outs[1])
+
+
+def test_bench_dump_is_what_the_solver_returns(nsol, tmp_path):
+    """bench.py --dump-outputs writes what its timed path computed: at 64^3 (every
+    voxel) the reconstruction PrimalDualSolver returns for the same volume after
+    the warm-up and the timed iterations; the line reports K timed steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import nsol_amd.linear_operators as LO
+    import nsol_amd.primal_dual_solver as pd
+    from nsol_amd.proximal_operators import ProximalOperators as prox
+    from nsol_amd.synthetic import synth_volume
+    from conftest import ROOT
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--size", "64", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], env=env, timeout=300,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    line = json.loads([ln for ln in p.stdout.decode().splitlines()
+                       if ln.startswith("{")][-1])
+    assert line["steps"] == 7 and line["config"]["timed_repetitions"] == 1
+    assert line["ms_per_step"] > 0
+    got = np.load(str(tmp_path / "x.npy"))
+    assert got.dtype == np.float32 and got.shape == (64 ** 3,)
+    shape = (64, 64, 64)
+    b = synth_volume(64, seed=0, kind="gauss", dtype=np.float32).reshape(-1)
+    xs = float(b.max())
+    grad, grad_adj = LO.LinearOperators3D().get_gradient_operators()
+    Z = grad(b.reshape(shape)).shape
+    D = lambda x: grad(x.reshape(*shape)).flatten()
+    Da = lambda x: grad_adj(x.reshape(*Z)).flatten()
+    pf = lambda x, tau: prox.prox_ell2_denoising(x, tau, x0=b, x_scale=xs)
+    s = pd.PrimalDualSolver(prox_f=pf, prox_g_conj=prox.prox_tv_conj, B=D, B_conj=Da,
+                            L2=16, x0=b, alpha=0.03, iterations=9, x_scale=xs,
+                            alg_type="ALG2", dtype=np.float32)
+    s.run()
+    assert s.get_execution() == "fused"
+    assert rel_l2(got, s.get_x()) <= F32_TOL

@@ -34,7 +34,13 @@ def test_library_builds_loads_and_exports_declared_symbols():
     assert lib.nsol_hip_abi_version() == 1
     assert lib.nsol_hip_reduce_ws_doubles() == 65536
     assert lib.nsol_lb_gram_ws_doubles() >= 256
-    assert lib.nsol_pd_fusedk_launches(3) == 0 and lib.nsol_pd_fusedk_launches(4) == -1
+    # the launch counter is process-wide and GPU tests may have run in this
+    # process before: a fresh process has launched nothing
+    fresh = subprocess.run(
+        [sys.executable, "-c", "from nsol_amd import _lib; lib = _lib.load(); "
+         "print(lib.nsol_pd_fusedk_launches(3), lib.nsol_pd_fusedk_launches(4))"],
+        cwd=ROOT, stdout=subprocess.PIPE, timeout=120)
+    assert fresh.stdout.split() == [b"0", b"-1"]
     for name in ("nsol_pd_fusedk_tuned", "nsol_pd_fusedk_plan",
                  "nsol_pd_fusedk_launches"):
         assert name in decl
@@ -452,6 +458,28 @@ def test_rccl_launcher_branch_against_a_stated_topology(tmp_path):
     d = json.loads([ln for ln in r.stdout.decode().splitlines()
                     if ln.startswith("{")][0])
     assert d["ranks_joined"] == 2
+
+
+def test_bench_dump_is_every_voxel_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: a small run's every voxel, volumes in order; beyond
+    DUMP_VOXELS the same seeded sample on every run, within 64 MB of float32.
+    --full is off unless asked for."""
+    import torch
+    import bench
+    assert np.array_equal(bench.dump_indices(1000), np.arange(1000))
+    n = 512 ** 3 * 8
+    big = bench.dump_indices(n)
+    assert np.array_equal(big, bench.dump_indices(n))
+    assert 0.9 * bench.DUMP_VOXELS < big.size <= bench.DUMP_VOXELS
+    assert big.size * 4 <= 64 << 20
+    assert np.all(np.diff(big) > 0) and 0 <= big[0] and big[-1] < n
+    vols = [torch.arange(5, dtype=torch.float32) + 10 * k for k in range(3)]
+    bench.dump_outputs(str(tmp_path / "d"), vols)
+    got = np.load(str(tmp_path / "d" / "x.npy"))
+    assert got.dtype == np.float32
+    assert np.array_equal(got, torch.cat(vols).numpy())
+    assert bench.parse_args([]).reps is None and not bench.parse_args([]).full
+    assert bench.parse_args(["--full"]).full
 
 
 def test_minres_scalars_restate_scipys_lsmr_stopping_tests():
