@@ -323,6 +323,9 @@ def main():
         "knobs": args.param, "blur_epilogue": not args.no_blur_epilogue,
         "prescaled_rhs": not args.no_prescaled_rhs,
         "lsmr_x": "carried" if args.carried_x else "assembled at the end"})
+    if args.minimizer.upper() == "L-BFGS-B":
+        from nsol_amd import lbfgsb as lb_mod
+        out["lbfgsb_stats"] = dict(lb_mod.STATS)      # (summed over every run)
     print(json.dumps(out))
 
 

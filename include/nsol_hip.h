@@ -821,8 +821,10 @@ int nsol_pair_stats_f64(const double *x, const double *y, int64_t n, double mx,
  *                 #moving variables without a breakpoint and g != 0, #moving
  *   count_window  result[0] = number of breakpoints with (tbk, i) >
  *                 (t_done, i_done) and tbk <= t_hi
- *   select        the indices of those breakpoints, unordered; *count = how
- *                 many (may exceed capacity: then size the window first)
+ *   select        the indices of the breakpoints with (t_done, i_done) <
+ *                 (tbk, i) <= (t_hi, i_hi), unordered (i_hi = INT64_MAX: all
+ *                 with tbk <= t_hi, count_window's); *count = how many (may
+ *                 exceed capacity: then shrink the window and select again)
  *   cauchy_finish xcp = bound for breakpoints up to (t_done, i_done), else
  *                 x + tsum*d; updates iwhere
  *   wcomb         out = free ? scale*(sum_k bcoef[k]*base[k] + sum_j wcoef[j]*w[j]) : 0
@@ -935,9 +937,12 @@ int nsol_lb_mdot_f32(const float *x, const float *y, const int8_t *iwhere, int64
 int nsol_lb_cauchy_setup_f32(const float *x, const float *g, int64_t n, double lo,
                              double hi, int8_t *iwhere, float *d, float *tbk,
                              double *result, double *ws, void *stream);
+/* Compaction of the breakpoints with (t_done, i_done) < (tbk[i], i) <= (t_hi, i_hi),
+ * compared as pairs, into out_idx (any order; at most `capacity` of them written).
+ * *count receives how many there are, also when that is more than capacity. */
 int nsol_lb_select_f32(const float *tbk, int64_t n, double t_done, int64_t i_done,
-                       double t_hi, int64_t *out_idx, int capacity, int *count,
-                       void *stream);
+                       double t_hi, int64_t i_hi, int64_t *out_idx, int capacity,
+                       int *count, void *stream);
 int nsol_lb_count_window_f32(const float *tbk, int64_t n, double t_done,
                              int64_t i_done, double t_hi, double *result,
                              double *ws, void *stream);
@@ -976,8 +981,8 @@ int nsol_lb_cauchy_setup_f64(const double *x, const double *g, int64_t n, double
                              double hi, int8_t *iwhere, double *d, double *tbk,
                              double *result, double *ws, void *stream);
 int nsol_lb_select_f64(const double *tbk, int64_t n, double t_done, int64_t i_done,
-                       double t_hi, int64_t *out_idx, int capacity, int *count,
-                       void *stream);
+                       double t_hi, int64_t i_hi, int64_t *out_idx, int capacity,
+                       int *count, void *stream);
 int nsol_lb_count_window_f64(const double *tbk, int64_t n, double t_done,
                              int64_t i_done, double t_hi, double *result,
                              double *ws, void *stream);

@@ -1187,7 +1187,9 @@ __global__ __launch_bounds__(kBlock) void k_cauchy_setup(
   block_partials<4>(a, ws, false);
 }
 
-// ---- breakpoints (t, i) lexicographically after (t_done, i_done), t <= t_hi
+// ---- breakpoints (t, i) lexicographically after (t_done, i_done) and at most
+// (t_hi, i_hi) (i_hi = INT64_MAX: every t <= t_hi; a smaller i_hi splits a run of
+// equal breakpoints that one window cannot hold)
 // Compaction into out[] (any order; the candidates are sorted afterwards).  A
 // workgroup looks at kSelSweeps x kSelPer elements per thread (16-byte loads, one
 // bit of state per element) and reserves its range with ONE returning atomic:
@@ -1202,6 +1204,7 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void k_select(const T *__restrict__ tbk,
                                                     int64_t n, T t_done,
                                                     int64_t i_done, T t_hi,
+                                                    int64_t i_hi,
                                                     int64_t *out, int capacity,
                                                     int *count) {
   __shared__ int s_cnt[kBlock / kWave];
@@ -1237,7 +1240,8 @@ __global__ __launch_bounds__(kBlock) void k_select(const T *__restrict__ tbk,
       for (int k = 0; k < VEC; ++k) {
         const int64_t i = i0 + k;
         const T t = t4[k];
-        if (i < n && t <= t_hi && (t > t_done || (t == t_done && i > i_done)))
+        if (i < n && (t < t_hi || (t == t_hi && i <= i_hi)) &&
+            (t > t_done || (t == t_done && i > i_done)))
           f |= 1u << (r * VEC + k);
       }
     }
@@ -1896,8 +1900,8 @@ int nsol_lb_masked_gram_rgrad_f64(const double *const *vecs, int nvec,
     return launch_status();                                                      \
   }                                                                              \
   int nsol_lb_select_##SUF(const T *tbk, int64_t n, double t_done,               \
-                           int64_t i_done, double t_hi, int64_t *out_idx,        \
-                           int capacity, int *count, void *s) {                  \
+                           int64_t i_done, double t_hi, int64_t i_hi,            \
+                           int64_t *out_idx, int capacity, int *count, void *s) { \
     if (n < 1 || !tbk || !out_idx || !count || capacity < 1)                     \
       return NSOL_EINVAL;                                                        \
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int), as_stream(s));          \
@@ -1906,7 +1910,7 @@ int nsol_lb_masked_gram_rgrad_f64(const double *const *vecs, int nvec,
     const int64_t blocks = (n + per - 1) / per;                                  \
     if (blocks > 0x7fffffff) return NSOL_EINVAL;                                 \
     hipLaunchKernelGGL(k_select<T>, dim3((unsigned)blocks), dim3(kBlock), 0,     \
-                       as_stream(s), tbk, n, (T)t_done, i_done, (T)t_hi,         \
+                       as_stream(s), tbk, n, (T)t_done, i_done, (T)t_hi, i_hi,   \
                        out_idx, capacity, count);                                \
     return launch_status();                                                      \
   }                                                                              \

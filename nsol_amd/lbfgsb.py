@@ -22,7 +22,8 @@ import math
 import numpy as np
 
 # counters of the last minimize() call (diagnostics for tools/profile_admm.py)
-STATS = {"cauchy_calls": 0, "breakpoints": 0, "crossed": 0, "fetches": 0}
+STATS = {"cauchy_calls": 0, "breakpoints": 0, "crossed": 0, "fetches": 0,
+         "window_shrinks": 0}
 
 EPSMCH = np.finfo(np.float64).eps
 # False: direction, projection, d = z - x and the BFGS update's products with d as

@@ -9,6 +9,7 @@ import torch
 
 from . import _lib, _timing, ops
 from .device import suffix, stream_ptr
+from .lbfgsb import STATS
 
 
 # The Cauchy search's window of breakpoints reaches to the minimiser of the current
@@ -26,6 +27,9 @@ def _fn(name, t):
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+ALL = np.iinfo(np.int64).max      # i_hi of a window that takes every index at t_hi
 
 
 class DeviceBackend(object):
@@ -329,23 +333,82 @@ class DeviceBackend(object):
                 np.zeros((m, 0))
             return (g(tbk), sub.cpu().numpy(), g(d), g(x), wyv, wsv)
 
+        T = np.float32 if f32 else np.float64
+
+        def select(S, t_hi, i_hi=ALL):
+            """Breakpoints (t, i) with (t_done, i_done) < (t, i) <= (t_hi, i_hi)
+            into idx; returns how many there are (also past the capacity)."""
+            self._check(sel(_p(tbk), n, float(S.t_done), int(S.i_done),
+                            float(t_hi), int(i_hi), _p(idx), cap, _p(cnt),
+                            stream_ptr()), "select")
+            return int(cnt.item())
+
+        def shrink(S, over, count):
+            """A window of 1 .. cap breakpoints at the start of one that holds
+            count > cap of them up to `over`.  The proportional shrink while no
+            window came back empty (breakpoints are dense and fairly even on
+            image data); then bisection between the largest empty and the
+            smallest overflowing limit; between two adjacent values of T (more
+            than cap breakpoints at one t), bisection on the index."""
+            q = lambda v: float(T(v))        # the limit the kernel compares with
+            empty = None
+            lim0 = over
+            base = max(S.t_done, 0.0)
+            while True:
+                STATS["window_shrinks"] += 1
+                if empty is None:
+                    lim = base + min(0.5, 0.8 * cap / count) * (over - base)
+                    if q(lim) >= q(over):
+                        lim = float(np.nextafter(T(over), T(-np.inf)))
+                else:
+                    lim = q(0.5 * (empty + over))
+                    if not q(empty) < lim < q(over):
+                        lim = float(np.nextafter(T(empty), T(over)))
+                if q(lim) >= q(over) or q(lim) < S.t_done:
+                    break          # no value of T below `over` left in the window
+                count = select(S, lim)
+                if count > cap and empty is None and over != lim0 and \
+                        S.t_done >= 0.0 and select(S, S.t_done) > cap:
+                    # a second overflow in a row: the shrink may be closing in on
+                    # a run of equal breakpoints at t_done itself (geometrically,
+                    # ~50 selects in float64) -- split that run by index at once
+                    over = S.t_done
+                    break
+                if count > cap:
+                    over = lim
+                elif count == 0:
+                    empty = lim
+                else:
+                    return count
+            t_over = q(over)
+            # every breakpoint of the window below (t_over, i_hi) has t == t_over,
+            # but those with t == t_done and i <= i_done are not in it
+            i_lo = S.i_done if S.t_done == t_over else -1
+            i_hi = n - 1
+            while True:
+                STATS["window_shrinks"] += 1
+                if i_hi - i_lo < 2:       # (one index adds at most one breakpoint)
+                    raise RuntimeError("Cauchy search: no window of at most %d "
+                                       "breakpoints" % cap)
+                mid = (i_lo + i_hi) // 2
+                count = select(S, t_over, mid)
+                if count > cap:
+                    i_hi = mid
+                elif count == 0:
+                    i_lo = mid
+                else:
+                    return count
+
         def advance(S):
             lim = (S.tsum + S.dtm) * (1.0 + (1e-6 if f32 else 1e-12)) + 1e-300
             if WINDOW_STRETCH != 1.0:
                 lim = S.tsum + WINDOW_STRETCH * (lim - S.tsum)
             # the compaction counts as it goes (its counter runs past the
-            # capacity): a window that overflows is halved and selected again
-            while True:
-                self._check(sel(_p(tbk), n, float(S.t_done), int(S.i_done),
-                                float(lim), _p(idx), cap, _p(cnt),
-                                stream_ptr()), "select")
-                count = int(cnt.item())
-                if count <= cap:
-                    break
-                # shrink in proportion to the overflow (breakpoints are dense
-                # and fairly even on image data), at least by half
-                base = max(S.t_done, 0.0)
-                lim = base + min(0.5, 0.8 * cap / count) * (lim - base)
+            # capacity): a window that overflows is shrunk and selected again,
+            # never to an empty one -- an empty answer would end the search
+            count = select(S, lim)
+            if count > cap:
+                count = shrink(S, lim, count)
             if count == 0:
                 return None
             tmp = scratch("sort", lib.nsol_lb_sort_tmp_bytes(

@@ -1,8 +1,14 @@
 """NumPy backend for nsol_amd.lbfgsb (TEST INFRASTRUCTURE): lets the CPU
 suite run the L-BFGS-B iteration logic of the product against
 scipy.optimize.minimize(method="L-BFGS-B") without a GPU.  The product uses
-nsol_amd.lbfgsb_device.DeviceBackend, whose kernels are held to this backend in
-the GPU tests."""
+nsol_amd.lbfgsb_device.DeviceBackend.  tests/test_lbfgsb_cauchy.py holds this
+backend's Cauchy search to a plain float64 reference of algorithm CP
+(test_numpy_cauchy_matches_reference), each device Cauchy stage -- set-up,
+select / sort / gather, the prefix-sum walk of a window (cumsum_walk's formulas),
+finish -- to the NumPy rule it implements (test_stage_*), the whole device search
+to that reference
+(test_device_cauchy_*), and the device's other length-n primitives to this
+backend (test_device_primitives_match_numpy_backend)."""
 import numpy as np
 
 
