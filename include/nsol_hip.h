@@ -808,6 +808,51 @@ int nsol_pair_stats_f64(const double *x, const double *y, int64_t n, double mx,
                         double my, double *result, double *ws, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * The remaining evaluation measures of similarity_measures.py:122-277
+ * (nsol_measures.hip).
+ *
+ * nsol_ssim_*: sum of skimage's SSIM map (compare_ssim with a box window of
+ *   `win` voxels along each of the ndim axes; win odd, 3..11) over the valid
+ *   windows, i.e. the map cropped by (win-1)/2 on every side of every axis.
+ *   result: device double[1].  C1, C2 = (K1 R)^2, (K2 R)^2; cov_norm = NP/(NP-1)
+ *   with NP = win^ndim.  One pass over x and y, float64 arithmetic for both
+ *   element types, fixed-order reduction (bit-reproducible).  Returns
+ *   NSOL_EINVAL when an extent is smaller than win.
+ *   ws: nsol_hip_reduce_ws_doubles() doubles.
+ * nsol_pair_range_*: result: device double[5] = { min x, max x, min y, max y,
+ *   number of non-finite values in x and y } (min / max over the finite ones).
+ *   ws: nsol_hip_reduce_ws_doubles() doubles.
+ * nsol_hist2d_*: joint histogram counts[ix * by + iy] (uint64, zeroed here) of
+ *   the pairs (x[i], y[i]) over increasing edges xedges[0..bx], yedges[0..by]
+ *   (device arrays of the element type: the comparison dtype).  The bin of v is
+ *   the last i with edges[i] <= v, v == edges[last] in the last bin: NumPy's
+ *   np.histogram / np.histogram2d for values inside the edges.  xscale, yscale:
+ *   bins / (last edge - first edge), the starting guess only.  bx * by <= 16384
+ *   count in LDS per workgroup, larger grids with global atomics.
+ * nsol_hist1d_*: the same for one array.
+ * ---------------------------------------------------------------------- */
+int nsol_ssim_f32(const float *x, const float *y, int ndim, int64_t nz, int64_t ny,
+                  int64_t nx, int win, double C1, double C2, double cov_norm,
+                  double *result, double *ws, void *stream);
+int nsol_ssim_f64(const double *x, const double *y, int ndim, int64_t nz, int64_t ny,
+                  int64_t nx, int win, double C1, double C2, double cov_norm,
+                  double *result, double *ws, void *stream);
+int nsol_pair_range_f32(const float *x, const float *y, int64_t n, double *result,
+                        double *ws, void *stream);
+int nsol_pair_range_f64(const double *x, const double *y, int64_t n, double *result,
+                        double *ws, void *stream);
+int nsol_hist2d_f32(const float *x, const float *y, int64_t n, const float *xedges,
+                    int bx, double xscale, const float *yedges, int by, double yscale,
+                    uint64_t *counts, void *stream);
+int nsol_hist2d_f64(const double *x, const double *y, int64_t n, const double *xedges,
+                    int bx, double xscale, const double *yedges, int by, double yscale,
+                    uint64_t *counts, void *stream);
+int nsol_hist1d_f32(const float *x, int64_t n, const float *edges, int bins,
+                    double scale, uint64_t *counts, void *stream);
+int nsol_hist1d_f64(const double *x, int64_t n, const double *edges, int bins,
+                    double scale, uint64_t *counts, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * Length-n pieces of a GPU-resident L-BFGS-B (nsol_amd/lbfgsb.py), replacing
  * the host loops of scipy.optimize.minimize(method="L-BFGS-B") behind
  * tikhonov_linear_solver.py:197-220.  Uniform bounds lo <= x <= hi (+-INFINITY

@@ -4,7 +4,12 @@ run_deconvolution.py:28-245 and the wiring of
 deconvolution_solver_parameter_study_interface.py:217-325, without plotting).
 
     python -m nsol_amd.application.run_deconvolution --observation blurred.png \\
-        --result out.png --blur 2 --reconstruction-type TVL2 --solver ADMM
+        --result out.png --blur 2 --reconstruction-type TVL2 --solver ADMM \\
+        [--reference gt.png] [--measures PSNR RMSE SSIM NCC NMI]
+
+With --reference, the measures are evaluated through an Observer on the flat
+iterates against the flat reference (as run_denoising does and as the
+reference's tool does) and printed as first -> last value.
 """
 import argparse
 import sys
@@ -17,7 +22,9 @@ from .. import admm_linear_solver as admm
 from .. import tikhonov_linear_solver as tk
 from .. import data_reader as dr
 from .. import data_writer as dw
+from .. import observer as Observer
 from ..proximal_operators import ProximalOperators as prox
+from ..similarity_measures import SimilarityMeasures
 
 
 def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
@@ -79,6 +86,10 @@ def main(argv=None):
         description="Run TK0L2/TK1L2/TVL2/HuberL2 deconvolution on an MI355X")
     ap.add_argument("--observation", required=True)
     ap.add_argument("--result", required=True)
+    ap.add_argument("--reference", required=False)
+    ap.add_argument("--measures", nargs="+",
+                    default=["PSNR", "RMSE", "SSIM", "NCC", "NMI"],
+                    choices=sorted(SimilarityMeasures.similarity_measures))
     ap.add_argument("--blur", type=float, default=1.2)
     ap.add_argument("--reconstruction-type", default="TVL2",
                     choices=["TK0L2", "TK1L2", "TVL2", "HuberL2"])
@@ -102,16 +113,33 @@ def main(argv=None):
     info = reader.get_image_sitk()
     spacing = np.ones(observed_nda.ndim) if info is None \
         else np.array(info.GetSpacing())
+    x_ref = None
+    if args.reference is not None:
+        ref_reader = dr.DataReader(args.reference)
+        ref_reader.read_data()
+        x_ref = ref_reader.get_data().flatten()
     for alpha in args.alpha:
         solver = build_solver(
             observed_nda, spacing, args.blur, args.reconstruction_type,
             args.solver, alpha, args.iterations, args.iter_max, args.rho,
             args.minimizer, args.data_loss, args.data_loss_scale, args.L2,
             args.verbose, np.dtype(args.dtype).type)
+        obs = None
+        if x_ref is not None:
+            obs = Observer.Observer()
+            obs.set_measures({
+                m: (lambda x, m=m:
+                    SimilarityMeasures.similarity_measures[m](x, x_ref))
+                for m in args.measures})
+            solver.set_observer(obs)
         solver.run()
         recon = np.array(solver.get_x().reshape(*observed_nda.shape))
         print("%s alpha=%g: %s" % (args.reconstruction_type, alpha,
                                    solver.get_computational_time()))
+        if obs is not None:
+            obs.compute_measures()
+            for m, vals in obs.get_measures().items():
+                print("  %s: %.6g -> %.6g" % (m, vals[0], vals[-1]))
         dw.DataWriter(recon, args.result, info).write_data()
     return 0
 

@@ -677,6 +677,198 @@ def pair_stats(x, y, mx=0.0, my=0.0):
     return res.cpu().numpy()
 
 
+# ------------------------------------------- SSIM, ranges, histograms ----
+# (nsol_measures.hip; the measures themselves are in similarity_measures.py)
+_ws_res = {}
+
+
+def _result(dev, n):
+    """Small per-device, per-stream device result buffer of n doubles."""
+    key = (dev.index, stream_ptr(), n)
+    if key not in _ws_res:
+        _ws_res[key] = torch.empty(n, dtype=torch.float64, device=dev)
+    return _ws_res[key]
+
+
+def ssim_sum(x, y, shape, win, C1, C2, cov_norm):
+    """Sum of the SSIM map over the valid windows of a box window `win` wide
+    along every axis of `shape` (nsol_ssim_*); x, y hold that volume.  Syncs."""
+    _same(x, y)
+    ndim, nz, ny, nx = dims3(shape)
+    if nz * ny * nx != x.numel():
+        raise ValueError("shape %s does not match %d elements" %
+                         (tuple(shape), x.numel()))
+    ws, _ = _workspace(x.device)
+    res = _result(x.device, 1)
+    _lib.check(_fn("ssim", x)(_p(x), _p(y), ndim, nz, ny, nx, int(win),
+                              float(C1), float(C2), float(cov_norm), _p(res),
+                              _p(ws), stream_ptr()), "nsol_ssim")
+    return float(res.item())
+
+
+def pair_range(x, y):
+    """(min x, max x, min y, max y, number of non-finite values) over the
+    finite values of x and y (nsol_pair_range_*).  Syncs."""
+    _same(x, y)
+    ws, _ = _workspace(x.device)
+    res = _result(x.device, 5)
+    _lib.check(_fn("pair_range", x)(_p(x), _p(y), x.numel(), _p(res), _p(ws),
+                                    stream_ptr()), "nsol_pair_range")
+    r = res.cpu().numpy()
+    return float(r[0]), float(r[1]), float(r[2]), float(r[3]), int(r[4])
+
+
+def numpy_dtype(x):
+    """NumPy dtype of a NumPy array or torch tensor."""
+    if isinstance(x, torch.Tensor):
+        return torch.empty(0, dtype=x.dtype).numpy().dtype
+    return np.asarray(x).dtype
+
+
+def _hist_dtype(dt):
+    """NumPy histograms bool data as uint8; float16 and complex are not covered."""
+    dt = np.dtype(dt)
+    if dt == np.bool_:
+        return np.dtype(np.uint8)
+    if dt.kind not in "iuf" or dt == np.float16 or dt.itemsize > 8:
+        raise TypeError("histograms of %s data are not supported" % dt)
+    return dt
+
+
+def _as_compare(t, edges):
+    """t in the comparison dtype of `edges` (float32 or float64; exact casts)."""
+    td = torch.float32 if edges.dtype == np.float32 else torch.float64
+    if edges.dtype not in (np.float32, np.float64):
+        raise TypeError("histogram edges of dtype %s are not supported" % edges.dtype)
+    return t if t.dtype == td else t.to(td).contiguous()
+
+
+def _edges_dev(e, t):
+    return torch.from_numpy(np.ascontiguousarray(e)).to(t.device)
+
+
+def _scale(e):
+    return (len(e) - 1) / (float(e[-1]) - float(e[0]))
+
+
+def hist1d_counts(x, edges):
+    """np.histogram counts (int64) of the values of device tensor x over the
+    increasing edges (NumPy array; its dtype is the comparison dtype).  Every
+    value must lie inside [edges[0], edges[-1]].  Syncs."""
+    _chk(x)
+    x = _as_compare(x.reshape(-1), edges)
+    e = _edges_dev(edges, x)
+    out = torch.empty(len(edges) - 1, dtype=torch.int64, device=x.device)
+    _lib.check(_fn("hist1d", x)(_p(x), x.numel(), _p(e), len(edges) - 1,
+                                _scale(edges), _p(out), stream_ptr()),
+               "nsol_hist1d")
+    return out.cpu().numpy()
+
+
+def hist2d_counts(x, y, xedges, yedges):
+    """np.histogram2d counts (int64, shape (bx, by)) of the pairs (x[i], y[i])
+    over increasing edges of one dtype (the comparison dtype).  Syncs."""
+    _chk(x)
+    _chk(y)
+    if xedges.dtype != yedges.dtype:
+        raise TypeError("edges of one comparison dtype expected")
+    x = _as_compare(x.reshape(-1), xedges)
+    y = _as_compare(y.reshape(-1), yedges)
+    _same(x, y)
+    ex, ey = _edges_dev(xedges, x), _edges_dev(yedges, x)
+    bx, by = len(xedges) - 1, len(yedges) - 1
+    out = torch.empty(bx * by, dtype=torch.int64, device=x.device)
+    _lib.check(_fn("hist2d", x)(_p(x), _p(y), x.numel(), _p(ex), bx,
+                                _scale(xedges), _p(ey), by, _scale(yedges),
+                                _p(out), stream_ptr()), "nsol_hist2d")
+    return out.cpu().numpy().reshape(bx, by)
+
+
+def _float_tensor(t):
+    return t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float64)
+
+
+def _int_bins(bins, n):
+    b = tuple(np.atleast_1d(bins).tolist()) if np.ndim(bins) else (bins,) * n
+    if len(b) != n or not all(isinstance(v, (int, np.integer)) for v in b):
+        raise ValueError("bins: an integer (or one per axis) is supported; "
+                         "explicit bin edges are not")
+    if any(v < 1 for v in b):
+        raise ValueError("bins must be positive")
+    return tuple(int(v) for v in b)
+
+
+def _check_range(r):
+    if r[4]:
+        raise ValueError("autodetected range of the data is not finite")
+
+
+def hist_edges(lo, hi, dtype, bins):
+    """np.histogram's edges for data of `dtype` with minimum lo and maximum hi
+    (exact in float64 for every supported dtype): NumPy builds them itself from
+    a two-point array of that dtype, so they are bit-identical to its own."""
+    return np.histogram_bin_edges(np.array([lo, hi], dtype), bins)
+
+
+def hist2d_edges(xrange_, yrange_, dx, dy, bins):
+    """np.histogram2d's (xedges, yedges) for data of dtypes dx, dy with the
+    given (min, max): NumPy's own, from two-point arrays (both axes in the
+    promoted dtype)."""
+    _, ex, ey = np.histogram2d(np.array(xrange_, dx), np.array(yrange_, dy), bins)
+    return ex, ey
+
+
+def histogram1d(x, bins=100, dtype=None):
+    """(counts, edges) of np.histogram(a, bins) for the array a held by the
+    device tensor x; dtype: a's NumPy dtype (fixes the edges' dtype), default
+    x's own."""
+    _chk(x)
+    (bins,) = _int_bins(bins, 1)
+    dt = _hist_dtype(dtype if dtype is not None else numpy_dtype(x))
+    x = _float_tensor(x).reshape(-1)
+    lo, hi, _, _, bad = pair_range(x, x)
+    _check_range((0, 0, 0, 0, bad))
+    edges = hist_edges(lo, hi, dt, bins)
+    return hist1d_counts(x, edges), edges
+
+
+def histogram2d(x, y, bins=100, dtypes=None, marginals=False):
+    """(counts, xedges, yedges) of np.histogram2d(a, b, bins) for the arrays a,
+    b held by the device tensors x, y (dtypes: their NumPy dtypes, default the
+    tensors' own).  marginals=True also returns the two 1-D np.histogram counts
+    of a and b: the joint histogram's row / column sums where NumPy's 1-D edges
+    are the joint ones (one pass), else a pass in each array's own dtype."""
+    _chk(x)
+    _chk(y)
+    bx, by = _int_bins(bins, 2)
+    if x.numel() != y.numel():
+        raise ValueError("x and y differ in length")
+    dx, dy = dtypes if dtypes is not None else (numpy_dtype(x), numpy_dtype(y))
+    dx, dy = _hist_dtype(dx), _hist_dtype(dy)
+    xf, yf = _float_tensor(x).reshape(-1), _float_tensor(y).reshape(-1)
+    common = torch.float32 if (xf.dtype == yf.dtype == torch.float32) else torch.float64
+    xc = xf if xf.dtype == common else xf.to(common)
+    yc = yf if yf.dtype == common else yf.to(common)
+    r = pair_range(xc, yc)
+    _check_range(r)
+    xedges, yedges = hist2d_edges(r[0:2], r[2:4], dx, dy, (bx, by))
+    counts = hist2d_counts(xc, yc, xedges, yedges)
+    if not marginals:
+        return counts, xedges, yedges
+    hx = hy = None
+    ex1 = hist_edges(r[0], r[1], dx, bx)
+    ey1 = hist_edges(r[2], r[3], dy, by)
+    if ex1.dtype == xedges.dtype and np.array_equal(ex1, xedges):
+        hx = counts.sum(axis=1)
+    else:
+        hx = hist1d_counts(xf, ex1)
+    if ey1.dtype == yedges.dtype and np.array_equal(ey1, yedges):
+        hy = counts.sum(axis=0)
+    else:
+        hy = hist1d_counts(yf, ey1)
+    return counts, xedges, yedges, hx, hy
+
+
 def loss_eval(f2, loss, f_scale=1.0, huber_gamma=1.345):
     """Element-wise (rho(f2), rho'(f2))."""
     _chk(f2)

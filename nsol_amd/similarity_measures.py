@@ -1,11 +1,20 @@
-"""Evaluation measures on the GPU (drop-in for the
-reduction-type measures of nsol/similarity_measures.py:26-120): SSD, SAD, MAE,
-MSE, RMSE, PSNR, NCC.  x, x_ref: NumPy arrays or torch HIP tensors of equal
-shape.  One fused pass (nsol_pair_stats_*) yields every sum; NCC takes a
-second, mean-centred pass for accuracy.  SSIM, MI, NMI and Dice of the
-reference are evaluation-only extras and are not provided.
+"""Evaluation measures on the GPU (drop-in for
+nsol/similarity_measures.py): SSD, SAD, MAE, MSE, RMSE, PSNR, NCC, SSIM, the
+Shannon and joint entropies, MI, NMI and Dice.  x, x_ref: NumPy arrays or torch
+HIP tensors of equal shape.
+
+One fused pass (nsol_pair_stats_*) yields the sums of the reduction-type
+measures; NCC takes a second, mean-centred pass for accuracy.  SSIM is
+skimage's compare_ssim with its defaults (box window of 7 along every axis of
+the input as given, K1 = 0.01, K2 = 0.03, sample covariance, data_range from
+the dtype of x) in one pass (nsol_ssim_*).  The entropies take NumPy's integer
+histogram counts from the device (nsol_pair_range_* fixes the edges,
+nsol_hist2d_* / nsol_hist1d_* count) and evaluate the reference's expression
+on the host.  The histogram measures keep the callers' dtypes: NumPy's bins
+depend on them.
 """
 import numpy as np
+import torch
 
 from . import ops
 from .device import is_device_tensor, to_device
@@ -24,6 +33,58 @@ def _pair(x, x_ref):
         np.asarray(x_ref, dtype=np.float64).reshape(-1), np.float64)
     dx = dx.contiguous().view(-1)
     return dx, dr.to(dx.dtype).contiguous().view(-1)
+
+
+def _upload(x):
+    """Device tensor of x: float32 stays float32, everything else float64
+    (exact for the integer types)."""
+    if is_device_tensor(x):
+        t = x.contiguous()
+        return t if t.dtype in (torch.float32, torch.float64) \
+            else t.to(torch.float64)
+    a = np.asarray(x)
+    return to_device(a, np.float32 if a.dtype == np.float32 else np.float64)
+
+
+def _common(a, b):
+    """Both tensors in one dtype: float32 if both are, else float64 (exact)."""
+    if a.dtype == b.dtype:
+        return a, b
+    f64 = torch.float64
+    return a.to(f64).contiguous(), b.to(f64).contiguous()
+
+
+def _dtype_range(dt):
+    """skimage's dtype_range[dt][1] - dtype_range[dt][0]."""
+    dt = np.dtype(dt)
+    if dt == np.bool_:
+        return 1.0
+    if dt.kind == "f":
+        return 2.0
+    if dt.kind in "iu":
+        info = np.iinfo(dt)
+        return float(info.max) - float(info.min)
+    raise ValueError("no default data_range for dtype %s" % dt)
+
+
+def _entropy(hist):
+    """The reference's expression (similarity_measures.py:157-161)."""
+    prob = hist / float(np.sum(hist))
+    return - sum([p * np.log(p) for p in prob.flatten() if p != 0])
+
+
+def _histograms(x, x_ref, bins):
+    """NumPy's histogram counts (x, x_ref, joint) of the two arrays, each in
+    its own dtype, from one joint pass (plus 1-D passes where the dtypes
+    give the 1-D histograms other edges than the joint one)."""
+    if tuple(x.shape) != tuple(x_ref.shape):
+        raise ValueError("Input data shapes do not match")
+    if np.ndim(bins) != 0:
+        raise ValueError("bins: only an integer number of bins is supported")
+    dx, dy = ops.numpy_dtype(x), ops.numpy_dtype(x_ref)
+    joint, _, _, hx, hy = ops.histogram2d(_upload(x), _upload(x_ref), bins,
+                                          dtypes=(dx, dy), marginals=True)
+    return hx, hy, joint
 
 
 class SimilarityMeasures(object):
@@ -69,6 +130,92 @@ class SimilarityMeasures(object):
         sy = np.sqrt(st[2] / (n - 1.0))
         return float(st[0] / (n * sx * sy))
 
+    @staticmethod
+    def structural_similarity(x, x_ref, win_size=7, data_range=None,
+                              gaussian_weights=False, gradient=False,
+                              full=False):
+        """skimage.measure.compare_ssim(x, x_ref) (the reference's call):
+        mean SSIM over the valid box windows of win_size along every axis."""
+        if gaussian_weights or gradient or full:
+            raise NotImplementedError(
+                "SSIM: gaussian_weights, gradient and full are not supported")
+        shape = tuple(x.shape)
+        if shape != tuple(x_ref.shape):
+            raise ValueError("Input images must have the same dimensions.")
+        if not 1 <= len(shape) <= 3:
+            raise NotImplementedError("SSIM: 1-D, 2-D and 3-D inputs only")
+        if win_size % 2 != 1:
+            raise ValueError("Window size must be odd.")
+        if any(n < win_size for n in shape):
+            raise ValueError("win_size exceeds image extent.")
+        if not 3 <= win_size <= 11:
+            raise NotImplementedError("SSIM: win_size 3, 5, 7, 9 or 11 only")
+        if data_range is None:
+            data_range = _dtype_range(ops.numpy_dtype(x))
+        npix = win_size ** len(shape)
+        cov_norm = npix / (npix - 1.0)
+        C1 = (0.01 * data_range) ** 2
+        C2 = (0.03 * data_range) ** 2
+        a, b = _common(_upload(x), _upload(x_ref))
+        total = ops.ssim_sum(a.view(-1), b.view(-1), shape, win_size, C1, C2,
+                             cov_norm)
+        count = 1
+        for n in shape:
+            count *= n - win_size + 1
+        return total / count
+
+    @staticmethod
+    def shannon_entropy(x, bins=100):
+        if np.ndim(bins) != 0:
+            raise ValueError("bins: only an integer number of bins is supported")
+        counts, _ = ops.histogram1d(_upload(x).view(-1), bins,
+                                    dtype=ops.numpy_dtype(x))
+        return _entropy(counts)
+
+    @staticmethod
+    def joint_entropy(x, x_ref, bins=100):
+        if tuple(x.shape) != tuple(x_ref.shape):
+            raise ValueError("Input data shapes do not match")
+        joint, _, _ = ops.histogram2d(
+            _upload(x), _upload(x_ref), bins,
+            dtypes=(ops.numpy_dtype(x), ops.numpy_dtype(x_ref)))
+        return _entropy(joint)
+
+    @staticmethod
+    def mutual_information(x, x_ref, bins=100):
+        hx, hy, joint = _histograms(x, x_ref, bins)
+        mi = _entropy(hx)
+        mi += _entropy(hy)
+        mi -= _entropy(joint)
+        return mi
+
+    @staticmethod
+    def normalized_mutual_information(x, x_ref, bins=100):
+        hx, hy, joint = _histograms(x, x_ref, bins)
+        nmi = _entropy(hx)
+        nmi += _entropy(hy)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nmi /= _entropy(joint)       # constant inputs: 0/0 = nan
+        return nmi
+
+    @staticmethod
+    def dice_score(x, x_ref):
+        """2 |x and x_ref| / (|x| + |x_ref|) of two boolean masks."""
+        if ops.numpy_dtype(x) != np.bool_ or ops.numpy_dtype(x_ref) != np.bool_:
+            raise ValueError("x and x_ref need to be of type boolean")
+        if tuple(x.shape) != tuple(x_ref.shape):
+            raise ValueError("Input data shapes do not match")
+        f32 = torch.float32
+
+        def mask(m):
+            if is_device_tensor(m):
+                return m.contiguous().view(-1).to(f32)
+            return to_device(np.asarray(m, dtype=np.float32).reshape(-1),
+                             np.float32)
+        st = ops.pair_stats(mask(x), mask(x_ref))   # exact integer sums
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.float64(2.0 * st[0]) / np.float64(st[6] + st[7])
+
     SSD = sum_of_squared_differences
     SAD = sum_of_absolute_differences
     MAE = mean_absolute_error
@@ -76,6 +223,9 @@ class SimilarityMeasures(object):
     RMSE = root_mean_square_error
     PSNR = peak_signal_to_noise_ratio
     NCC = normalized_cross_correlation
+    SSIM = structural_similarity
+    MI = mutual_information
+    NMI = normalized_mutual_information
 
 
 SimilarityMeasures.similarity_measures = {
@@ -85,5 +235,12 @@ SimilarityMeasures.similarity_measures = {
     "MSE": SimilarityMeasures.mean_squared_error,
     "RMSE": SimilarityMeasures.root_mean_square_error,
     "PSNR": SimilarityMeasures.peak_signal_to_noise_ratio,
+    "SSIM": SimilarityMeasures.structural_similarity,
     "NCC": SimilarityMeasures.normalized_cross_correlation,
+    "MI": SimilarityMeasures.mutual_information,
+    "NMI": SimilarityMeasures.normalized_mutual_information,
 }
+
+# values that stand for an undefined measure (the reference's UNDEF)
+SimilarityMeasures.UNDEF = {k: np.nan for k in (
+    "SSD", "MAE", "MSE", "RMSE", "PSNR", "SSIM", "NCC", "MI", "NMI")}
