@@ -853,6 +853,46 @@ int nsol_hist1d_f64(const double *x, int64_t n, const double *edges, int bins,
                     double scale, uint64_t *counts, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * Observation of a solver iterate (nsol_observe.hip; nsol_amd/observer.py).
+ *
+ * nsol_observe_*: the sums of one observation point in one pass over x, as
+ *   the float64 host path would form them from Solver.get_x(): every voxel is
+ *   xs = (double)(x * (T)x_scale), the product rounded in the element type
+ *   (nsol_scale_*).  x holds an [nz][ny][nx] volume whose rows start `pitch`
+ *   elements apart (pitch <= 0: nx, contiguous); y (contiguous, element type T,
+ *   or double when y_f64) is read only for NSOL_OBS_PAIR.  Sums in float64,
+ *   fixed-order two-stage reduction (bit-reproducible); row: device double[9] =
+ *     { sum (xs-y)^2, sum |xs-y|, sum xs, sum (xs-ybar)(y-ybar),
+ *       sum (xs-ybar)^2,                                  (NSOL_OBS_PAIR)
+ *       sum |D xs|, sum huber(|D xs|^2) / (2 gamma), sum |D xs|^2,
+ *                                                         (NSOL_OBS_GRAD; the
+ *       Huber sum only with NSOL_OBS_HUBER as well)
+ *       sum xs^2 }                                        (NSOL_OBS_SQ)
+ *   with D the forward differences of nsol_grad_* (constant boundaries, the
+ *   inverse spacings wx, wy, wz, ndim components) and huber the loss of
+ *   nsol_loss_eval_* with f_scale = 1; sums of groups not asked for are 0.
+ *   ws: nsol_hip_reduce_ws_doubles() doubles.
+ * nsol_observe_widen_*: out[i] = (double)(x[i] * (T)x_scale) in contiguous
+ *   order from the (pitched) volume x: the float64 iterate the host path sees.
+ * ---------------------------------------------------------------------- */
+#define NSOL_OBS_PAIR 1
+#define NSOL_OBS_GRAD 2
+#define NSOL_OBS_SQ 4
+#define NSOL_OBS_HUBER 8
+int nsol_observe_f32(const float *x, double x_scale, const void *y, int y_f64,
+                     double ybar, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                     int64_t pitch, double wx, double wy, double wz, double gamma,
+                     int flags, double *row, double *ws, void *stream);
+int nsol_observe_f64(const double *x, double x_scale, const void *y, int y_f64,
+                     double ybar, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                     int64_t pitch, double wx, double wy, double wz, double gamma,
+                     int flags, double *row, double *ws, void *stream);
+int nsol_observe_widen_f32(double *out, const float *x, double x_scale, int64_t nz,
+                           int64_t ny, int64_t nx, int64_t pitch, void *stream);
+int nsol_observe_widen_f64(double *out, const double *x, double x_scale, int64_t nz,
+                           int64_t ny, int64_t nx, int64_t pitch, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * Length-n pieces of a GPU-resident L-BFGS-B (nsol_amd/lbfgsb.py), replacing
  * the host loops of scipy.optimize.minimize(method="L-BFGS-B") behind
  * tikhonov_linear_solver.py:197-220.  Uniform bounds lo <= x <= hi (+-INFINITY

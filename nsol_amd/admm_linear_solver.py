@@ -54,8 +54,9 @@ class ADMMLinearSolver(LinearSolver):
 
     # ------------------------------------------------------------------
     def _run(self):
-        if self._observer is not None:
-            self._observer.add_x(self.get_x())
+        # (a device-mode observer, observer.py, looks at x after each x-update
+        # without a copy to the host and keeps the one-pass outer step)
+        self._observe_start(self._iterations)
 
         x = self._x0_device().clone()
         self._warm = None
@@ -116,8 +117,7 @@ class ADMMLinearSolver(LinearSolver):
                 # (admm :208-216 after the last x-update changes v and w only, which
                 # nobody reads any more: not done)
                 self._x = x
-                if self._observer is not None:
-                    self._observer.add_x(self.get_x())
+                self._observe_iteration(i + 1, x)
                 break
             if fused and prescale and USE_ONE_PASS_OUTER_STEP:
                 start = self._one_pass_outer_step(x, w, c, breg, desc, thr, sa)
@@ -145,9 +145,14 @@ class ADMMLinearSolver(LinearSolver):
                 if c is not None:
                     breg = ops.lincomb2(1.0, breg, 1.0, c, out=breg)
             self._x = x
-            if self._observer is not None:
-                self._observer.add_x(self.get_x())
+            self._observe_iteration(i + 1, x)
         self._x = x
+
+    def _observe_iteration(self, it, x):
+        if self._observing_on_device():
+            self._observe_at(it, x)
+        elif self._observer is not None:
+            self._observer.add_x(self.get_x())
 
     _warm = None
     _inner_log = ()
@@ -165,7 +170,7 @@ class ADMMLinearSolver(LinearSolver):
         ("g", "gg", "fill") plus the new w and the sum of squares of the right-hand
         side it stands for."""
         import torch
-        if self._observer is not None:
+        if self._observer is not None and self._observer.get_keep_iterates():
             return None
         b = self._dev(self._b)
         atb = tk._adjoint_of_data(self._A_adj, BridgedCallable(self._A_adj, self._dtype),

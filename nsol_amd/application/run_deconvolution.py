@@ -105,6 +105,10 @@ def main(argv=None):
     ap.add_argument("--dtype", default="float32",
                     choices=["float32", "float64"])
     ap.add_argument("--verbose", type=int, default=0)
+    ap.add_argument("--observe-every", type=int, default=None, metavar="K",
+                    help="evaluate the measures on the device every K "
+                         "iterations (and at the last) instead of on a host "
+                         "copy of every iterate")
     args = ap.parse_args(argv)
 
     reader = dr.DataReader(args.observation)
@@ -126,7 +130,8 @@ def main(argv=None):
             args.verbose, np.dtype(args.dtype).type)
         obs = None
         if x_ref is not None:
-            obs = Observer.Observer()
+            obs = Observer.Observer() if args.observe_every is None else \
+                Observer.Observer(keep_iterates=False, every=args.observe_every)
             obs.set_measures({
                 m: (lambda x, m=m:
                     SimilarityMeasures.similarity_measures[m](x, x_ref))

@@ -72,6 +72,10 @@ def main(argv=None):
     ap.add_argument("--dtype", default="float32",
                     choices=["float32", "float64"])
     ap.add_argument("--verbose", type=int, default=0)
+    ap.add_argument("--observe-every", type=int, default=None, metavar="K",
+                    help="evaluate the measures on the device every K "
+                         "iterations (and at the last) instead of on a host "
+                         "copy of every iterate")
     args = ap.parse_args(argv)
 
     if len(args.alpha) == 1 and args.result is None:
@@ -94,7 +98,8 @@ def main(argv=None):
                               alg_type=args.alg_type)
         obs = None
         if x_ref is not None:
-            obs = Observer.Observer()
+            obs = Observer.Observer() if args.observe_every is None else \
+                Observer.Observer(keep_iterates=False, every=args.observe_every)
             obs.set_measures({
                 m: (lambda x, m=m:
                     SimilarityMeasures.similarity_measures[m](x, x_ref))

@@ -690,20 +690,84 @@ def _result(dev, n):
     return _ws_res[key]
 
 
-def ssim_sum(x, y, shape, win, C1, C2, cov_norm):
+def ssim_sum(x, y, shape, win, C1, C2, cov_norm, out=None):
     """Sum of the SSIM map over the valid windows of a box window `win` wide
-    along every axis of `shape` (nsol_ssim_*); x, y hold that volume.  Syncs."""
+    along every axis of `shape` (nsol_ssim_*); x, y hold that volume.  Syncs;
+    out (a float64 device tensor of one element): the sum is written there and
+    nothing is read back (returns out)."""
     _same(x, y)
     ndim, nz, ny, nx = dims3(shape)
     if nz * ny * nx != x.numel():
         raise ValueError("shape %s does not match %d elements" %
                          (tuple(shape), x.numel()))
     ws, _ = _workspace(x.device)
-    res = _result(x.device, 1)
+    res = _result(x.device, 1) if out is None else out
+    if res.dtype != torch.float64 or res.numel() < 1:
+        raise ValueError("out: a float64 device tensor of one element")
     _lib.check(_fn("ssim", x)(_p(x), _p(y), ndim, nz, ny, nx, int(win),
                               float(C1), float(C2), float(cov_norm), _p(res),
                               _p(ws), stream_ptr()), "nsol_ssim")
+    if out is not None:
+        return _wrote(out)
     return float(res.item())
+
+
+# ------------------------------------------------------ observation ----
+# (nsol_observe.hip; the observer itself is observer.py)
+OBS_PAIR, OBS_GRAD, OBS_SQ, OBS_HUBER = 1, 2, 4, 8
+OBS_SUMS = 9
+
+
+def observe(x, x_scale, row, shape, y=None, ybar=0.0, w=(1.0, 1.0, 1.0),
+            ndim=None, gamma=0.05, flags=0, pitch=0):
+    """The 9 sums of nsol_observe_* of x * x_scale into the float64 device
+    tensor `row` (at least 9 elements); x holds the volume `shape` with its rows
+    `pitch` elements apart (0: contiguous).  y: contiguous reference of the
+    volume's size, x's dtype or float64 (OBS_PAIR).  ndim: gradient components
+    (OBS_GRAD; default len(shape)).  Does not synchronise."""
+    _chk(x)
+    _chk(row)
+    gdim, nz, ny, nx = dims3(shape)
+    ndim = gdim if ndim is None else int(ndim)
+    rows = nz * ny
+    if x.numel() != rows * (pitch if pitch else nx) or (pitch and pitch < nx):
+        raise ValueError("x does not hold a %s volume at pitch %d" %
+                         (tuple(shape), pitch))
+    if row.dtype != torch.float64 or row.numel() < OBS_SUMS:
+        raise ValueError("row: a float64 device tensor of %d elements" % OBS_SUMS)
+    y_f64 = 0
+    if flags & OBS_PAIR:
+        _chk(y)
+        if y.numel() != rows * nx or y.dtype not in (x.dtype, torch.float64):
+            raise ValueError("y: %d elements of %s or float64" % (rows * nx, x.dtype))
+        y_f64 = int(y.dtype == torch.float64)
+    else:
+        y = None
+    ws, _ = _workspace(x.device)
+    _lib.check(_fn("observe", x)(
+        _p(x), float(x_scale), _p(y), y_f64, float(ybar), ndim, nz, ny, nx,
+        int(pitch), float(w[0]), float(w[1]), float(w[2]), float(gamma), int(flags),
+        _p(row), _p(ws), stream_ptr()), "nsol_observe")
+    return _wrote(row)
+
+
+def observe_widen(x, x_scale, shape, pitch=0, out=None):
+    """(double)(x * (T)x_scale) as a contiguous float64 device tensor: the
+    iterate Solver.get_x() hands the host, without leaving the device."""
+    _chk(x)
+    _, nz, ny, nx = dims3(shape)
+    if x.numel() != nz * ny * (pitch if pitch else nx) or (pitch and pitch < nx):
+        raise ValueError("x does not hold a %s volume at pitch %d" %
+                         (tuple(shape), pitch))
+    if out is None:
+        out = torch.empty(nz * ny * nx, dtype=torch.float64, device=x.device)
+    _chk(out)
+    if out.dtype != torch.float64 or out.numel() != nz * ny * nx:
+        raise ValueError("out: %d float64 elements" % (nz * ny * nx))
+    _lib.check(_fn("observe_widen", x)(_p(out), _p(x), float(x_scale), nz, ny, nx,
+                                       int(pitch), stream_ptr()),
+               "nsol_observe_widen")
+    return _wrote(out)
 
 
 def pair_range(x, y):

@@ -152,8 +152,7 @@ class PrimalDualSolver(Solver):
                     data_scale=df[2])
 
     def _run(self):
-        if self._observer is not None:
-            self._observer.add_x(self.get_x())
+        self._points = self._observe_start(self._iterations)
         lmbda = 1. / self._alpha
         sig, ta, th = step_schedule(self._alg_type, self._L2, lmbda,
                                     self._iterations)
@@ -173,9 +172,13 @@ class PrimalDualSolver(Solver):
         p = [torch.empty(plan["dim"] * n, dtype=x.dtype, device=x.device)
              for _ in range(2)]
         bt = scaled_data_on_device(plan["data"], plan["data_scale"], x)
+        # a device-mode observer (observer.py) keeps the multi-iteration kernels
+        # and the row pitch: the run is enqueued in chunks between its
+        # observation points, nsol_observe_* reads the pitched x as it is
+        unobserved = self._observer is None or self._points is not None
         pitch = ops.row_pitch(plan["shape"], x) if USE_ROW_PITCH and \
             n >= PITCH_MIN_VOXELS and self._iterations > 1 and \
-            self._observer is None and not self._verbose else 0
+            unobserved and not self._verbose else 0
         if pitch:
             # rows that are not whole 16-byte vectors (511^3, 181 x 217 x 181 ...): the
             # run's arrays hold them at a pitch of whole vectors -- aligned accesses
@@ -189,21 +192,18 @@ class PrimalDualSolver(Solver):
                   torch.empty(plan["dim"] * np_, dtype=x.dtype, device=x.device)]
             btq = ops.to_pitched(bt, shape, pitch)
             try:
-                ops.pd_run(xbq[0], xbq[1], xq, btq, pq[0], pq[1], shape, plan["w"],
-                           lmbda, sig, ta, th, True, plan["gamma"], plan["flags"],
-                           x_alt=torch.zeros_like(xq), swap_ok=True, pitch=pitch)
+                self._chunks(xbq, xq, btq, pq, plan, lmbda, sig, ta, th,
+                             torch.zeros_like(xq), pitch)
                 self._x = ops.from_pitched(xq, shape, pitch)
                 return
             except ValueError:
                 # the pitched entry declined (NSOL_EINVAL: the ragged-row form is
                 # switched off, knob pd_rag): the contiguous arrays are untouched
                 del xq, xbq, pq, btq
-        if self._observer is None and not self._verbose:
+        if unobserved and not self._verbose:
             # scratch for the two-iterations-per-pass kernel (x ping-pong)
             x_alt = torch.empty_like(x) if self._iterations > 1 else None
-            ops.pd_run(xbar[0], xbar[1], x, bt, p[0], p[1], plan["shape"],
-                       plan["w"], lmbda, sig, ta, th, True, plan["gamma"],
-                       plan["flags"], x_alt=x_alt, swap_ok=True)
+            self._chunks(xbar, x, bt, p, plan, lmbda, sig, ta, th, x_alt, 0)
             self._x = x
             return
         for i in range(self._iterations):      # observed / verbose: stepwise
@@ -218,9 +218,42 @@ class PrimalDualSolver(Solver):
                               plan["shape"], plan["w"], sig[i], hden, ta[i],
                               ta[i] * lmbda, th[i], plan["flags"])
             self._x = x
-            if self._observer is not None:
-                self._observer.add_x(self.get_x())
+            self._observe_iteration(i + 1, x)
         self._x = x
+
+    _points = None
+
+    def _chunks(self, xbar, x, bt, p, plan, lmbda, sig, ta, th, x_alt, pitch):
+        """ops.pd_run over the whole run, or, with a device-mode observer, over
+        the stretches between its observation points (the multi-iteration
+        kernels are bit-identical to a launch per iteration, so the chunks
+        change no bit of x): each chunk starts from the xbar / p slot the
+        previous one ended in, p counts as zero in the first chunk only."""
+        pts = self._points
+        bounds = [0, self._iterations] if pts is None else pts
+        layout = (plan["shape"], pitch) if pitch else None
+        k, first = 0, True
+        for a, b in zip(bounds[:-1], bounds[1:]):
+            slot = ops.pd_run(xbar[k], xbar[1 - k], x, bt, p[k], p[1 - k],
+                              plan["shape"], plan["w"], lmbda, sig[a:b], ta[a:b],
+                              th[a:b], first, plan["gamma"], plan["flags"],
+                              x_alt=x_alt, swap_ok=True, pitch=pitch)
+            k = k if slot == 0 else 1 - k
+            first = False
+            if pts is not None:
+                if ops._pending_runs:
+                    # (a persistent chunk that timed out is repeated here, before
+                    # its x is observed)
+                    ops.settle_persist_runs()
+                self._observe_at(b, x, layout)
+
+    def _observe_iteration(self, it, x):
+        if self._observer is None:
+            return
+        if self._points is None:
+            self._observer.add_x(self.get_x())
+        else:
+            self._observe_at(it, x)
 
     # ------------------------------------------------------------------
     def _run_generic(self, lmbda, sig, ta, th):
@@ -251,8 +284,7 @@ class PrimalDualSolver(Solver):
             xbar = ops.lincomb2(1.0, x_new, th[i], d)
             x = x_new
             self._x = x
-            if self._observer is not None:
-                self._observer.add_x(self.get_x())
+            self._observe_iteration(i + 1, x)
         self._x = x
         self._execution = "device" if all(
             c.on_device for c in (B, Bc, pg, pf)) else "host"
@@ -280,8 +312,7 @@ class PrimalDualSolver(Solver):
             xbar = ops.extrapolate(x_new, x, th[i], out=xbar)
             x = x_new
             self._x = x
-            if self._observer is not None:
-                self._observer.add_x(self.get_x())
+            self._observe_iteration(i + 1, x)
         self._x = x
         self._execution = "device" if pf.on_device else "host"
 

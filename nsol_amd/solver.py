@@ -103,6 +103,8 @@ class Solver(object):
             # (a persistent-kernel run that timed out is repeated here, before anyone
             # can consume its result on the device or on the host)
             ops.settle_persist_runs(synchronize=False)
+            if self._observing_on_device():
+                self._observer._finish()      # the board, read once
         # (_borrow / _sync_after_run = False: an inner solve of an outer solver of this
         # package, which goes on enqueueing behind it and synchronises at the end of ITS
         # run: draining the device here left it idle while the outer loop prepared its
@@ -117,6 +119,50 @@ class Solver(object):
                 self.get_computational_time())
 
     _sync_after_run = True
+
+    # ---- observation of the iterates on the device (observer.py, device mode)
+    def _observing_on_device(self):
+        o = self._observer
+        return o is not None and not o.get_keep_iterates()
+
+    def _observe_begin(self, iterations):
+        """Observation points of a device-mode observer for a run of
+        `iterations` iterations (None without one)."""
+        if not self._observing_on_device():
+            return None
+        n = int(self._x0_host.size if self._x0_host is not None
+                else self._x0_dev.numel())
+        return self._observer._begin(n, iterations)
+
+    def _observe_start(self, iterations):
+        """The observation of the start vector: a host copy for an observer
+        that keeps iterates, the device observation of point 0 otherwise.
+        Returns the observation points (None when not in device mode)."""
+        if self._observer is None:
+            return None
+        if not self._observing_on_device():
+            self._observer.add_x(self.get_x())
+            return None
+        pts = self._observe_begin(iterations)
+        self._observe_at(0)
+        return pts
+
+    def _observe_at(self, it, x=None, layout=None):
+        """Device observation of iteration `it` (ignored unless it is a point):
+        x the unscaled device iterate, default what get_x() would return."""
+        scale = self._x_scale
+        if x is None:
+            if self._x is None and self._x0_host is not None:
+                # get_x() returns x0 itself here: observe it in its own dtype
+                # (exact), and let the upload serve as the solver's x0 as well
+                raw = to_device(self._x0_host.reshape(-1),
+                                self._x0_host.dtype.type)
+                if self._x0_dev is None and self._x0_host.dtype == self._dtype:
+                    self._x0_dev = ops.scale(raw, self._x_scale, divide=True)
+                x, scale = raw, 1.0
+            else:
+                x = self._x if self._x is not None else self._x0_device()
+        self._observer._observe(it, x, scale, layout)
 
     def _run(self):
         raise NotImplementedError

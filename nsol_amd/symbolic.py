@@ -95,3 +95,43 @@ def trace_prox(fn, n):
     if not isinstance(out, Sym) or out.desc is None:
         return None
     return out.desc
+
+
+class MeasureDesc(object):
+    """What an evaluation measure of similarity_measures.py / prior_measures.py
+    answers the probe with (observer.py recognises measure lambdas by it).
+    kind: the measure ("SSD", ..., "TV", "Huber", "NMI", ...); shape: the
+    probe's shape as the measure saw it; ref: the reference array as given;
+    grad: trace_operator's ("grad", op, shape) of the gradient callable;
+    gamma, bins, ssim: the measure's own arguments."""
+
+    def __init__(self, kind, shape, ref=None, grad=None, gamma=None, bins=None,
+                 ssim=None):
+        self.kind = kind
+        self.shape = tuple(shape)
+        self.ref = ref
+        self.grad = grad
+        self.gamma = gamma
+        self.bins = bins
+        self.ssim = ssim
+
+    def __repr__(self):
+        return "MeasureDesc(%s, shape=%s)" % (self.kind, self.shape)
+
+
+def measure_probe(kind, x, x_ref=None, **kw):
+    """The descriptor of measure `kind` applied to the probe x (and a concrete
+    reference x_ref); TraceAbort where the call is not the measure of the bare
+    probe (a traced operator applied first, the probe as the reference, shapes
+    that the measure itself would refuse)."""
+    if not isinstance(x, Sym) or x.desc is not None or isinstance(x_ref, Sym):
+        raise TraceAbort("measure of something other than the bare probe")
+    if x_ref is not None:
+        ref_shape = tuple(getattr(x_ref, "shape", np.shape(x_ref)))
+        if ref_shape != x.shape:
+            raise TraceAbort("reference shape differs from the probe's")
+    return MeasureDesc(kind, x.shape, ref=x_ref, **kw)
+
+
+def is_probe(*args):
+    return any(isinstance(a, Sym) for a in args)

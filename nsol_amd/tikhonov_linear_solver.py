@@ -186,8 +186,9 @@ class TikhonovLinearSolver(LinearSolver):
             raise ValueError(
                 "lsq_linear solver cannot be used with non-linear data loss")
 
-        if self._observer is not None:
-            self._observer.add_x(self.get_x())
+        # (start and end points; a device-mode observer, observer.py, looks at
+        # them without a copy to the host)
+        self._observe_start(1)
 
         x0 = self._x0_device()
         lsmr_path = self._minimizer == "lsmr" and self._data_loss == "linear"
@@ -208,7 +209,9 @@ class TikhonovLinearSolver(LinearSolver):
         else:
             self._x = self._run_minimize(x0)
 
-        if self._observer is not None:
+        if self._observing_on_device():
+            self._observe_at(1, self._x)
+        elif self._observer is not None:
             self._observer.add_x(self.get_x())
 
     # ------------------------------------------------------------------
