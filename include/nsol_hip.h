@@ -577,6 +577,60 @@ int nsol_pd_fusedk_tail2_pitched(int elem_size, int64_t nz, int64_t ny, int64_t 
                                  int64_t pitch);
 
 /* ---------------------------------------------------------------------- *
+ * Parameter sweep: `members` independent primal-dual runs on ONE observation
+ * (solver_parameter_study.py: one solver per element of itertools.product of the
+ * parameter lists), advanced together -- one launch per iteration for all of
+ * them (nsol_pds.hip).  The arithmetic is nsol_pd_fused_iter_*'s: member m is
+ * bit-identical to a single run with that member's scalars.
+ * Layout, member-major: xbar0/xbar1/x hold members * n elements (x[m n + i]),
+ * p0/p1 members * ndim * n (p[m ndim n + c n + i]), so member m of every array
+ * is a contiguous slice that the single-volume functions take as it is; bt (the
+ * scaled observation, n elements) is shared by all members.
+ * nsol_pd_sweep_run_*: lmbda_host[members]; sigma/tau/theta_host[members][iterations]
+ * (row m: the schedule of member m).  The run entry rounds them into a table
+ * [iteration][member] of nsol_pd_sweep_entry_bytes(elem_size)-byte entries, written
+ * to tab_host (caller-owned HOST memory, page-locked if the call is to return
+ * before the copy has run; it must stay untouched until the copy has) and copied
+ * once to tab (device, 16-byte aligned), both tab_bytes >= entry bytes * members *
+ * iterations; then `iterations` launches are enqueued on `stream`, each reading its
+ * row of the table: no further copy, no synchronisation.  gamma_huber and flags are
+ * common to the sweep; p_is_zero as for nsol_pd_run_*.  Slot 0 is read first;
+ * *final_slot_host = iterations & 1.
+ * nsol_pd_sweep_iter_*: one launch, iteration `iteration` of a table filled earlier.
+ * Both return -2, having launched nothing, for what the stacked kernel does not
+ * take: members < 1 or > 65535, members * n over 2^31 voxels, a geometry
+ * nsol_pd_fused_iter_* would refuse.
+ * nsol_pd_sweep_launches: launches of the stacked kernel this process has made. */
+int nsol_pd_sweep_entry_bytes(int elem_size);
+int nsol_pd_sweep_launches(void);
+int nsol_pd_sweep_iter_f32(const float *xbar_in, float *xbar_out, float *x,
+                           const float *bt, const float *p_in, float *p_out,
+                           int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                           double wx, double wy, double wz, const void *tab,
+                           int iteration, void *stream);
+int nsol_pd_sweep_iter_f64(const double *xbar_in, double *xbar_out, double *x,
+                           const double *bt, const double *p_in, double *p_out,
+                           int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                           double wx, double wy, double wz, const void *tab,
+                           int iteration, void *stream);
+int nsol_pd_sweep_run_f32(float *xbar0, float *xbar1, float *x, const float *bt,
+                          float *p0, float *p1, int members, int ndim, int64_t nz,
+                          int64_t ny, int64_t nx, double wx, double wy, double wz,
+                          const double *lmbda_host, const double *sigma_host,
+                          const double *tau_host, const double *theta_host,
+                          int iterations, int p_is_zero, double gamma_huber, int flags,
+                          void *tab_host, void *tab, int64_t tab_bytes,
+                          int *final_slot_host, void *stream);
+int nsol_pd_sweep_run_f64(double *xbar0, double *xbar1, double *x, const double *bt,
+                          double *p0, double *p1, int members, int ndim, int64_t nz,
+                          int64_t ny, int64_t nx, double wx, double wy, double wz,
+                          const double *lmbda_host, const double *sigma_host,
+                          const double *tau_host, const double *theta_host,
+                          int iterations, int p_is_zero, double gamma_huber, int flags,
+                          void *tab_host, void *tab, int64_t tab_bytes,
+                          int *final_slot_host, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

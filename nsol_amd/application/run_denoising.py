@@ -5,8 +5,13 @@ without plotting).
     python -m nsol_amd.application.run_denoising --observation in.nii.gz \\
         --result out.nii.gz --reconstruction-type TVL2 --alpha 0.03 \\
         --iterations 50 [--reference gt.nii.gz] [--L2 8] [--dtype float32]
+
+Several values of --alpha are a parameter sweep (nsol_amd/parameter_sweep.py): the
+members run stacked, one launch per iteration for all of them; --result-dir DIR
+keeps every member (<stem>_alpha<value><ext>) next to a sweep.npz.
 """
 import argparse
+import os
 import sys
 
 import numpy as np
@@ -20,9 +25,9 @@ from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
 
 
-def build_solver(observed_nda, reconstruction_type, alpha, iterations, L2=8,
-                 verbose=0, dtype=None, alg_type="ALG2"):
-    """Wiring of run_denoising.py:95-154."""
+def wiring(observed_nda, reconstruction_type):
+    """Wiring of run_denoising.py:95-154: the callables, start and scale that
+    PrimalDualSolver / PrimalDualSweep are built from."""
     dimension = observed_nda.ndim
     b = observed_nda.flatten()
     x0 = observed_nda.flatten()
@@ -46,10 +51,71 @@ def build_solver(observed_nda, reconstruction_type, alpha, iterations, L2=8,
                          reconstruction_type)
     prox_g_conj = prox.prox_huber_conj \
         if reconstruction_type.startswith("Huber") else prox.prox_tv_conj
+    return dict(prox_f=prox_f, prox_g_conj=prox_g_conj, B=D_1D, B_conj=D_adj_1D,
+                x0=x0, x_scale=x_scale)
+
+
+def build_solver(observed_nda, reconstruction_type, alpha, iterations, L2=8,
+                 verbose=0, dtype=None, alg_type="ALG2"):
     return pd.PrimalDualSolver(
-        prox_f=prox_f, prox_g_conj=prox_g_conj, B=D_1D, B_conj=D_adj_1D,
-        L2=L2, x0=x0, alpha=alpha, iterations=iterations, x_scale=x_scale,
-        verbose=verbose, alg_type=alg_type, dtype=dtype)
+        L2=L2, alpha=alpha, iterations=iterations, verbose=verbose,
+        alg_type=alg_type, dtype=dtype, **wiring(observed_nda, reconstruction_type))
+
+
+def member_result_path(result_dir, like, alpha):
+    """<result_dir>/<stem>_alpha<value><ext> with stem and extension (".nii.gz"
+    counts as one) of the file name `like`."""
+    base = os.path.basename(like)
+    stem, _, ext = base.partition(".")
+    return os.path.join(result_dir, "%s_alpha%g%s" % (stem, alpha,
+                                                     "." + ext if ext else ""))
+
+
+def run_sweep(args, observed_nda, x_ref, reader):
+    """Several alphas: the members stacked through PrimalDualSweep."""
+    from ..parameter_sweep import PrimalDualSweep
+    sweep = PrimalDualSweep(
+        L2=args.L2, parameters={"alpha": list(args.alpha)},
+        iterations=args.iterations, alg_type=args.alg_type,
+        dtype=np.dtype(args.dtype).type,
+        **wiring(observed_nda, args.reconstruction_type))
+    if x_ref is not None:
+        sweep.set_measures({
+            m: (lambda x, m=m:
+                SimilarityMeasures.similarity_measures[m](x, x_ref))
+            for m in args.measures},
+            every=args.observe_every or max(args.iterations, 1))
+    sweep.run()
+    measures = sweep.get_measures()
+    like = args.result if args.result is not None else args.observation
+    for k, alpha in enumerate(args.alpha):
+        print("%s alpha=%g: %d iterations in %s (%s)" % (
+            args.reconstruction_type, alpha, args.iterations,
+            sweep.get_computational_time(), sweep.get_execution()))
+        for m, vals in measures.items():
+            print("  %s: %.6g -> %.6g" % (m, vals[k, 0], vals[k, -1]))
+        if args.result is not None or args.result_dir is not None:
+            recon = np.array(sweep.get_x(k).reshape(*observed_nda.shape))
+        if args.result is not None:
+            dw.DataWriter(recon, args.result,
+                          reader.get_image_sitk()).write_data()
+        if args.result_dir is not None:
+            dw.DataWriter(recon, member_result_path(args.result_dir, like, alpha),
+                          reader.get_image_sitk()).write_data()
+    if measures:
+        lower = ("RMSE", "MSE", "MAE", "SSD", "SAD")
+        print("best alpha: " + ", ".join(
+            "%s %g" % (m, sweep.best(m, "min" if m in lower else "max")[1]["alpha"])
+            for m in measures))
+    if args.result_dir is not None:
+        os.makedirs(args.result_dir, exist_ok=True)
+        np.savez(os.path.join(args.result_dir, "sweep.npz"),
+                 parameter_names=np.array(["alpha"]),
+                 parameters=np.array(args.alpha, dtype=np.float64).reshape(-1, 1),
+                 observed_iterations=np.array(sweep.get_observed_iterations(),
+                                              dtype=np.int64),
+                 **{"measure_" + m: v for m, v in measures.items()})
+    return 0
 
 
 def main(argv=None):
@@ -76,6 +142,10 @@ def main(argv=None):
                     help="evaluate the measures on the device every K "
                          "iterations (and at the last) instead of on a host "
                          "copy of every iterate")
+    ap.add_argument("--result-dir", default=None, metavar="DIR",
+                    help="with several --alpha: every member's result as "
+                         "<stem>_alpha<value><ext> and the sweep's parameters "
+                         "and measures as sweep.npz in DIR")
     args = ap.parse_args(argv)
 
     if len(args.alpha) == 1 and args.result is None:
@@ -89,6 +159,9 @@ def main(argv=None):
         ref_reader = dr.DataReader(args.reference)
         ref_reader.read_data()
         x_ref = ref_reader.get_data().flatten()
+
+    if len(args.alpha) > 1 and not args.verbose:
+        return run_sweep(args, observed_nda, x_ref, reader)
 
     for alpha in args.alpha:
         solver = build_solver(observed_nda, args.reconstruction_type, alpha,

@@ -1,0 +1,249 @@
+// Member-stacked Chambolle-Pock iteration for gfx950 (MI355X): P independent
+// primal-dual runs on ONE observation (a parameter sweep: the members differ in
+// lambda = 1/alpha and in their step schedules only) advance by one iteration in
+// one launch.
+//
+// reference: solver_parameter_study.py (_run: one solver per element of
+// itertools.product of the parameter lists) driving primal_dual_solver.py:232-261.
+//
+// The arithmetic is k_pd_fused's (nsol_pd.hip): both kernels run pd_fused_tile of
+// nsol_pd_fused_body.hpp, so member m of a stacked run is bit-identical to a
+// single run with that member's scalars.  The member index is blockIdx.y; it
+// offsets the base pointers (x[m n + i], p[m dim n + c n + i]; bt is shared) and
+// selects the row PdScalars[iteration][member] of a device table that
+// nsol_pd_sweep_run_* fills once per run.
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+
+#include "nsol_common.hpp"
+#include "nsol_pd_common.hpp"
+#include "nsol_pd_fused_body.hpp"
+
+using namespace nsol;
+
+namespace {
+
+std::atomic<int> g_sweep_launches{0};
+
+template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+__global__ __launch_bounds__(kBlock) void k_pd_sweep(
+    const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
+    const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
+    Geom<T> G, const PdScalars<T> *__restrict__ tab, int ntx, int nty, int zchunk,
+    int slab) {
+  int tx, ty, zc;
+  if (!pd_fused_block_tile(blockIdx.x, ntx, nty, slab, tx, ty, zc)) return;
+  // gridDim.y = members: the row of this iteration starts at `tab`
+  const int64_t m = blockIdx.y;
+  const PdScalars<T> S = tab[m];           // uniform per workgroup, read-only
+  const int64_t xo = m * G.n;
+  const int64_t po = m * G.n * NDIM;
+  pd_fused_tile<T, VEC, LX, RY, NDIM, RAG>(xbar_in + xo, xbar_out + xo, x + xo, bt,
+                                           p_in + po, p_out + po, G, S, tx, ty, zc,
+                                           zchunk);
+}
+
+template <typename T>
+struct SweepArgs {
+  const T *xbar_in;
+  T *xbar_out, *x;
+  const T *bt, *p_in;
+  T *p_out;
+  Geom<T> G;
+  const PdScalars<T> *row;
+  int members;
+  hipStream_t st;
+};
+
+// Launch geometry: the rules of launch_fused_t / launch_fused_ry (nsol_pd.hip)
+// with the members counted as tiles -- 64 members of a 256 x 256 image fill the
+// chip where one does not, so the stack takes two rows per lane and whole z runs
+// sooner than a single volume would.  Placement never changes a result.
+template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+int launch_sweep_t(const SweepArgs<T> &a) {
+  constexpr int LY = kWave / LX;
+  constexpr int TY = (kBlock / kWave) * LY * RY;
+  constexpr int TX = LX * VEC;
+  const Geom<T> &G = a.G;
+  const int64_t ntx = (G.nx + TX - 1) / TX;
+  const int64_t nty = (G.ny + TY - 1) / TY;
+  const int64_t tiles = ntx * nty * a.members;
+  const int64_t want = (4096 + tiles - 1) / tiles;
+  int64_t zchunk = (G.nz + want - 1) / want;
+  if (zchunk < 2) zchunk = 2;
+  if (zchunk > G.nz) zchunk = G.nz;
+  const int64_t nzc = (G.nz + zchunk - 1) / zchunk;
+  int64_t slab = 0;
+  int64_t blocks = ntx * nty * nzc;
+  if (nty >= 16) {
+    slab = (nty + 7) / 8;
+    blocks = 8 * slab * ntx * nzc;
+  }
+  if (blocks > 0x7fffffff) return -2;
+  hipLaunchKernelGGL((k_pd_sweep<T, VEC, LX, RY, NDIM, RAG>),
+                     dim3((unsigned)blocks, (unsigned)a.members), dim3(kBlock), 0, a.st,
+                     a.xbar_in, a.xbar_out, a.x, a.bt, a.p_in, a.p_out, G, a.row,
+                     (int)ntx, (int)nty, (int)zchunk, (int)slab);
+  const int rc = launch_status();
+  if (rc == 0) g_sweep_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+template <typename T, int VEC, int LX, bool RAG>
+int launch_sweep(const SweepArgs<T> &a) {
+  const Geom<T> &G = a.G;
+  constexpr int TY2 = (kBlock / kWave) * (kWave / LX) * 2;
+  const int64_t tiles =
+      ((G.nx + LX * VEC - 1) / (LX * VEC)) * ((G.ny + TY2 - 1) / TY2) * a.members;
+  const bool two_rows = tiles * ((G.nz + 1) / 2) >= 512;
+  switch (G.ndim) {
+    case 1: return launch_sweep_t<T, VEC, LX, 1, 1, RAG>(a);
+    case 2:
+      return two_rows ? launch_sweep_t<T, VEC, LX, 2, 2, RAG>(a)
+                      : launch_sweep_t<T, VEC, LX, 1, 2, RAG>(a);
+    default:
+      return two_rows ? launch_sweep_t<T, VEC, LX, 2, 3, RAG>(a)
+                      : launch_sweep_t<T, VEC, LX, 1, 3, RAG>(a);
+  }
+}
+
+template <typename T>
+inline bool aligned16(const T *a) {
+  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
+}
+
+// What the stacked kernel takes: a geometry fused_iter_impl (nsol_pd.hip) takes,
+// at least one member, all members together within 2^31 voxels, members within
+// the grid's y extent.
+inline bool sweep_takes(int members, int ndim, int64_t nz, int64_t ny, int64_t nx) {
+  if (members < 1 || members > 65535) return false;
+  if (!geom_ok(ndim, nz, ny, nx)) return false;
+  const int64_t n = nz * ny * nx;
+  return n <= (int64_t(1) << 31) / members;
+}
+
+template <typename T>
+int sweep_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p_in,
+                    T *p_out, int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                    double wx, double wy, double wz, const void *tab, int iteration,
+                    void *stream) {
+  if (!sweep_takes(members, ndim, nz, ny, nx)) return -2;
+  if (!xbar_in || !xbar_out || !x || !bt || !p_in || !p_out || !tab || iteration < 0 ||
+      xbar_in == xbar_out || p_in == p_out)
+    return NSOL_EINVAL;
+  SweepArgs<T> a;
+  a.xbar_in = xbar_in; a.xbar_out = xbar_out; a.x = x; a.bt = bt;
+  a.p_in = p_in; a.p_out = p_out;
+  a.G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
+  a.members = members;
+  a.st = as_stream(stream);
+  constexpr int VW = 16 / sizeof(T);  // elements per 16-byte access
+  // (every member's slice starts a whole number of vectors behind the base when
+  // the volume is whole vectors)
+  const bool vec_ok = (nx % VW == 0) && aligned16(xbar_in) && aligned16(xbar_out) &&
+                      aligned16(x) && aligned16(bt) && aligned16(p_out) &&
+                      aligned16(p_in) && ((nz * ny * nx) % VW == 0);
+  if (vec_ok) {
+    if (nx / VW >= kWave) return launch_sweep<T, VW, 64, false>(a);
+    return launch_sweep<T, VW, 16, false>(a);
+  }
+  if (nx >= 2 * VW) {   // ragged rows: element-aligned 16-byte accesses
+    if ((nx + VW - 1) / VW >= kWave) return launch_sweep<T, VW, 64, true>(a);
+    return launch_sweep<T, VW, 16, true>(a);
+  }
+  if (nx >= kWave) return launch_sweep<T, 1, 64, false>(a);
+  return launch_sweep<T, 1, 16, false>(a);
+}
+
+template <typename T>
+int sweep_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int members,
+                   int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+                   double wz, const double *lmbda, const double *sig, const double *tau,
+                   const double *theta, int iterations, int p_is_zero, double gamma_huber,
+                   int flags, void *tab_host, void *tab, int64_t tab_bytes,
+                   int *final_slot, void *stream) {
+  if (!sweep_takes(members, ndim, nz, ny, nx)) return -2;
+  if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
+      tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)
+    return NSOL_EINVAL;
+  const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
+  // the table, [iteration][member], rounded exactly as make_scalars (nsol_pd.hip)
+  // rounds the scalars of a single run
+  PdScalars<T> *h = static_cast<PdScalars<T> *>(tab_host);
+  for (int n = 0; n < iterations; ++n)
+    for (int m = 0; m < members; ++m) {
+      const int64_t k = (int64_t)m * iterations + n;
+      const double tl = tau[k] * lmbda[m];
+      PdScalars<T> &S = h[(int64_t)n * members + m];
+      memset(&S, 0, sizeof(S));
+      S.sigma = (T)sig[k];
+      S.hden = huber_den<T>(huber ? 1.0 + sig[k] * gamma_huber : 1.0);
+      S.tau = (T)tau[k];
+      S.tl = (T)tl;
+      S.one_plus_tl = prox_den<T>(tl);
+      S.theta = (T)theta[k];
+      S.huber = huber ? 1 : 0;
+      S.l1 = (flags & NSOL_PD_DATA_L1) ? 1 : 0;
+      S.has_p = (n == 0 && p_is_zero) ? 0 : 1;
+    }
+  if (iterations > 0) {
+    hipError_t e = hipMemcpyAsync(tab, tab_host,
+                                  sizeof(PdScalars<T>) * (size_t)members * iterations,
+                                  hipMemcpyHostToDevice, as_stream(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  T *xb[2] = {xbar0, xbar1};
+  T *pp[2] = {p0, p1};
+  int slot = 0;
+  for (int n = 0; n < iterations; ++n, slot ^= 1) {
+    const int rc = sweep_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, pp[slot], pp[slot ^ 1],
+                                      members, ndim, nz, ny, nx, wx, wy, wz, tab, n,
+                                      stream);
+    if (rc) return rc;     // (-2 can only come from the first launch: nothing ran)
+  }
+  if (final_slot) *final_slot = slot;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsol_pd_sweep_entry_bytes(int elem_size) {
+  if (elem_size == 4) return (int)sizeof(PdScalars<float>);
+  if (elem_size == 8) return (int)sizeof(PdScalars<double>);
+  return NSOL_EINVAL;
+}
+
+int nsol_pd_sweep_launches(void) {
+  return g_sweep_launches.load(std::memory_order_relaxed);
+}
+
+#define NSOL_PDS_DEF(T, SUF)                                                          \
+  int nsol_pd_sweep_iter_##SUF(const T *xi, T *xo, T *x, const T *bt, const T *pi,    \
+                               T *po, int members, int ndim, int64_t nz, int64_t ny,  \
+                               int64_t nx, double wx, double wy, double wz,           \
+                               const void *tab, int iteration, void *s) {             \
+    return sweep_iter_impl<T>(xi, xo, x, bt, pi, po, members, ndim, nz, ny, nx, wx,   \
+                              wy, wz, tab, iteration, s);                             \
+  }                                                                                   \
+  int nsol_pd_sweep_run_##SUF(T *xb0, T *xb1, T *x, const T *bt, T *p0, T *p1,        \
+                              int members, int ndim, int64_t nz, int64_t ny,          \
+                              int64_t nx, double wx, double wy, double wz,            \
+                              const double *lm, const double *sg, const double *ta,   \
+                              const double *th, int iters, int p_is_zero, double gh,  \
+                              int flags, void *tab_host, void *tab, int64_t tab_bytes, \
+                              int *final_slot, void *s) {                             \
+    return sweep_run_impl<T>(xb0, xb1, x, bt, p0, p1, members, ndim, nz, ny, nx, wx,  \
+                             wy, wz, lm, sg, ta, th, iters, p_is_zero, gh, flags,     \
+                             tab_host, tab, tab_bytes, final_slot, s);                \
+  }
+
+NSOL_PDS_DEF(float, f32)
+NSOL_PDS_DEF(double, f64)
+#undef NSOL_PDS_DEF
+
+}  // extern "C"

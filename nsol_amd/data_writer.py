@@ -12,7 +12,12 @@ class DataWriter(object):
         self._nda = nda
         self._path_to_file = path_to_file
         self._image_info = image_sitk
-        self._file_type = os.path.basename(path_to_file).split(".")[1]
+        # the last known type among the dotted parts ("x.nii.gz" -> nii, and a
+        # stem with dots of its own, "x_alpha0.03.npy" -> npy); else the first,
+        # which write_data() then refuses by name
+        parts = os.path.basename(path_to_file).split(".")
+        known = [t for t in parts[1:] if t in ("txt", "png", "mat", "nii", "npy")]
+        self._file_type = known[-1] if known else parts[1]
 
     def write_data(self):
         d = os.path.dirname(self._path_to_file)

@@ -188,12 +188,15 @@ class Observer(object):
         return dict(self._session.classes)
 
     # ---- used by the solvers (device mode) ----------------------------
-    def _begin(self, n, iterations):
+    def _begin(self, n, iterations, refs=None):
         """Start of a device-mode run of a solver with n unknowns and
         `iterations` iterations: classify, upload, allocate the board.
-        Returns the observation points."""
+        Returns the observation points.  refs: a dict that several observers of
+        runs on the same data hand in (parameter_sweep.py), so that a reference
+        they share is uploaded and summed once, not once per observer."""
         self._session = _DeviceRun(self._functions, n,
-                                   observation_points(iterations, self._every))
+                                   observation_points(iterations, self._every),
+                                   refs)
         for key in self._functions:
             self._values[key] = None
         return self._session.points
@@ -212,7 +215,7 @@ class _DeviceRun(object):
     """One device-mode run: the classified measures, the references on the
     device, the board and the values of the histogram and host classes."""
 
-    def __init__(self, functions, n, points):
+    def __init__(self, functions, n, points, refs=None):
         import torch
         from .device import device
         self.n = int(n)
@@ -225,7 +228,7 @@ class _DeviceRun(object):
             d = probe_measure(fn, self.n)
             self.descs[key] = d
             self.classes[key] = classify(d)
-        self._refs = {}             # id(ref) -> _Reference
+        self._refs = {} if refs is None else refs     # id(ref) -> _Reference
         self.passes = self._plan()
         ssim = [k for k, c in self.classes.items() if c == "ssim"]
         self.ssim_slot = {k: 9 * len(self.passes) + j for j, k in enumerate(ssim)}

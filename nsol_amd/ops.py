@@ -1331,6 +1331,103 @@ def pd_run(xbar0, xbar1, x, bt, p0, p1, shape, w, lmbda, sigma, tau, theta,
     return int(slot.value) & 1
 
 
+# ------------------------------------------------------- parameter sweep ----
+# Members of a sweep (nsol_amd/parameter_sweep.py) are stacked in one launch per
+# iteration while one member has at most PD_SWEEP_MAX_VOXELS voxels, in groups whose
+# state (x, two xbar, two p: 3 + 2 dim arrays of the member's size) stays under
+# PD_SWEEP_GROUP_BYTES.  Both decide speed only: results are the same bits on either
+# side of them.  From tools/bench_sweep.py --explore (float32 TV-l2, 100 iterations,
+# 4 / 16 / 64 alphas; DESIGN.md section 4a has the table):
+#  * a group that stays within the 256 MB last-level cache beats one launch for all
+#    members once their state outgrows it -- 1024^2 x 16: 10.7 ms in groups of 9
+#    against 13.1 ms in one group; 128^3 x 16: 28.1 ms in groups of 3 against 34.9 ms;
+#    128^3 x 64: 114 against 127 ms -- and costs 2 % where it splits a stack that was
+#    cache-resident anyway (64^3 x 64: 17.7 against 17.4 ms);
+#  * at 256^3, the largest size measured, the stacked form (one member per launch by
+#    then) still beats one solver after the other, 0.108 against 0.143 s for 4 alphas
+#    and 1.00 against 1.59 s for 64, because it uploads and scales the observation
+#    once; nothing larger was measured, so the limit is that size.
+PD_SWEEP_MAX_VOXELS = 1 << 24
+PD_SWEEP_GROUP_BYTES = 256 << 20
+_sweep_staging = []        # (event, pinned table) of runs whose upload may be pending
+
+
+def pd_sweep_launches():
+    """Launches of the member-stacked kernel so far (for tests and tools)."""
+    return int(_lib.load().nsol_pd_sweep_launches())
+
+
+def sweep_group_size(members, n, dim, elem_size):
+    """Members per stacked group: as many as keep a group's state under
+    PD_SWEEP_GROUP_BYTES and within the kernel's 2^31 voxels, at least one."""
+    per_member = (3 + 2 * int(dim)) * int(n) * int(elem_size)
+    g = min(PD_SWEEP_GROUP_BYTES // per_member, (1 << 31) // int(n))
+    return int(max(1, min(int(members), g)))
+
+
+def sweep_groups(members, group):
+    """[(first, last + 1), ...]: every member once, in order, `group` at a time."""
+    members, group = int(members), int(group)
+    if members < 1 or group < 1:
+        raise ValueError("members and group size must be positive")
+    return [(a, min(a + group, members)) for a in range(0, members, group)]
+
+
+def pd_sweep_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, tau,
+                 theta, p_is_zero, gamma_huber, flags):
+    """Enqueue sigma.shape[1] iterations of `members` stacked primal-dual runs that
+    share the scaled observation bt: one launch per iteration for all of them.
+    x, xbar0/1 hold members * n elements, p0/p1 members * dim * n, member-major;
+    lmbda is (members,), sigma/tau/theta (members, iterations).  Returns the slot
+    (0/1) of xbar/p that holds the final state, or None when the library declined
+    (nothing was launched).  Does not synchronise."""
+    import ctypes
+    ndim, nz, ny, nx = dims3(shape)
+    members = int(members)
+    n = nz * ny * nx
+    _chk(bt)
+    _same(x, xbar0, xbar1)
+    _same(p0, p1)
+    if bt.dtype != x.dtype or p0.dtype != x.dtype or bt.numel() != n or \
+            x.numel() != members * n or p0.numel() != members * ndim * n:
+        raise ValueError("operand mismatch: %d members of %d voxels against x[%d], "
+                         "bt[%d], p[%d]" % (members, n, x.numel(), bt.numel(),
+                                            p0.numel()))
+    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if sigma.ndim != 2 or sigma.shape[0] != members or lmbda.size != members or \
+            tau.shape != sigma.shape or theta.shape != sigma.shape:
+        raise ValueError("schedules must be (members, iterations) arrays")
+    iters = int(sigma.shape[1])
+    if _pending_runs:
+        settle_persist_runs()     # as pd_run: an earlier persistent run may feed this
+    # the upload of a run's table is stream-ordered: its pinned source lives until
+    # the event behind the run has passed
+    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
+    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
+    nbytes = max(16, entry * members * iters)
+    tab_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    tab = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    slot = ctypes.c_int(0)
+    rc = _fn("pd_sweep_run", x)(
+        _p(xbar0), _p(xbar1), _p(x), _p(bt), _p(p0), _p(p1), members, ndim, nz, ny,
+        nx, w[0], w[1], w[2], lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
+        theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber),
+        int(flags), tab_host.data_ptr(), _p(tab), nbytes, ctypes.addressof(slot),
+        stream_ptr())
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_pd_sweep_run")
+    _wrote(xbar0, xbar1, x, p0, p1)
+    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
+    ev = torch.cuda.Event()
+    ev.record()
+    _sweep_staging.append((ev, tab_host))
+    return int(slot.value)
+
+
 # ----------------------------------------------------------------- ADMM ----
 def admm_vw_update(x, v, w_, c, rhs, shape, w, thr, rhs_scale, want_norm=False):
     """v, w_ and the next right-hand side rhs = rhs_scale * (v - w_ + c) from one

@@ -1,0 +1,273 @@
+"""Parameter sweeps of the primal-dual solver on one observation (the job of the
+reference's solver_parameter_study.py / primal_dual_solver_parameter_study.py,
+without their SimpleITK / pysitk / natsort file handling).
+
+    sweep = PrimalDualSweep(prox_f, prox_g_conj, B, B_conj, L2, x0,
+                            parameters={"alpha": [...], "alg_type": [...]},
+                            iterations=50, x_scale=xs)
+    sweep.set_measures({"PSNR": lambda x: ...}, every=10)
+    sweep.run()
+    m, best = sweep.best("PSNR")
+
+The members are the elements of itertools.product over the parameter lists in
+the order the dictionary gives them (solver_parameter_study.py, _run).  Two
+execution forms, the same results and the same interface:
+  stacked     a natively fused configuration (PrimalDualSolver.plan()): the
+              observation is uploaded and scaled once and all members advance
+              together, ONE launch per iteration (nsol_pd_sweep_run_*), in
+              groups that keep the state under ops.PD_SWEEP_GROUP_BYTES; the
+              measures are taken on the device from each member's slice of the
+              stacked iterate;
+  sequential  anything else (foreign callables, deconvolution, members larger
+              than ops.PD_SWEEP_MAX_VOXELS, a geometry the library declines):
+              one PrimalDualSolver after the other.
+"""
+import datetime
+import itertools
+import time
+
+import numpy as np
+
+from . import ops
+from .observer import Observer
+from .primal_dual_solver import PrimalDualSolver, step_schedule
+
+PARAMETER_KEYS = ("alpha", "alg_type", "L2")
+
+
+def member_parameters(parameters):
+    """The members of a sweep: one dict per element of itertools.product over the
+    value lists, in the dictionary's own key order."""
+    keys = list(parameters.keys())
+    for k in keys:
+        if k not in PARAMETER_KEYS:
+            raise ValueError("unknown sweep parameter '%s' (known: %s)" %
+                             (k, ", ".join(PARAMETER_KEYS)))
+    values = []
+    for k in keys:
+        v = parameters[k]
+        v = [v] if isinstance(v, (str, bytes)) or np.ndim(v) == 0 else list(v)
+        if len(v) == 0:
+            raise ValueError("sweep parameter '%s' has no values" % k)
+        values.append(v)
+    if not keys:
+        raise ValueError("a sweep needs at least one parameter")
+    return [dict(zip(keys, combo)) for combo in itertools.product(*values)]
+
+
+class PrimalDualSweep(object):
+
+    def __init__(self, prox_f, prox_g_conj, B, B_conj, L2, x0, parameters,
+                 iterations=50, x_scale=1., dtype=None, alpha=0.01,
+                 alg_type="ALG2"):
+        self._callables = dict(prox_f=prox_f, prox_g_conj=prox_g_conj, B=B,
+                               B_conj=B_conj)
+        self._x0 = x0
+        self._defaults = dict(alpha=alpha, alg_type=alg_type, L2=L2)
+        self._members = member_parameters(parameters)
+        self._iterations = int(iterations)
+        self._x_scale = float(x_scale)
+        self._dtype = dtype
+        self._functions = {}
+        self._every = None
+        self._execution = None
+        self._computational_time = datetime.timedelta(seconds=0)
+        self._x_all = None          # stacked: (P * n) device tensor, solver units
+        self._x_list = None         # sequential: per member, caller's units
+        self._observers = []
+        self._n = None
+
+    # ------------------------------------------------------------------
+    def set_measures(self, measures_dic, every=None):
+        """Measures of every member's iterate x (caller's units), taken at
+        iterations 0, every, 2 every, ... and the last; every=None: at the
+        final iterate only."""
+        if every is not None and int(every) < 1:
+            raise ValueError("every must be a positive integer")
+        self._functions = dict(measures_dic)
+        self._every = None if every is None else int(every)
+
+    def get_parameters(self):
+        return [dict(m) for m in self._members]
+
+    def get_execution(self):
+        """'stacked' or 'sequential' after run() (None before)."""
+        return self._execution
+
+    def get_computational_time(self):
+        return self._computational_time
+
+    def _solver(self, member=None):
+        kw = dict(self._defaults)
+        kw.update(member or {})
+        return PrimalDualSolver(
+            x0=self._x0, iterations=self._iterations, x_scale=self._x_scale,
+            dtype=self._dtype, alpha=kw["alpha"], alg_type=kw["alg_type"],
+            L2=kw["L2"], **self._callables)
+
+    def _observer(self):
+        if not self._functions:
+            return None
+        obs = Observer(keep_iterates=False,
+                       every=self._every or max(self._iterations, 1))
+        obs.set_measures(self._functions)
+        return obs
+
+    # ------------------------------------------------------------------
+    def run(self):
+        import torch
+        t0 = time.time()
+        template = self._solver(self._members[0])
+        if template._x0_ndim != 1:
+            raise ValueError("Initial value x0 must be a 1D array")
+        self._x_all = self._x_list = None
+        self._observers = []
+        plan = template.plan()
+        stacked = False
+        if plan is not None and self._iterations > 0 and \
+                int(np.prod(plan["shape"])) <= ops.PD_SWEEP_MAX_VOXELS:
+            stacked = self._run_stacked(template, plan)
+        if not stacked:
+            self._run_sequential()
+        torch.cuda.synchronize()
+        ops.settle_persist_runs(synchronize=False)
+        for obs in self._observers:
+            obs._finish()                 # every board, read after the one wait
+        self._execution = "stacked" if stacked else "sequential"
+        # the measure step: a measure that raised during the run fails here
+        for obs in self._observers:
+            obs.compute_measures()
+        self._computational_time = datetime.timedelta(seconds=time.time() - t0)
+
+    def _run_sequential(self):
+        """One solver after the other, as the command-line tools loop."""
+        self._x_list, self._observers = [], []
+        for member in self._members:
+            solver = self._solver(member)
+            obs = self._observer()
+            if obs is not None:
+                solver.set_observer(obs)
+                self._observers.append(obs)
+            solver.run()
+            self._n = solver._x.numel()
+            self._x_list.append(solver.get_x_device())
+
+    def _run_stacked(self, template, plan):
+        """All members in one launch per iteration; False when the library
+        declined (nothing has run then)."""
+        import torch
+        from .device import to_device
+        from .proximal_operators import scaled_data_on_device
+        members, iters = self._members, self._iterations
+        P = len(members)
+        x0 = template._x0_device()
+        n, dim = x0.numel(), plan["dim"]
+        lmbda = np.empty(P)
+        sig, ta, th = (np.empty((P, iters)) for _ in range(3))
+        for m, member in enumerate(members):
+            kw = dict(self._defaults)
+            kw.update(member)
+            lmbda[m] = 1. / float(kw["alpha"])
+            sig[m], ta[m], th[m] = step_schedule(kw["alg_type"], float(kw["L2"]),
+                                                 lmbda[m], iters)
+        bt = scaled_data_on_device(plan["data"], plan["data_scale"], x0)
+        G = ops.sweep_group_size(P, n, dim, x0.element_size())
+        x_all = torch.empty(P * n, dtype=x0.dtype, device=x0.device)
+        x_all.view(P, n).copy_(x0)
+        xbar = [torch.empty(G * n, dtype=x0.dtype, device=x0.device)
+                for _ in range(2)]
+        p = [torch.empty(G * dim * n, dtype=x0.dtype, device=x0.device)
+             for _ in range(2)]
+        # the observation of the start vector, as Solver._observe_at(0) makes it
+        observers, bounds = [], [0, iters]
+        if self._functions:
+            refs = {}
+            for _ in members:
+                obs = self._observer()
+                bounds = obs._begin(n, iters, refs)
+                observers.append(obs)
+            if self._every is not None:
+                if template._x0_host is not None:
+                    start, scale = to_device(template._x0_host.reshape(-1),
+                                             template._x0_host.dtype.type), 1.0
+                else:
+                    start, scale = x0, self._x_scale
+                for obs in observers:
+                    obs._observe(0, start, scale)
+        first_call = True
+        for a, b in ops.sweep_groups(P, G):
+            g = b - a
+            x = x_all[a * n:b * n]
+            xb = [t[:g * n] for t in xbar]
+            pp = [t[:g * dim * n] for t in p]
+            xb[0].view(g, n).copy_(x0)
+            k = 0
+            for i0, i1 in zip(bounds[:-1], bounds[1:]):
+                slot = ops.pd_sweep_run(
+                    xb[k], xb[1 - k], x, bt, pp[k], pp[1 - k], g, plan["shape"],
+                    plan["w"], lmbda[a:b], sig[a:b, i0:i1], ta[a:b, i0:i1],
+                    th[a:b, i0:i1], i0 == 0, plan["gamma"], plan["flags"])
+                if slot is None:
+                    if first_call:
+                        return False
+                    raise RuntimeError("nsol_pd_sweep_run declined in mid-sweep")
+                first_call = False
+                k = k if slot == 0 else 1 - k
+                for m in range(a, b):
+                    if observers:
+                        observers[m]._observe(i1, x_all[m * n:(m + 1) * n],
+                                              self._x_scale)
+        self._x_all, self._n, self._observers = x_all, n, observers
+        self._group = G
+        return True
+
+    _group = None
+
+    def get_group_size(self):
+        """Members per stacked launch of the last run (None: sequential)."""
+        return self._group if self._execution == "stacked" else None
+
+    # ------------------------------------------------------------------
+    def get_x_all_device(self):
+        """(P, n) device tensor of all members' results in the caller's units."""
+        import torch
+        if self._x_all is not None:
+            return ops.scale(self._x_all, self._x_scale).view(len(self._members), -1)
+        if self._x_list is None:
+            raise RuntimeError("run() first")
+        return torch.stack(self._x_list)
+
+    def get_x_device(self, m):
+        if self._x_all is not None:
+            n = self._n
+            return ops.scale(self._x_all[m * n:(m + 1) * n], self._x_scale)
+        if self._x_list is None:
+            raise RuntimeError("run() first")
+        return self._x_list[m].clone()
+
+    def get_x(self, m):
+        from .device import to_numpy
+        return to_numpy(self.get_x_device(m))
+
+    def get_observed_iterations(self):
+        if not self._observers:
+            return []
+        pts = self._observers[0].get_observed_iterations()
+        return pts if self._every is not None else pts[-1:]
+
+    def get_measures(self):
+        """{name: float64 array (members, observation points)}."""
+        out = {}
+        for name in self._functions:
+            rows = np.array([np.asarray(obs.get_measures()[name], np.float64)
+                             for obs in self._observers])
+            out[name] = rows if self._every is not None else rows[:, -1:]
+        return out
+
+    def best(self, name, mode="max"):
+        """(member index, its parameters) of the best final value of a measure."""
+        if mode not in ("max", "min"):
+            raise ValueError("mode must be 'max' or 'min'")
+        last = self.get_measures()[name][:, -1]
+        m = int(np.nanargmax(last) if mode == "max" else np.nanargmin(last))
+        return m, dict(self._members[m])
