@@ -21,6 +21,10 @@ template <typename T>
 struct Taps {
   T w[kMaxTaps];
 };
+// Passed by value: k_blur3_dma takes three of them next to 128 bytes of other
+// arguments, and HIP limits a kernel's arguments to 4 KB.
+static_assert(3 * sizeof(Taps<double>) + 128 <= 4096,
+              "three tap sets by value no longer fit the kernel-argument limit");
 
 template <typename T, int V>
 struct VecOf {

@@ -268,7 +268,10 @@ int try_launch_wrap(const T *x, T *out, int axis, int64_t nz, int64_t ny,
     return -2;
   // grid limits: x < 2^31 blocks, y and z <= 65535
   if (nx / VEC > (int64_t)65535 * 64 || nz * ny > (int64_t)0x7fffffff) return -2;
-  if (axis != 2 && (axis == 0 ? nz : ny) > (int64_t)65535 * 4) return -2;
+  // (outputs per lane along the axis as launch_wrap_nt picks them: corr_ra = 2 has
+  // len / 2 blocks along z)
+  const int ra = g_corr_ra == 8 ? 8 : (g_corr_ra == 2 ? 2 : 4);
+  if (axis != 2 && (axis == 0 ? nz : ny) > (int64_t)65535 * ra) return -2;
 #define NSOL_NT_CASE(N) \
   case N: return launch_wrap_nt<T, VEC, N>(x, out, axis, nz, ny, nx, taps, st);
   switch (ntaps) {
