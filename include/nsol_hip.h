@@ -62,6 +62,14 @@ extern "C" {
 #define NSOL_PD_REG_HUBER 1 /* proximal_operators.py:156-159 prox_huber_conj */
 #define NSOL_PD_DATA_L2 0   /* proximal_operators.py:117-120 prox_ell2_denoising */
 #define NSOL_PD_DATA_L1 2   /* proximal_operators.py:95-98  prox_ell1_denoising */
+/* or-ed with NSOL_PD_REG_TV / _HUBER: the dual projection is ISOTROPIC, p = q /
+ * max(1, |q|_2) with |q|_2 the Euclidean norm of the voxel's stacked gradient vector
+ * -- the vector admm_linear_solver.py:239-253 shrinks and prior_measures.py:27-52
+ * measures -- instead of the reference's per-component clamp.  Taken by
+ * nsol_pd_fused_iter_*, nsol_pd_run_* and nsol_pd_run_pitched_* (one launch of
+ * k_pd_fused_iso, nsol_pdi.hip, per iteration); every other fused form returns -2,
+ * having launched nothing. */
+#define NSOL_PD_REG_ISOTROPIC 4
 /* nsol_pd_run_* only: the caller can take the final primal iterate from x_alt (see
  * there) -- no copy back into x after an odd number of multi-iteration launches */
 #define NSOL_PD_RUN_X_MAY_SWAP 0x100
@@ -323,6 +331,16 @@ int nsol_prox_dual_clamp_f32(float *out, const float *x, double den, int64_t n,
                              void *stream);
 int nsol_prox_dual_clamp_f64(double *out, const double *x, double den,
                              int64_t n, void *stream);
+/* The isotropic counterpart: x holds `dim` blocks of n_per_block elements (the
+ * stacking of linear_operators.py:121-137); with q_a = x_a / den,
+ * out_a = q_a / max(1, sqrt(((q_0 q_0) + q_1 q_1) + q_2 q_2)) voxel by voxel -- the
+ * projection onto the unit ball of the per-voxel vector norm that
+ * admm_linear_solver.py:239-253 shrinks by and prior_measures.py:27-52 sums.
+ * den = 1: TV, den = 1 + sigma*gamma: Huber.  dim = 1..3; out may alias x. */
+int nsol_prox_dual_project_f32(float *out, const float *x, double den,
+                               int64_t n_per_block, int dim, void *stream);
+int nsol_prox_dual_project_f64(double *out, const double *x, double den,
+                               int64_t n_per_block, int dim, void *stream);
 /* out = (x + tau*bt) / (1 + tau), bt = b / x_scale precomputed;
  * proximal_operators.py:117-120 */
 int nsol_prox_ell2_f32(float *out, const float *x, const float *bt, double tau,
@@ -360,6 +378,19 @@ int nsol_pd_dual_step_f64(const double *xbar, const double *p_in,
                           double *p_out, int ndim, int64_t nz, int64_t ny,
                           int64_t nx, double wx, double wy, double wz,
                           double sigma, double hden, void *stream);
+/* The dual step with the isotropic projection (NSOL_PD_REG_ISOTROPIC): q = (p_in +
+ * sigma * grad(xbar)) / hden, p_out = q / max(1, |q|_2) per voxel -- the vector norm of
+ * admm_linear_solver.py:239-253 and prior_measures.py:27-52 in the place of
+ * proximal_operators.py:138-140's clamp.  Same aliasing rules as nsol_pd_dual_step_*;
+ * followed by nsol_pd_primal_step_* it is the two-pass form of an isotropic iteration. */
+int nsol_pd_dual_step_iso_f32(const float *xbar, const float *p_in, float *p_out,
+                              int ndim, int64_t nz, int64_t ny, int64_t nx,
+                              double wx, double wy, double wz, double sigma,
+                              double hden, void *stream);
+int nsol_pd_dual_step_iso_f64(const double *xbar, const double *p_in,
+                              double *p_out, int ndim, int64_t nz, int64_t ny,
+                              int64_t nx, double wx, double wy, double wz,
+                              double sigma, double hden, void *stream);
 /* primal step: u = x - tau*grad_adj(p); x_new = prox_f(u, tl); xbar = x_new +
  * theta*(x_new - x); x is updated in place (primal_dual_solver.py:246-256).
  * flags: NSOL_PD_DATA_L2 | NSOL_PD_DATA_L1; tl = tau*lambda. */
@@ -377,7 +408,8 @@ int nsol_pd_primal_step_f64(const double *p, double *x, double *xbar,
  * reads xbar_in, x, bt, p_in; writes p_out, x (in place), xbar_out.
  * xbar_out must not alias xbar_in and p_out must not alias p_in (neighbouring
  * workgroups read the old values).  p_in may be NULL on the first iteration.
- * flags: NSOL_PD_REG_* | NSOL_PD_DATA_*. */
+ * flags: NSOL_PD_REG_* | NSOL_PD_DATA_*; with NSOL_PD_REG_ISOTROPIC the launch is
+ * k_pd_fused_iso's (same traffic, same aliasing rules). */
 int nsol_pd_fused_iter_f32(const float *xbar_in, float *xbar_out, float *x,
                            const float *bt, const float *p_in, float *p_out,
                            int ndim, int64_t nz, int64_t ny, int64_t nx,

@@ -30,7 +30,8 @@ from ..similarity_measures import SimilarityMeasures
 def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  tv_solver="PD", alpha=0.01, iterations=10, iter_max=10,
                  rho=0.1, minimizer="lsmr", data_loss="linear",
-                 data_loss_scale=1., L2=8, verbose=0, dtype=None):
+                 data_loss_scale=1., L2=8, verbose=0, dtype=None,
+                 isotropic=False):
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -72,6 +73,11 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
             data_loss_scale=data_loss_scale, x_scale=x_scale)
         pg = prox.prox_tv_conj if reconstruction_type == "TVL2" \
             else prox.prox_huber_conj
+        if isotropic:
+            # the per-voxel vector norm ADMM shrinks by (prox_*_conj_isotropic)
+            iso = prox.prox_tv_conj_isotropic if reconstruction_type == "TVL2" \
+                else prox.prox_huber_conj_isotropic
+            pg = lambda x, sigma: iso(x, sigma, dimension)
         return pd.PrimalDualSolver(prox_f=prox_f, prox_g_conj=pg, B=D_1D,
                                    B_conj=D_adj_1D, L2=L2, alpha=alpha,
                                    x0=x0, iterations=iterations,
@@ -105,6 +111,10 @@ def main(argv=None):
     ap.add_argument("--dtype", default="float32",
                     choices=["float32", "float64"])
     ap.add_argument("--verbose", type=int, default=0)
+    ap.add_argument("--isotropic", action="store_true",
+                    help="primal-dual TVL2 / HuberL2: the isotropic TV / Huber "
+                         "norm (the one ADMM minimises) instead of the sum over "
+                         "the gradient's components")
     ap.add_argument("--observe-every", type=int, default=None, metavar="K",
                     help="evaluate the measures on the device every K "
                          "iterations (and at the last) instead of on a host "
@@ -127,7 +137,7 @@ def main(argv=None):
             observed_nda, spacing, args.blur, args.reconstruction_type,
             args.solver, alpha, args.iterations, args.iter_max, args.rho,
             args.minimizer, args.data_loss, args.data_loss_scale, args.L2,
-            args.verbose, np.dtype(args.dtype).type)
+            args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \

@@ -5,6 +5,11 @@ without plotting).
     python -m nsol_amd.application.run_denoising --observation in.nii.gz \\
         --result out.nii.gz --reconstruction-type TVL2 --alpha 0.03 \\
         --iterations 50 [--reference gt.nii.gz] [--L2 8] [--dtype float32]
+        [--isotropic]
+
+--isotropic: the regulariser is the isotropic TV / Huber norm -- the per-voxel
+vector norm that PriorMeasures reports and ADMM minimises -- instead of the
+reference's sum over the components (one fused launch per iteration).
 
 Several values of --alpha are a parameter sweep (nsol_amd/parameter_sweep.py): the
 members run stacked, one launch per iteration for all of them; --result-dir DIR
@@ -25,9 +30,10 @@ from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
 
 
-def wiring(observed_nda, reconstruction_type):
+def wiring(observed_nda, reconstruction_type, isotropic=False):
     """Wiring of run_denoising.py:95-154: the callables, start and scale that
-    PrimalDualSolver / PrimalDualSweep are built from."""
+    PrimalDualSolver / PrimalDualSweep are built from.  isotropic: the dual prox
+    projects every voxel's gradient vector (prox_*_conj_isotropic)."""
     dimension = observed_nda.ndim
     b = observed_nda.flatten()
     x0 = observed_nda.flatten()
@@ -51,15 +57,23 @@ def wiring(observed_nda, reconstruction_type):
                          reconstruction_type)
     prox_g_conj = prox.prox_huber_conj \
         if reconstruction_type.startswith("Huber") else prox.prox_tv_conj
+    if isotropic:
+        if reconstruction_type.startswith("Huber"):
+            prox_g_conj = lambda x, sigma: prox.prox_huber_conj_isotropic(
+                x, sigma, dimension)
+        else:
+            prox_g_conj = lambda x, sigma: prox.prox_tv_conj_isotropic(
+                x, sigma, dimension)
     return dict(prox_f=prox_f, prox_g_conj=prox_g_conj, B=D_1D, B_conj=D_adj_1D,
                 x0=x0, x_scale=x_scale)
 
 
 def build_solver(observed_nda, reconstruction_type, alpha, iterations, L2=8,
-                 verbose=0, dtype=None, alg_type="ALG2"):
+                 verbose=0, dtype=None, alg_type="ALG2", isotropic=False):
     return pd.PrimalDualSolver(
         L2=L2, alpha=alpha, iterations=iterations, verbose=verbose,
-        alg_type=alg_type, dtype=dtype, **wiring(observed_nda, reconstruction_type))
+        alg_type=alg_type, dtype=dtype,
+        **wiring(observed_nda, reconstruction_type, isotropic))
 
 
 def member_result_path(result_dir, like, alpha):
@@ -78,7 +92,7 @@ def run_sweep(args, observed_nda, x_ref, reader):
         L2=args.L2, parameters={"alpha": list(args.alpha)},
         iterations=args.iterations, alg_type=args.alg_type,
         dtype=np.dtype(args.dtype).type,
-        **wiring(observed_nda, args.reconstruction_type))
+        **wiring(observed_nda, args.reconstruction_type, args.isotropic))
     if x_ref is not None:
         sweep.set_measures({
             m: (lambda x, m=m:
@@ -142,6 +156,10 @@ def main(argv=None):
                     help="evaluate the measures on the device every K "
                          "iterations (and at the last) instead of on a host "
                          "copy of every iterate")
+    ap.add_argument("--isotropic", action="store_true",
+                    help="isotropic TV / Huber: project every voxel's gradient "
+                         "vector onto the unit ball (what PriorMeasures reports "
+                         "and ADMM minimises) instead of clamping its components")
     ap.add_argument("--result-dir", default=None, metavar="DIR",
                     help="with several --alpha: every member's result as "
                          "<stem>_alpha<value><ext> and the sweep's parameters "
@@ -168,7 +186,8 @@ def main(argv=None):
                               args.iterations, L2=args.L2,
                               verbose=args.verbose,
                               dtype=np.dtype(args.dtype).type,
-                              alg_type=args.alg_type)
+                              alg_type=args.alg_type,
+                              isotropic=args.isotropic)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \

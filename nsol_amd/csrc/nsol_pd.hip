@@ -207,6 +207,11 @@ int fused_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt,
                     int64_t nx, double wx, double wy, double wz, double sigma,
                     double hden, double tau, double tl, double theta, int flags,
                     void *stream, int64_t pitch = 0) {
+  if (flags & NSOL_PD_REG_ISOTROPIC)   // k_pd_fused_iso, nsol_pdi.hip
+    return pd_iso_fused_iter<T>(xbar_in, xbar_out, x, bt, p_in, p_out, ndim, nz, ny, nx,
+                                wx, wy, wz, sigma, hden, tau, tl, theta, flags, stream,
+                                pitch, PdLaunchTune{g_tune.zchunk, g_tune.ry,
+                                                    g_tune.xcd_map, g_tune.rag});
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!xbar_in || !xbar_out || !x || !bt || !p_out || xbar_in == xbar_out ||
       p_in == p_out)
@@ -357,11 +362,14 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
   T *xcur = x, *xoth = x_alt;
   int slot = 0;
   const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
+  // the isotropic projection has the one-iteration forms only (the multi-iteration
+  // entries decline it): one launch of k_pd_fused_iso per iteration
+  const bool iso = (flags & NSOL_PD_REG_ISOTROPIC) != 0;
   int n = 0;
   while (n < iterations) {
     const T *pin = (n == 0 && p_is_zero) ? nullptr : pp[slot];
     int rc = -2;
-    if (xoth && n + 1 < iterations && !g_tune.force_two_pass) {
+    if (!iso && xoth && n + 1 < iterations && !g_tune.force_two_pass) {
       // deepest temporal blocking first: 3 iterations per pass (tiled
       // footprints), then 2 (tiled or full-row footprints), then 1
       double h3[3], tl3[3];
@@ -427,8 +435,10 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
     }
     const double hden = huber ? 1.0 + sig[n] * gamma_huber : 1.0;
     if (g_tune.force_two_pass && !pitched) {
-      rc = dual_step_impl<T>(xb[slot], pin, pp[slot ^ 1], ndim, nz, ny, nx, wx, wy,
-                             wz, sig[n], hden, stream);
+      rc = iso ? pd_iso_dual_step<T>(xb[slot], pin, pp[slot ^ 1], ndim, nz, ny, nx, wx,
+                                     wy, wz, sig[n], hden, stream)
+               : dual_step_impl<T>(xb[slot], pin, pp[slot ^ 1], ndim, nz, ny, nx, wx, wy,
+                                   wz, sig[n], hden, stream);
       if (rc) return rc;
       rc = primal_step_impl<T>(pp[slot ^ 1], xcur, xb[slot ^ 1], bt, ndim, nz, ny,
                                nx, wx, wy, wz, tau[n], tau[n] * lambda, theta[n],

@@ -466,6 +466,9 @@ int fused2_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out,
                 int64_t ny, int64_t nx, double wx, double wy, double wz,
                 const double *sigma, const double *hden, const double *tau,
                 const double *tl, const double *theta, int flags, void *stream) {
+  // the isotropic projection needs a neighbour's whole dual vector: only
+  // k_pd_fused_iso (nsol_pdi.hip) has that form
+  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!xbar_in || !xbar_out || !x_in || !x_out || !bt || !p_out ||
       xbar_in == xbar_out || p_in == p_out || x_in == x_out)

@@ -119,6 +119,25 @@ __device__ __forceinline__ T adj_term(T p, T p_prev, T w) {
   return UNIT ? p_prev - p : p * (-w) + p_prev * w;
 }
 
+// The knobs of nsol_pd.hip that shape a one-iteration launch, handed to the
+// isotropic launcher of nsol_pdi.hip (which nsol_pd_fused_iter_* / nsol_pd_run_*
+// call when NSOL_PD_REG_ISOTROPIC is set).
+struct PdLaunchTune {
+  int zchunk, ry, xcd_map, rag;
+};
+// one iteration through k_pd_fused_iso / the isotropic dual step of the two-pass
+// form (nsol_pdi.hip); arguments as fused_iter_impl / dual_step_impl
+template <typename T>
+int pd_iso_fused_iter(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p_in,
+                      T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,
+                      double wy, double wz, double sigma, double hden, double tau,
+                      double tl, double theta, int flags, void *stream, int64_t pitch,
+                      PdLaunchTune tune);
+template <typename T>
+int pd_iso_dual_step(const T *xbar, const T *p_in, T *p_out, int ndim, int64_t nz,
+                     int64_t ny, int64_t nx, double wx, double wy, double wz,
+                     double sigma, double hden, void *stream);
+
 template <bool L1, typename T>
 __device__ __forceinline__ T prox_data_s(T u, T bt, T tl, T one_plus_tl) {
   if constexpr (L1) return prox_ell1(u, bt, tl);

@@ -1416,6 +1416,9 @@ int fusedk_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T 
                 const double *sigma, const double *hden, const double *tau,
                 const double *tl, const double *theta, int flags, void *stream,
                 int64_t pitch = 0) {
+  // the footprint overlap is sized for the component-wise clamp: the isotropic
+  // projection (nsol_pdi.hip) has no multi-iteration form
+  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!xbar_in || !xbar_out || !x_in || !x_out || !bt || !p_out || !sigma ||
       !hden || !tau || !tl || !theta || xbar_in == xbar_out || p_in == p_out ||

@@ -481,6 +481,9 @@ int persist_run(const T *xbar, const T *x, const T *bt, const T *p, T *xbar_out,
                 const double *sig, const double *tau, const double *theta, int iterations,
                 int p_is_zero, double gamma_huber, int flags, void *ws, int64_t ws_bytes,
                 unsigned int *err_word, void *stream) {
+  // the faces handed between workgroups carry one dual component each: the
+  // isotropic projection (nsol_pdi.hip) has no persistent form
+  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   constexpr int VEC = 16 / (int)sizeof(T);
   if (!xbar || !x || !bt || !p || !xbar_out || !x_out || !p_out || !sig || !tau ||

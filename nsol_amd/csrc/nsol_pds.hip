@@ -165,6 +165,9 @@ int sweep_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int memb
                    const double *theta, int iterations, int p_is_zero, double gamma_huber,
                    int flags, void *tab_host, void *tab, int64_t tab_bytes,
                    int *final_slot, void *stream) {
+  // the stacked kernel shares pd_fused_tile, the component-wise clamp: isotropic
+  // sweeps run their members one after the other (nsol_pdi.hip)
+  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
   if (!sweep_takes(members, ndim, nz, ny, nx)) return -2;
   if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
       tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)

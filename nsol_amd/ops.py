@@ -13,6 +13,9 @@ from .device import suffix, stream_ptr, empty_like
 MODES = {"constant": 0, "wrap": 1, "nearest": 2, "reflect": 3, "mirror": 4}
 LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2, "cauchy": 3, "arctan": 4}
 PD_REG_TV, PD_REG_HUBER, PD_DATA_L2, PD_DATA_L1 = 0, 1, 0, 2
+# or-ed with PD_REG_TV / PD_REG_HUBER: the dual projection divides the voxel's
+# whole gradient vector by max(1, its Euclidean norm) (NSOL_PD_REG_ISOTROPIC)
+PD_REG_ISOTROPIC = 4
 
 
 def _fn(name, t):
@@ -479,6 +482,27 @@ def prox_dual_clamp(x, den=1.0, out=None):
     _lib.check(_fn("prox_dual_clamp", x)(_p(out), _p(x), float(den),
                                          x.numel(), stream_ptr()),
                "nsol_prox_dual_clamp")
+    return _wrote(out)
+
+
+def prox_dual_project(x, dim, den=1.0, out=None):
+    """x holds `dim` blocks of x.numel() / dim elements; every voxel's vector
+    (x / den) is divided by max(1, its Euclidean norm): the isotropic prox_tv_conj
+    (den = 1) / prox_huber_conj (den = 1 + sigma * gamma)."""
+    _chk(x)
+    dim = int(dim)
+    if dim < 1 or dim > 3:
+        raise ValueError("dimension must be 1, 2 or 3, not %d" % dim)
+    if x.numel() == 0 or x.numel() % dim:
+        raise ValueError("%d elements are not %d blocks of equal length" %
+                         (x.numel(), dim))
+    if out is None:
+        out = empty_like(x)
+    else:
+        _same(x, out)
+    _lib.check(_fn("prox_dual_project", x)(_p(out), _p(x), float(den),
+                                           x.numel() // dim, dim, stream_ptr()),
+               "nsol_prox_dual_project")
     return _wrote(out)
 
 
@@ -962,6 +986,15 @@ def pd_dual_step(xbar, p_in, p_out, shape, w, sigma, hden):
     _wrote(p_out)
 
 
+def pd_dual_step_iso(xbar, p_in, p_out, shape, w, sigma, hden):
+    """pd_dual_step with the isotropic projection (PD_REG_ISOTROPIC)."""
+    ndim, nz, ny, nx = dims3(shape)
+    _lib.check(_fn("pd_dual_step_iso", xbar)(
+        _p(xbar), _p(p_in), _p(p_out), ndim, nz, ny, nx, w[0], w[1], w[2],
+        float(sigma), float(hden), stream_ptr()), "nsol_pd_dual_step_iso")
+    _wrote(p_out)
+
+
 def pd_primal_step(p, x, xbar, bt, shape, w, tau, tl, theta, flags):
     ndim, nz, ny, nx = dims3(shape)
     _lib.check(_fn("pd_primal_step", x)(
@@ -1292,7 +1325,10 @@ def pd_run(xbar0, xbar1, x, bt, p0, p1, shape, w, lmbda, sigma, tau, theta,
         if slot.value & 2:
             x.data, x_alt.data = x_alt.data, x.data
         return int(slot.value) & 1
-    if PD_PERSIST and persist_pays(shape, np.size(sigma)):
+    # (the persistent kernel declines the isotropic projection: no attempt, so
+    # no pending-run record for a launch that is never made)
+    if PD_PERSIST and not (int(flags) & PD_REG_ISOTROPIC) and \
+            persist_pays(shape, np.size(sigma)):
         # the result goes to the other half of the ping-pong arrays (and to the
         # x scratch volume): the inputs stay as they are until the run's error
         # word has been looked at

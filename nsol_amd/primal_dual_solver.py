@@ -3,7 +3,9 @@ nsol/primal_dual_solver.py:26-403).
 
 `run()` picks one of three execution forms:
   fused   B = grad, B_conj = grad_adj of nsol_amd.linear_operators, prox_g_conj
-          in {prox_tv_conj, prox_huber_conj}, prox_f in {prox_ell1_denoising,
+          in {prox_tv_conj, prox_huber_conj} or their isotropic forms
+          {prox_tv_conj_isotropic, prox_huber_conj_isotropic} (one single-pass
+          kernel per iteration, k_pd_fused_iso), prox_f in {prox_ell1_denoising,
           prox_ell2_denoising} -- recognised THROUGH caller-side lambdas with
           a symbolic probe; nsol_pd_run_* enqueues the whole run: three
           iterations per pass over memory on large 3-D volumes (11 words of
@@ -122,13 +124,19 @@ class PrimalDualSolver(Solver):
                 tuple(dBt[2]) != tuple(gop._out_shape(shape)):
             return None
         dg = trace_prox(self._prox_g_conj, gop.dimension * n)
-        if dg is None or dg[0] not in ("prox_tv_conj", "prox_huber_conj") \
-                or not isinstance(dg[1], TauSym):
+        if dg is None or dg[0] not in (
+                "prox_tv_conj", "prox_huber_conj", "prox_tv_conj_iso",
+                "prox_huber_conj_iso") or not isinstance(dg[1], TauSym):
             return None
+        huber = dg[0].startswith("prox_huber_conj")
+        flags = ops.PD_REG_HUBER if huber else ops.PD_REG_TV
+        if dg[0].endswith("_iso"):
+            # the vector norm is taken over the gradient operator's components
+            if dg[-1] != gop.dimension:
+                return None
+            flags |= ops.PD_REG_ISOTROPIC
         return dict(shape=tuple(shape), w=gop.w, dim=gop.dimension, n=n,
-                    flags=(ops.PD_REG_HUBER if dg[0] == "prox_huber_conj"
-                           else ops.PD_REG_TV),
-                    gamma=(dg[2] if dg[0] == "prox_huber_conj" else 0.05))
+                    flags=flags, gamma=(dg[2] if huber else 0.05))
 
     def plan(self):
         """Recognise a fully native configuration.  Returns a dict for the
@@ -300,13 +308,14 @@ class PrimalDualSolver(Solver):
         shape, w = dual["shape"], dual["w"]
         p = torch.empty(dual["dim"] * x.numel(), dtype=x.dtype, device=x.device)
         huber = bool(dual["flags"] & ops.PD_REG_HUBER)
+        dual_step = ops.pd_dual_step_iso \
+            if dual["flags"] & ops.PD_REG_ISOTROPIC else ops.pd_dual_step
         for i in range(self._iterations):
             if self._verbose:
                 print("Primal-Dual iteration %d/%d" % (i + 1,
                                                        self._iterations))
             hden = 1. + sig[i] * dual["gamma"] if huber else 1.
-            ops.pd_dual_step(xbar, None if i == 0 else p, p, shape, w, sig[i],
-                             hden)
+            dual_step(xbar, None if i == 0 else p, p, shape, w, sig[i], hden)
             u = ops.grad_adj_axpy(p, x, ta[i], shape, w)
             x_new = pf(u, float(ta[i] * lmbda))
             xbar = ops.extrapolate(x_new, x, th[i], out=xbar)

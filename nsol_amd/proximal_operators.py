@@ -82,6 +82,22 @@ def _elementwise(x, fn, desc):
     return to_numpy(fn(to_device(arr, dt).view(-1)), dt).reshape(arr.shape)
 
 
+def _project(x, dimension, den, desc):
+    """The isotropic dual prox of a stacked gradient field x."""
+    dimension = int(dimension)
+    if dimension not in (1, 2, 3):
+        raise ValueError("dimension must be 1, 2 or 3, not %r" % (dimension,))
+    if isinstance(x, Sym):
+        size = x.size
+    else:
+        size = int(x.numel()) if is_device_tensor(x) else int(np.size(x))
+    if size == 0 or size % dimension:
+        raise ValueError("a gradient field of %d elements is not %d blocks of "
+                         "equal length" % (size, dimension))
+    return _elementwise(
+        x, lambda d: ops.prox_dual_project(d, dimension, den), desc)
+
+
 class ProximalOperators(object):
 
     @staticmethod
@@ -151,3 +167,21 @@ class ProximalOperators(object):
         return _elementwise(
             x, lambda d: ops.prox_dual_clamp(d, 1. + sigma * gamma),
             ("prox_huber_conj", sigma, float(gamma)))
+
+    @staticmethod
+    def prox_tv_conj_isotropic(x, sigma, dimension):
+        """prox_tv_conj for the isotropic total variation: x is the stacked
+        gradient field of linear_operators.py:121-137 (`dimension` blocks), and
+        every voxel's vector is divided by max(1, its Euclidean norm) -- the norm
+        prior_measures.py:27-52 sums and admm_linear_solver.py:239-253 shrinks
+        by -- where proximal_operators.py:138-140 clamps component by component."""
+        return _project(x, dimension, 1.0,
+                        ("prox_tv_conj_iso", sigma, int(dimension)))
+
+    @staticmethod
+    def prox_huber_conj_isotropic(x, sigma, dimension, gamma=0.05):
+        """prox_huber_conj (proximal_operators.py:156-159) with the per-voxel
+        vector norm: (x / (1 + sigma gamma)) / max(1, |x / (1 + sigma gamma)|_2)."""
+        return _project(x, dimension, 1. + sigma * gamma,
+                        ("prox_huber_conj_iso", sigma, float(gamma),
+                         int(dimension)))
