@@ -54,19 +54,6 @@ constexpr int kDmaLxb = 16;   // lanes per tile row of the LDS-DMA staged kernel
 #define NSOL_B3_AUX_RAW 0
 #endif
 
-inline int blur3_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 // what nsol_conv.hip calls: -2 when the kernel does not apply (nothing launched).
 // epi 1: io = ca * blur(x) + cb * io in place (out = io) and *result = the sum of
 // squares of the new io (part: >= tiles doubles of scratch).  epi 2: out = blur(x),
@@ -1422,7 +1409,7 @@ int launch_blur3_dma(const T *x, T *out, int64_t nz, int64_t ny, int64_t nx,
   // ceil(workgroups / slots) rounds of (chunk + 2R) plane steps
   const int per_cu = (int)((160 * 1024) / lds) < (32 / NWD) ? (int)((160 * 1024) / lds)
                                                             : (32 / NWD);
-  const int64_t slots = (int64_t)blur3_cu_count() * (per_cu < 1 ? 1 : per_cu);
+  const int64_t slots = (int64_t)cu_count() * (per_cu < 1 ? 1 : per_cu);
   int64_t zchunk = nz, best = -1;
   for (int64_t c = 1; c <= nz && (nz + c - 1) / c >= R; ++c) {
     const int64_t len = (nz + c - 1) / c;

@@ -35,6 +35,27 @@ inline int grid_for(int64_t n, int per_block = kBlock) {
   return static_cast<int>(b);
 }
 
+// what a 16-byte vector access needs of its base address
+template <typename T>
+inline bool aligned16(const T *a) {
+  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
+}
+
+// compute units of the device that was current at the first call (256 if unknown);
+// one cache for the whole library
+inline int cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipGetDeviceProperties(&prop, dev) == hipSuccess)
+      n = prop.multiProcessorCount;
+    if (n <= 0) n = 256;
+  }
+  return n;
+}
+
 // Volume extents + inverse spacings handed to kernels by value.
 template <typename T>
 struct Geom {

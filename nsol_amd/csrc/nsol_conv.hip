@@ -839,7 +839,7 @@ int launch_blur3(const T *x, T *out, int64_t nz, int64_t ny, int64_t nx,
   // ceil(workgroups / CUs) rounds of (chunk + 2R) plane steps; take the chunk
   // count that minimises that (512^3, 64 tiles: 4 chunks = 256 workgroups = one
   // round of 140 steps, 0.418 ms; 8 chunks = two rounds of 76, 0.444 ms)
-  const int64_t cus = blur3_cu_count();
+  const int64_t cus = cu_count();
   int64_t zchunk = nz, best = -1;
   for (int64_t c = 1; c <= nz && (nz + c - 1) / c >= R; ++c) {
     const int64_t len = (nz + c - 1) / c;

@@ -426,8 +426,8 @@ int u_impl(const T *Av, const T *v, T *u_top, T *u_bot, int bmode, int ndim,
       (bmode != kBNone && (!v || !u_bot)) || (!Av && bmode == kBNone))
     return NSOL_EINVAL;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = (!Av || ptr16(Av)) && ptr16(u_top) && (!v || ptr16(v)) &&
-                  (!u_bot || ptr16(u_bot)) && G.n % 4 == 0;
+  const bool al = (!Av || aligned16(Av)) && aligned16(u_top) && (!v || aligned16(v)) &&
+                  (!u_bot || aligned16(u_bot)) && G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -451,8 +451,8 @@ int v_impl(const T *Atu, const T *u_bot, const T *v, T *v_out, int bmode, int nd
       (bmode != kBNone && !u_bot))
     return NSOL_EINVAL;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = ptr16(Atu) && ptr16(v) && ptr16(v_out) && (!u_bot || ptr16(u_bot)) &&
-                  G.n % 4 == 0;
+  const bool al = aligned16(Atu) && aligned16(v) && aligned16(v_out) &&
+                  (!u_bot || aligned16(u_bot)) && G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -489,7 +489,7 @@ int tk1_reg_impl(const T *x, const T *g, T *grad, int ndim, int64_t nz, int64_t 
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!x || !g || !grad || !result || !ws || x == grad) return NSOL_EINVAL;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = ptr16(x) && ptr16(g) && ptr16(grad) && G.n % 4 == 0;
+  const bool al = aligned16(x) && aligned16(g) && aligned16(grad) && G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -513,8 +513,8 @@ int tk1_objective_impl(const T *x, const T *g, T *grad, const T *d, const T *gol
       (gold && (gold == grad || ydiff == grad || ydiff == x || ydiff == g || ydiff == d)))
     return NSOL_EINVAL;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = ptr16(x) && ptr16(g) && ptr16(grad) && (!d || ptr16(d)) &&
-                  (!gold || (ptr16(gold) && ptr16(ydiff))) && G.n % 4 == 0;
+  const bool al = aligned16(x) && aligned16(g) && aligned16(grad) && (!d || aligned16(d)) &&
+                  (!gold || (aligned16(gold) && aligned16(ydiff))) && G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -535,7 +535,7 @@ int tk1_norm_impl(const T *x, int ndim, int64_t nz, int64_t ny, int64_t nx, doub
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!x || !result || !ws) return NSOL_EINVAL;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = ptr16(x) && G.n % 4 == 0;
+  const bool al = aligned16(x) && G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -558,7 +558,8 @@ int tk1_lanczos_impl(const T *x, const T *g, const T *z, T *out, int ndim, int64
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!x || !g || !out || !result || !ws || x == out || z == out) return NSOL_EINVAL;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = ptr16(x) && ptr16(g) && ptr16(out) && (!z || ptr16(z)) && G.n % 4 == 0;
+  const bool al = aligned16(x) && aligned16(g) && aligned16(out) && (!z || aligned16(z)) &&
+                  G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;

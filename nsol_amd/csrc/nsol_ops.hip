@@ -747,7 +747,7 @@ int grad_impl(const T *x, T *g, int ndim, int64_t nz, int64_t ny, int64_t nx,
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!x || !g) return NSOL_EINVAL;
   Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  return dispatch_stencil<T>(nz, ny, nx, ptr16(x) && ptr16(g) && G.n % 4 == 0,
+  return dispatch_stencil<T>(nz, ny, nx, aligned16(x) && aligned16(g) && G.n % 4 == 0,
                              [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -763,7 +763,7 @@ int grad_adj_impl(const T *p, T *out, int ndim, int64_t nz, int64_t ny,
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!p || !out) return NSOL_EINVAL;
   Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  return dispatch_stencil<T>(nz, ny, nx, ptr16(p) && ptr16(out) && G.n % 4 == 0,
+  return dispatch_stencil<T>(nz, ny, nx, aligned16(p) && aligned16(out) && G.n % 4 == 0,
                              [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -781,7 +781,7 @@ int grad_adj_axpy_impl(const T *p, const T *x, T *out, int ndim, int64_t nz, int
   if (!p || !x || !out) return NSOL_EINVAL;
   Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
   return dispatch_stencil<T>(nz, ny, nx,
-                             ptr16(p) && ptr16(x) && ptr16(out) && G.n % 4 == 0,
+                             aligned16(p) && aligned16(x) && aligned16(out) && G.n % 4 == 0,
                              [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -822,8 +822,8 @@ int admm_vw_impl(const T *x, T *v, T *w, const T *c, T *rhs, int ndim,
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!x || !w || (result && (!ws || !rhs))) return NSOL_EINVAL;
   Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  const bool al = ptr16(x) && (!v || ptr16(v)) && ptr16(w) && (!c || ptr16(c)) &&
-                  (!rhs || ptr16(rhs)) && G.n % 4 == 0;
+  const bool al = aligned16(x) && (!v || aligned16(v)) && aligned16(w) && (!c || aligned16(c)) &&
+                  (!rhs || aligned16(rhs)) && G.n % 4 == 0;
   return dispatch_stencil<T>(nz, ny, nx, al, [&](auto vec, auto rows, auto rag) {
     constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
     constexpr bool RG = decltype(rag)::value;
@@ -856,8 +856,8 @@ int admm_vw_g_impl(const T *x, const T *w_in, T *w_out, const T *c, const T *atb
       !result || !ws)
     return NSOL_EINVAL;
   constexpr int VEC = 16 / sizeof(T);
-  if (ndim != 3 || nx % VEC != 0 || nx < VEC || !ptr16(x) || !ptr16(w_in) || !ptr16(w_out) ||
-      (c && !ptr16(c)) || !ptr16(atb) || !ptr16(g) || (nz * ny * nx) % 4 != 0)
+  if (ndim != 3 || nx % VEC != 0 || nx < VEC || !aligned16(x) || !aligned16(w_in) ||
+      !aligned16(w_out) || (c && !aligned16(c)) || !aligned16(atb) || !aligned16(g) || (nz * ny * nx) % 4 != 0)
     return -2;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
   constexpr int XT = kBlock / 4;

@@ -21,6 +21,7 @@
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
 #include "nsol_pd_fused_body.hpp"
+#include "nsol_pd_launch.hpp"
 
 using namespace nsol;
 
@@ -120,86 +121,39 @@ __global__ __launch_bounds__(kBlock) void k_pd_fused(
                                            tx, ty, zc, zchunk);
 }
 
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG = false>
-int launch_fused_t(const T *xbar_in, T *xbar_out, T *x, const T *bt,
-                   const T *p_in, T *p_out, const Geom<T> &G,
-                   const PdScalars<T> &S, hipStream_t st) {
-  constexpr int LY = kWave / LX;
-  constexpr int TY = (kBlock / kWave) * LY * RY;
-  constexpr int TX = LX * VEC;
-  const int64_t ntx = (G.nx + TX - 1) / TX;
-  const int64_t nty = (G.ny + TY - 1) / TY;
-  int64_t zchunk = g_tune.zchunk;
-  if (zchunk <= 0) {
-    // enough workgroups to fill 256 CUs several times; cache-resident volumes
-    // get chunks as short as 2 planes (the extra plane per chunk is an L2 hit
-    // there and 8 workgroups would leave the chip idle)
-    const int64_t want = (4096 + ntx * nty - 1) / (ntx * nty);
-    zchunk = (G.nz + want - 1) / want;
-    if (zchunk < 2) zchunk = 2;
+struct FusedKernel {
+  template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+  static int launch_t(const PdLaunchArgs<T> &a) {
+    const PdGridPlan g = pd_plan_grid<VEC, LX, RY>(a.G, 1, a.tune);
+    if (g.blocks > kPdMaxBlocks) return NSOL_EINVAL;
+    hipLaunchKernelGGL((k_pd_fused<T, VEC, LX, RY, NDIM, RAG>), dim3((unsigned)g.blocks),
+                       dim3(kBlock), 0, a.st, a.xbar_in, a.xbar_out, a.x, a.bt, a.p_in,
+                       a.p_out, a.G, a.S, g.ntx, g.nty, g.zchunk, g.slab);
+    return launch_status();
   }
-  if (zchunk > G.nz) zchunk = G.nz;
-  const int64_t nzc = (G.nz + zchunk - 1) / zchunk;
-  int64_t slab = 0;
-  int64_t blocks = ntx * nty * nzc;
-  if (g_tune.xcd_map && nty >= 16) {
-    slab = (nty + 7) / 8;
-    blocks = 8 * slab * ntx * nzc;
-  }
-  if (blocks > 0x7fffffff) return NSOL_EINVAL;
-  hipLaunchKernelGGL((k_pd_fused<T, VEC, LX, RY, NDIM, RAG>), dim3((unsigned)blocks),
-                     dim3(kBlock), 0, st, xbar_in, xbar_out, x, bt, p_in, p_out,
-                     G, S, (int)ntx, (int)nty, (int)zchunk, (int)slab);
-  return launch_status();
-}
 
-template <typename T, int VEC, int LX, int RY, bool RAG = false>
-int launch_fused_nd(const T *xbar_in, T *xbar_out, T *x, const T *bt,
-                    const T *p_in, T *p_out, const Geom<T> &G,
-                    const PdScalars<T> &S, hipStream_t st) {
-  switch (G.ndim) {
-    case 1: return launch_fused_t<T, VEC, LX, 1, 1, RAG>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-    case 2: return launch_fused_t<T, VEC, LX, RY, 2, RAG>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-    default: return launch_fused_t<T, VEC, LX, RY, 3, RAG>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
+  template <typename T, int VEC, int LX, int RY, bool RAG>
+  static int launch_nd(const PdLaunchArgs<T> &a) {
+    switch (a.G.ndim) {
+      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
+      case 2: return launch_t<T, VEC, LX, RY, 2, RAG>(a);
+      default: return launch_t<T, VEC, LX, RY, 3, RAG>(a);
+    }
   }
-}
 
-template <typename T, int VEC, int LX, bool RAG = false>
-int launch_fused_ry(const T *xbar_in, T *xbar_out, T *x, const T *bt,
-                    const T *p_in, T *p_out, const Geom<T> &G,
-                    const PdScalars<T> &S, hipStream_t st) {
-  int ry = g_tune.ry;
-  if (ry == 0) {
-    // two rows per lane unless that leaves fewer than ~2 workgroups per CU
-    constexpr int TY2 = (kBlock / kWave) * (kWave / LX) * 2;
-    const int64_t tiles = ((G.nx + LX * VEC - 1) / (LX * VEC)) * ((G.ny + TY2 - 1) / TY2);
-    ry = (tiles * ((G.nz + 1) / 2) < 512) ? 1 : 2;
+  // knob "pd_ry": 0 = choose; 4 has no ragged form and falls to 2, as any other value
+  template <typename T, int VEC, int LX, bool RAG>
+  static int launch(const PdLaunchArgs<T> &a) {
+    int ry = a.tune.ry;
+    if (ry == 0) ry = pd_auto_rows_per_lane<VEC, LX>(a.G, 1);
+    switch (ry) {
+      case 1: return launch_nd<T, VEC, LX, 1, RAG>(a);
+      case 4:
+        if constexpr (!RAG) return launch_nd<T, VEC, LX, 4, false>(a);
+      default: return launch_nd<T, VEC, LX, 2, RAG>(a);
+    }
   }
-  switch (ry) {
-    case 1: return launch_fused_nd<T, VEC, LX, 1, RAG>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-    case 4:
-      if constexpr (!RAG)
-        return launch_fused_nd<T, VEC, LX, 4>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-    default: return launch_fused_nd<T, VEC, LX, 2, RAG>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-  }
-}
-
-template <typename T>
-inline bool aligned16(const T *a) {
-  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
-}
-
-template <typename T>
-PdScalars<T> make_scalars(double sigma, double hden, double tau, double tl,
-                          double theta, int flags, bool has_p) {
-  PdScalars<T> S;
-  S.sigma = (T)sigma; S.hden = huber_den<T>(hden); S.tau = (T)tau; S.tl = (T)tl;
-  S.one_plus_tl = prox_den<T>(tl); S.theta = (T)theta;
-  S.huber = (flags & NSOL_PD_REG_HUBER) ? 1 : 0;
-  S.l1 = (flags & NSOL_PD_DATA_L1) ? 1 : 0;
-  S.has_p = has_p ? 1 : 0;
-  return S;
-}
+};
 
 template <typename T>
 int fused_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt,
@@ -207,41 +161,23 @@ int fused_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt,
                     int64_t nx, double wx, double wy, double wz, double sigma,
                     double hden, double tau, double tl, double theta, int flags,
                     void *stream, int64_t pitch = 0) {
+  const PdLaunchTune tune{g_tune.zchunk, g_tune.ry, g_tune.xcd_map, g_tune.rag};
   if (flags & NSOL_PD_REG_ISOTROPIC)   // k_pd_fused_iso, nsol_pdi.hip
     return pd_iso_fused_iter<T>(xbar_in, xbar_out, x, bt, p_in, p_out, ndim, nz, ny, nx,
                                 wx, wy, wz, sigma, hden, tau, tl, theta, flags, stream,
-                                pitch, PdLaunchTune{g_tune.zchunk, g_tune.ry,
-                                                    g_tune.xcd_map, g_tune.rag});
+                                pitch, tune);
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!xbar_in || !xbar_out || !x || !bt || !p_out || xbar_in == xbar_out ||
       p_in == p_out)
     return NSOL_EINVAL;
-  // (rows at a pitch: only the strides change -- the kernel below indexes rows and
-  // planes by G.sy / G.sz and a gradient field's components by G.n)
-  const Geom<T> G = make_geom_pitched<T>(ndim, nz, ny, nx, pitch, wx, wy, wz);
-  const PdScalars<T> S =
-      make_scalars<T>(sigma, hden, tau, tl, theta, flags, p_in != nullptr);
-  hipStream_t st = as_stream(stream);
-  constexpr int VW = 16 / sizeof(T);  // elements per 16-byte access
-  const bool vec_ok = (nx % VW == 0) && aligned16(xbar_in) && aligned16(xbar_out) &&
-                      aligned16(x) && aligned16(bt) && aligned16(p_out) &&
-                      (!p_in || aligned16(p_in)) && ((nz * ny * nx) % VW == 0);
-  if (G.padded && !(g_tune.rag && nx >= 2 * VW) && !vec_ok) return NSOL_EINVAL;
-  if (vec_ok) {
-    if (nx / VW >= kWave)
-      return launch_fused_ry<T, VW, 64>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-    return launch_fused_ry<T, VW, 16>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-  }
-  // rows that are not a multiple of 16 bytes / unaligned arrays: element-aligned
-  // 16-byte accesses (g_tune.rag = 0 restores the 4-byte form, for the tests)
-  if (g_tune.rag && nx >= 2 * VW) {
-    if ((nx + VW - 1) / VW >= kWave)
-      return launch_fused_ry<T, VW, 64, true>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-    return launch_fused_ry<T, VW, 16, true>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-  }
-  if (nx >= kWave)
-    return launch_fused_ry<T, 1, 64>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
-  return launch_fused_ry<T, 1, 16>(xbar_in, xbar_out, x, bt, p_in, p_out, G, S, st);
+  // (rows at a pitch: only the strides change -- the kernel indexes rows and planes
+  // by G.sy / G.sz and a gradient field's components by G.n)
+  PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
+                    make_geom_pitched<T>(ndim, nz, ny, nx, pitch, wx, wy, wz),
+                    pd_make_scalars<T>(sigma, hden, tau, tl, theta, flags, p_in != nullptr)};
+  a.tune = tune;
+  a.st = as_stream(stream);
+  return pd_launch<FusedKernel>(a);
 }
 
 template <typename T>
@@ -269,74 +205,6 @@ int primal_step_impl(const T *p, T *x, T *xbar, const T *bt, int ndim,
                      as_stream(stream), p, x, xbar, bt, G, (T)tau, (T)tl,
                      prox_den<T>(tl), (T)theta, (flags & NSOL_PD_DATA_L1) != 0);
   return launch_status();
-}
-
-inline int fused2_call(const float *a, float *b, const float *c, float *d,
-                       const float *e, const float *f, float *g, int ndim,
-                       int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
-                       double wz, const double *s, const double *h,
-                       const double *t, const double *tl, const double *th,
-                       int flags, void *st) {
-  return nsol_pd_fused2_iter_f32(a, b, c, d, e, f, g, ndim, nz, ny, nx, wx, wy, wz,
-                                 s, h, t, tl, th, flags, st);
-}
-inline int fused2_call(const double *a, double *b, const double *c, double *d,
-                       const double *e, const double *f, double *g, int ndim,
-                       int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
-                       double wz, const double *s, const double *h,
-                       const double *t, const double *tl, const double *th,
-                       int flags, void *st) {
-  return nsol_pd_fused2_iter_f64(a, b, c, d, e, f, g, ndim, nz, ny, nx, wx, wy, wz,
-                                 s, h, t, tl, th, flags, st);
-}
-
-inline int fusedk_call(const float *a, float *b, const float *c, float *d,
-                       const float *e, const float *f, float *g, int ndim,
-                       int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
-                       double wz, int k, const double *s, const double *h,
-                       const double *t, const double *tl, const double *th,
-                       int flags, void *st) {
-  return nsol_pd_fusedk_iter_f32(a, b, c, d, e, f, g, ndim, nz, ny, nx, wx, wy, wz,
-                                 k, s, h, t, tl, th, flags, st);
-}
-inline int fusedk_call(const double *a, double *b, const double *c, double *d,
-                       const double *e, const double *f, double *g, int ndim,
-                       int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
-                       double wz, int k, const double *s, const double *h,
-                       const double *t, const double *tl, const double *th,
-                       int flags, void *st) {
-  return nsol_pd_fusedk_iter_f64(a, b, c, d, e, f, g, ndim, nz, ny, nx, wx, wy, wz,
-                                 k, s, h, t, tl, th, flags, st);
-}
-
-extern "C" int nsol_pd_fusedk_tail2(int elem_size, int64_t nz, int64_t ny, int64_t nx);
-
-extern "C" int nsol_pd_fusedk_tail2_pitched(int elem_size, int64_t nz, int64_t ny, int64_t nx,
-                                            int64_t pitch);
-extern "C" int nsol_pd_fusedk_iter_pitched_f32(
-    const float *, float *, const float *, float *, const float *, const float *, float *, int,
-    int64_t, int64_t, int64_t, int64_t, double, double, double, int, const double *,
-    const double *, const double *, const double *, const double *, int, void *);
-extern "C" int nsol_pd_fusedk_iter_pitched_f64(
-    const double *, double *, const double *, double *, const double *, const double *,
-    double *, int, int64_t, int64_t, int64_t, int64_t, double, double, double, int,
-    const double *, const double *, const double *, const double *, const double *, int,
-    void *);
-inline int fusedk_pitched(const float *a, float *b, const float *c, float *d, const float *e,
-                          const float *f, float *g, int ndim, int64_t nz, int64_t ny,
-                          int64_t nx, int64_t pitch, double wx, double wy, double wz, int k,
-                          const double *s, const double *h, const double *t, const double *tl,
-                          const double *th, int flags, void *st) {
-  return nsol_pd_fusedk_iter_pitched_f32(a, b, c, d, e, f, g, ndim, nz, ny, nx, pitch, wx, wy,
-                                         wz, k, s, h, t, tl, th, flags, st);
-}
-inline int fusedk_pitched(const double *a, double *b, const double *c, double *d,
-                          const double *e, const double *f, double *g, int ndim, int64_t nz,
-                          int64_t ny, int64_t nx, int64_t pitch, double wx, double wy,
-                          double wz, int k, const double *s, const double *h, const double *t,
-                          const double *tl, const double *th, int flags, void *st) {
-  return nsol_pd_fusedk_iter_pitched_f64(a, b, c, d, e, f, g, ndim, nz, ny, nx, pitch, wx, wy,
-                                         wz, k, s, h, t, tl, th, flags, st);
 }
 
 // pitch > nx: every array holds its rows at that pitch (elements; whole 16-byte vectors),
@@ -368,7 +236,6 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
   int n = 0;
   while (n < iterations) {
     const T *pin = (n == 0 && p_is_zero) ? nullptr : pp[slot];
-    int rc = -2;
     if (!iso && xoth && n + 1 < iterations && !g_tune.force_two_pass) {
       // deepest temporal blocking first: 3 iterations per pass (tiled
       // footprints), then 2 (tiled or full-row footprints), then 1
@@ -378,54 +245,40 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
         h3[i] = huber ? 1.0 + sig[n + i] * gamma_huber : 1.0;
         tl3[i] = tau[n + i] * lambda;
       }
+      auto fusedk = [&](int depth) {
+        return pd_fusedk_iter<T>(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
+                                 ndim, nz, ny, nx, wx, wy, wz, depth, sig + n, h3, tau + n,
+                                 tl3, theta + n, flags, stream, pitched ? pitch : 0);
+      };
+      auto fused2 = [&](int) {
+        return pd_fused2_iter<T>(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
+                                 ndim, nz, ny, nx, wx, wy, wz, sig + n, h3, tau + n, tl3,
+                                 theta + n, flags, stream);
+      };
+      // one rung: nothing once an earlier one has run; 0 -> `depth` iterations are
+      // done; -2 -> the kernel declined, the next rung is tried; else the error
       int done = 0;
+      auto attempt = [&](int depth, auto call) {
+        if (done) return 0;
+        const int rc = call(depth);
+        if (rc == 0) done = depth;
+        return rc == -2 ? 0 : rc;
+      };
+      int err = 0;
       if (pitched) {
         // rows at a pitch: depth 3, then depth 2 of k_pd_fusedk (k_pd_fused2 wants
         // contiguous whole rows), then one iteration at a time
-        for (int depth = left >= 3 ? 3 : 2; depth >= 2 && !done; --depth) {
-          rc = fusedk_pitched(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
-                              ndim, nz, ny, nx, pitch, wx, wy, wz, depth, sig + n, h3,
-                              tau + n, tl3, theta + n, flags, stream);
-          if (rc == 0) done = depth;
-          else if (rc != -2) return rc;
-        }
-        if (done) {
-          n += done;
-          slot ^= 1;
-          T *t = xcur; xcur = xoth; xoth = t;
-          continue;
-        }
-        rc = -2;
-      }
-      if (!pitched && left == 2 && nsol_pd_fusedk_tail2((int)sizeof(T), nz, ny, nx)) {
+        if (left >= 3) err = attempt(3, fusedk);
+        if (!err) err = attempt(2, fusedk);
+      } else {
         // trailing pair of a run on a shape whose depth-3 plan has settled
-        rc = fusedk_call(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
-                         ndim, nz, ny, nx, wx, wy, wz, 2, sig + n, h3, tau + n, tl3,
-                         theta + n, flags, stream);
-        if (rc == 0) done = 2;
-        else if (rc != -2) return rc;
+        if (left == 2 && nsol_pd_fusedk_tail2((int)sizeof(T), nz, ny, nx))
+          err = attempt(2, fusedk);
+        if (!err && left >= 3) err = attempt(3, fusedk);
+        if (!err) err = attempt(2, fused2);
+        if (!err) err = attempt(2, fusedk);   // e.g. rows too short for the full-row footprints
       }
-      if (!pitched && !done && left >= 3) {
-        rc = fusedk_call(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
-                         ndim, nz, ny, nx, wx, wy, wz, 3, sig + n, h3, tau + n, tl3,
-                         theta + n, flags, stream);
-        if (rc == 0) done = 3;
-        else if (rc != -2) return rc;
-      }
-      if (!pitched && !done) {
-        rc = fused2_call(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
-                         ndim, nz, ny, nx, wx, wy, wz, sig + n, h3, tau + n, tl3,
-                         theta + n, flags, stream);
-        if (rc == 0) done = 2;
-        else if (rc != -2) return rc;
-      }
-      if (!pitched && !done) {   // e.g. rows too short for the full-row footprints
-        rc = fusedk_call(xb[slot], xb[slot ^ 1], xcur, xoth, bt, pin, pp[slot ^ 1],
-                         ndim, nz, ny, nx, wx, wy, wz, 2, sig + n, h3, tau + n, tl3,
-                         theta + n, flags, stream);
-        if (rc == 0) done = 2;
-        else if (rc != -2) return rc;
-      }
+      if (err) return err;
       if (done) {
         n += done;
         slot ^= 1;
@@ -434,6 +287,7 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
       }
     }
     const double hden = huber ? 1.0 + sig[n] * gamma_huber : 1.0;
+    int rc;
     if (g_tune.force_two_pass && !pitched) {
       rc = iso ? pd_iso_dual_step<T>(xb[slot], pin, pp[slot ^ 1], ndim, nz, ny, nx, wx,
                                      wy, wz, sig[n], hden, stream)

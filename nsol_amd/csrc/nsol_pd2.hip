@@ -27,6 +27,7 @@
 
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
+#include "nsol_pd_launch.hpp"
 
 using namespace nsol;
 
@@ -382,19 +383,6 @@ struct Tuning {
                      // 1 = two rows per lane, (WX x 4) waves [203 VGPRs, 0.98 ms]
 };
 
-inline int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 // z-chunk length: trade the one-plane overlap per chunk end against filling
 // the last round of workgroups (one footprint-sized workgroup per CU).
 inline int64_t pick_zchunk(int64_t nz, int64_t tiles, int blocks_per_cu) {
@@ -414,11 +402,6 @@ inline int64_t pick_zchunk(int64_t nz, int64_t tiles, int blocks_per_cu) {
   return best_chunk;
 }
 Tuning g_tune2;
-
-template <typename T>
-inline bool al16(const T *a) {
-  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
-}
 
 template <typename T, int VEC, int WX, int WY, int RY, int WPE, bool HUBER, bool L1>
 int launch2_f(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
@@ -459,13 +442,18 @@ int launch2(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
 #undef NSOL_F
 }
 
+}  // namespace nsol_pd2
+
+namespace nsol {
+
 // returns -2 if the two-iteration kernel does not apply to this problem
 template <typename T>
-int fused2_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out,
-                const T *bt, const T *p_in, T *p_out, int ndim, int64_t nz,
-                int64_t ny, int64_t nx, double wx, double wy, double wz,
-                const double *sigma, const double *hden, const double *tau,
-                const double *tl, const double *theta, int flags, void *stream) {
+int pd_fused2_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
+                   const T *p_in, T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                   double wx, double wy, double wz, const double *sigma,
+                   const double *hden, const double *tau, const double *tl,
+                   const double *theta, int flags, void *stream) {
+  using nsol_pd2::g_tune2;
   // the isotropic projection needs a neighbour's whole dual vector: only
   // k_pd_fused_iso (nsol_pdi.hip) has that form
   if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
@@ -475,23 +463,18 @@ int fused2_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out,
     return NSOL_EINVAL;
   constexpr int VW = 16 / sizeof(T);
   if (!g_tune2.enable || ndim != 3 || nx % VW != 0 || nx / VW < 64 || ny < 8 ||
-      nz < 8 || !al16(xbar_in) || !al16(xbar_out) || !al16(x_in) ||
-      !al16(x_out) || !al16(bt) || !al16(p_out) || (p_in && !al16(p_in)) ||
+      nz < 8 || !aligned16(xbar_in) || !aligned16(xbar_out) || !aligned16(x_in) ||
+      !aligned16(x_out) || !aligned16(bt) || !aligned16(p_out) || (p_in && !aligned16(p_in)) ||
       (nz * ny * nx) % VW != 0)
     return -2;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
   PdScalars<T> S[2];
-  for (int i = 0; i < 2; ++i) {
-    S[i].sigma = (T)sigma[i]; S[i].hden = huber_den<T>(hden[i]); S[i].tau = (T)tau[i];
-    S[i].tl = (T)tl[i]; S[i].one_plus_tl = prox_den<T>(tl[i]);
-    S[i].theta = (T)theta[i];
-    S[i].huber = (flags & NSOL_PD_REG_HUBER) ? 1 : 0;
-    S[i].l1 = (flags & NSOL_PD_DATA_L1) ? 1 : 0;
-    S[i].has_p = (i == 1 || p_in != nullptr) ? 1 : 0;
-  }
+  for (int i = 0; i < 2; ++i)
+    S[i] = pd_make_scalars<T>(sigma[i], hden[i], tau[i], tl[i], theta[i], flags,
+                              i == 1 || p_in != nullptr);
   hipStream_t st = as_stream(stream);
 #define NSOL_L2(WX, WY, RY, WPE)                                                \
-  launch2<T, VW, WX, WY, RY, WPE>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out,  \
+  nsol_pd2::launch2<T, VW, WX, WY, RY, WPE>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out,  \
                                   G, S[0], S[1], st)
   const bool wide = nx / VW > 64;
   switch (g_tune2.variant) {
@@ -501,7 +484,17 @@ int fused2_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out,
 #undef NSOL_L2
 }
 
-}  // namespace nsol_pd2
+#define NSOL_PD2_INST(T)                                                             \
+  template int pd_fused2_iter<T>(const T *, T *, const T *, T *, const T *, const T *, \
+                                 T *, int, int64_t, int64_t, int64_t, double, double,  \
+                                 double, const double *, const double *,               \
+                                 const double *, const double *, const double *, int,  \
+                                 void *);
+NSOL_PD2_INST(float)
+NSOL_PD2_INST(double)
+#undef NSOL_PD2_INST
+
+}  // namespace nsol
 
 extern "C" {
 
@@ -515,28 +508,20 @@ int nsol_hip_set_param_pd2(const char *name, int value) {
   return 0;
 }
 
-int nsol_pd_fused2_iter_f32(const float *xbar_in, float *xbar_out,
-                            const float *x_in, float *x_out, const float *bt,
-                            const float *p_in, float *p_out, int ndim,
-                            int64_t nz, int64_t ny, int64_t nx, double wx,
-                            double wy, double wz, const double *sigma2,
-                            const double *hden2, const double *tau2,
-                            const double *tl2, const double *theta2, int flags,
-                            void *stream) {
-  return nsol_pd2::fused2_impl<float>(xbar_in, xbar_out, x_in, x_out, bt, p_in,
-                                      p_out, ndim, nz, ny, nx, wx, wy, wz, sigma2,
-                                      hden2, tau2, tl2, theta2, flags, stream);
-}
-int nsol_pd_fused2_iter_f64(const double *xbar_in, double *xbar_out,
-                            const double *x_in, double *x_out, const double *bt,
-                            const double *p_in, double *p_out, int ndim,
-                            int64_t nz, int64_t ny, int64_t nx, double wx,
-                            double wy, double wz, const double *sigma2,
-                            const double *hden2, const double *tau2,
-                            const double *tl2, const double *theta2, int flags,
-                            void *stream) {
-  return nsol_pd2::fused2_impl<double>(xbar_in, xbar_out, x_in, x_out, bt, p_in,
-                                       p_out, ndim, nz, ny, nx, wx, wy, wz, sigma2,
-                                       hden2, tau2, tl2, theta2, flags, stream);
-}
-}
+#define NSOL_PD2_DEF(T, SUF)                                                          \
+  int nsol_pd_fused2_iter_##SUF(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, \
+                                const T *bt, const T *p_in, T *p_out, int ndim,        \
+                                int64_t nz, int64_t ny, int64_t nx, double wx,         \
+                                double wy, double wz, const double *sigma2,            \
+                                const double *hden2, const double *tau2,               \
+                                const double *tl2, const double *theta2, int flags,    \
+                                void *stream) {                                        \
+    return pd_fused2_iter<T>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, ndim,    \
+                             nz, ny, nx, wx, wy, wz, sigma2, hden2, tau2, tl2, theta2, \
+                             flags, stream);                                           \
+  }
+NSOL_PD2_DEF(float, f32)
+NSOL_PD2_DEF(double, f64)
+#undef NSOL_PD2_DEF
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// Helpers shared by the single-pass primal-dual kernels (nsol_pd.hip,
-// nsol_pd2.hip).
+// Device helpers, the scalars' struct and the entries that the primal-dual units
+// (nsol_pd*.hip) call in each other.  The host-side launch path of the
+// one-iteration kernels is nsol_pd_launch.hpp.
 #pragma once
 
 #include "nsol_common.hpp"
@@ -119,14 +120,15 @@ __device__ __forceinline__ T adj_term(T p, T p_prev, T w) {
   return UNIT ? p_prev - p : p * (-w) + p_prev * w;
 }
 
-// The knobs of nsol_pd.hip that shape a one-iteration launch, handed to the
-// isotropic launcher of nsol_pdi.hip (which nsol_pd_fused_iter_* / nsol_pd_run_*
-// call when NSOL_PD_REG_ISOTROPIC is set).
+// The knobs of nsol_pd.hip that shape a one-iteration launch (nsol_pd_launch.hpp),
+// handed on to the isotropic launcher of nsol_pdi.hip.
 struct PdLaunchTune {
   int zchunk, ry, xcd_map, rag;
 };
-// one iteration through k_pd_fused_iso / the isotropic dual step of the two-pass
-// form (nsol_pdi.hip); arguments as fused_iter_impl / dual_step_impl
+// What nsol_pd.hip's entries call in the other units; each is instantiated for
+// float and double where it is defined.
+// One iteration through k_pd_fused_iso / the isotropic dual step of the two-pass
+// form (nsol_pdi.hip); arguments as nsol_pd_fused_iter_* / nsol_pd_dual_step_*.
 template <typename T>
 int pd_iso_fused_iter(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p_in,
                       T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,
@@ -137,6 +139,21 @@ template <typename T>
 int pd_iso_dual_step(const T *xbar, const T *p_in, T *p_out, int ndim, int64_t nz,
                      int64_t ny, int64_t nx, double wx, double wy, double wz,
                      double sigma, double hden, void *stream);
+// Two iterations through k_pd_fused2 (nsol_pd2.hip), k = 2 or 3 through k_pd_fusedk
+// (nsol_pdk.hip; pitch > nx: rows at that pitch); arguments as nsol_pd_fused2_iter_* /
+// nsol_pd_fusedk_iter_pitched_*.  -2: the kernel does not apply, nothing was launched.
+template <typename T>
+int pd_fused2_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
+                   const T *p_in, T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                   double wx, double wy, double wz, const double *sigma,
+                   const double *hden, const double *tau, const double *tl,
+                   const double *theta, int flags, void *stream);
+template <typename T>
+int pd_fusedk_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
+                   const T *p_in, T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                   double wx, double wy, double wz, int k, const double *sigma,
+                   const double *hden, const double *tau, const double *tl,
+                   const double *theta, int flags, void *stream, int64_t pitch);
 
 template <bool L1, typename T>
 __device__ __forceinline__ T prox_data_s(T u, T bt, T tl, T one_plus_tl) {

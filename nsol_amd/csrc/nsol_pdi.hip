@@ -17,6 +17,7 @@
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
 #include "nsol_pd_iso_body.hpp"
+#include "nsol_pd_launch.hpp"
 
 using namespace nsol;
 
@@ -102,73 +103,38 @@ __global__ __launch_bounds__(kBlock) void k_pd_fused_iso(
                                                S, tx, ty, zc, zchunk);
 }
 
-template <typename T>
-struct IsoArgs {
-  const T *xbar_in; T *xbar_out; T *x; const T *bt; const T *p_in; T *p_out;
-  Geom<T> G; PdScalars<T> S; PdLaunchTune tune; hipStream_t st;
+struct IsoKernel {
+  template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+  static int launch_t(const PdLaunchArgs<T> &a) {
+    const PdGridPlan g = pd_plan_grid<VEC, LX, RY>(a.G, 1, a.tune);
+    if (g.blocks > kPdMaxBlocks) return NSOL_EINVAL;
+    hipLaunchKernelGGL((k_pd_fused_iso<T, VEC, LX, RY, NDIM, RAG>), dim3((unsigned)g.blocks),
+                       dim3(kBlock), 0, a.st, a.xbar_in, a.xbar_out, a.x, a.bt, a.p_in,
+                       a.p_out, a.G, a.S, g.ntx, g.nty, g.zchunk, g.slab);
+    return launch_status();
+  }
+
+  // knob "pd_ry": 1 or 2 rows per lane, any other value = choose
+  template <typename T, int VEC, int LX, bool RAG>
+  static int launch(const PdLaunchArgs<T> &a) {
+    int ry = a.tune.ry;
+    if (ry != 1 && ry != 2) ry = pd_auto_rows_per_lane<VEC, LX>(a.G, 1);
+    switch (a.G.ndim) {
+      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
+      case 2:
+        if (ry == 1) return launch_t<T, VEC, LX, 1, 2, RAG>(a);
+        return launch_t<T, VEC, LX, 2, 2, RAG>(a);
+      default:
+        if (ry == 1) return launch_t<T, VEC, LX, 1, 3, RAG>(a);
+        return launch_t<T, VEC, LX, 2, 3, RAG>(a);
+    }
+  }
 };
-
-// grid shape: the rules of launch_fused_t (nsol_pd.hip)
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
-int launch_iso_t(const IsoArgs<T> &a) {
-  constexpr int LY = kWave / LX;
-  constexpr int TY = (kBlock / kWave) * LY * RY;
-  constexpr int TX = LX * VEC;
-  const Geom<T> &G = a.G;
-  const int64_t ntx = (G.nx + TX - 1) / TX;
-  const int64_t nty = (G.ny + TY - 1) / TY;
-  int64_t zchunk = a.tune.zchunk;
-  if (zchunk <= 0) {
-    const int64_t want = (4096 + ntx * nty - 1) / (ntx * nty);
-    zchunk = (G.nz + want - 1) / want;
-    if (zchunk < 2) zchunk = 2;
-  }
-  if (zchunk > G.nz) zchunk = G.nz;
-  const int64_t nzc = (G.nz + zchunk - 1) / zchunk;
-  int64_t slab = 0;
-  int64_t blocks = ntx * nty * nzc;
-  if (a.tune.xcd_map && nty >= 16) {
-    slab = (nty + 7) / 8;
-    blocks = 8 * slab * ntx * nzc;
-  }
-  if (blocks > 0x7fffffff) return NSOL_EINVAL;
-  hipLaunchKernelGGL((k_pd_fused_iso<T, VEC, LX, RY, NDIM, RAG>), dim3((unsigned)blocks),
-                     dim3(kBlock), 0, a.st, a.xbar_in, a.xbar_out, a.x, a.bt, a.p_in,
-                     a.p_out, G, a.S, (int)ntx, (int)nty, (int)zchunk, (int)slab);
-  return launch_status();
-}
-
-template <typename T, int VEC, int LX, bool RAG>
-int launch_iso(const IsoArgs<T> &a) {
-  const Geom<T> &G = a.G;
-  int ry = a.tune.ry;
-  if (ry != 1 && ry != 2) {
-    // two rows per lane unless that leaves fewer than ~2 workgroups per CU
-    constexpr int TY2 = (kBlock / kWave) * (kWave / LX) * 2;
-    const int64_t tiles = ((G.nx + LX * VEC - 1) / (LX * VEC)) * ((G.ny + TY2 - 1) / TY2);
-    ry = (tiles * ((G.nz + 1) / 2) < 512) ? 1 : 2;
-  }
-  switch (G.ndim) {
-    case 1: return launch_iso_t<T, VEC, LX, 1, 1, RAG>(a);
-    case 2:
-      if (ry == 1) return launch_iso_t<T, VEC, LX, 1, 2, RAG>(a);
-      return launch_iso_t<T, VEC, LX, 2, 2, RAG>(a);
-    default:
-      if (ry == 1) return launch_iso_t<T, VEC, LX, 1, 3, RAG>(a);
-      return launch_iso_t<T, VEC, LX, 2, 3, RAG>(a);
-  }
-}
-
-template <typename T>
-inline bool aligned16(const T *a) {
-  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
-}
 
 }  // namespace
 
 namespace nsol {
 
-// the dispatch of fused_iter_impl (nsol_pd.hip), kernel by kernel
 template <typename T>
 int pd_iso_fused_iter(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p_in,
                       T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,
@@ -179,33 +145,12 @@ int pd_iso_fused_iter(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T 
   if (!xbar_in || !xbar_out || !x || !bt || !p_out || xbar_in == xbar_out ||
       p_in == p_out)
     return NSOL_EINVAL;
-  IsoArgs<T> a;
-  a.xbar_in = xbar_in; a.xbar_out = xbar_out; a.x = x; a.bt = bt;
-  a.p_in = p_in; a.p_out = p_out;
-  a.G = make_geom_pitched<T>(ndim, nz, ny, nx, pitch, wx, wy, wz);
-  PdScalars<T> &S = a.S;
-  S.sigma = (T)sigma; S.hden = huber_den<T>(hden); S.tau = (T)tau; S.tl = (T)tl;
-  S.one_plus_tl = prox_den<T>(tl); S.theta = (T)theta;
-  S.huber = (flags & NSOL_PD_REG_HUBER) ? 1 : 0;
-  S.l1 = (flags & NSOL_PD_DATA_L1) ? 1 : 0;
-  S.has_p = p_in ? 1 : 0;
+  PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
+                    make_geom_pitched<T>(ndim, nz, ny, nx, pitch, wx, wy, wz),
+                    pd_make_scalars<T>(sigma, hden, tau, tl, theta, flags, p_in != nullptr)};
   a.tune = tune;
   a.st = as_stream(stream);
-  constexpr int VW = 16 / sizeof(T);  // elements per 16-byte access
-  const bool vec_ok = (nx % VW == 0) && aligned16(xbar_in) && aligned16(xbar_out) &&
-                      aligned16(x) && aligned16(bt) && aligned16(p_out) &&
-                      (!p_in || aligned16(p_in)) && ((nz * ny * nx) % VW == 0);
-  if (a.G.padded && !(tune.rag && nx >= 2 * VW) && !vec_ok) return NSOL_EINVAL;
-  if (vec_ok) {
-    if (nx / VW >= kWave) return launch_iso<T, VW, 64, false>(a);
-    return launch_iso<T, VW, 16, false>(a);
-  }
-  if (tune.rag && nx >= 2 * VW) {
-    if ((nx + VW - 1) / VW >= kWave) return launch_iso<T, VW, 64, true>(a);
-    return launch_iso<T, VW, 16, true>(a);
-  }
-  if (nx >= kWave) return launch_iso<T, 1, 64, false>(a);
-  return launch_iso<T, 1, 16, false>(a);
+  return pd_launch<IsoKernel>(a);
 }
 
 template <typename T>

@@ -915,19 +915,6 @@ struct Tuning {
 };
 Tuning g_tunek;
 
-inline int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 int g_split = -1;   // -1 / 1: split lane mapping where it applies; 0: never (experiment)
 
 struct Config {
@@ -1013,11 +1000,6 @@ inline double model_cost(const Tiling &q, int64_t nx, int64_t ny, int64_t nz,
   const double reads = lines * 128.0 * rows * (double)nz * 6.0;
   const double writes = 5.0 * (double)nx * ny * nz * esize;
   return (reads + writes) / zeff;
-}
-
-template <typename T>
-inline bool al16(const T *a) {
-  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
 }
 
 template <typename T, int VEC, int NW, int K, int WPE, bool HUBER, bool L1, bool PF2,
@@ -1408,14 +1390,18 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
 #undef NSOL_GO
 }
 
+}  // namespace nsol_pdk
+
+namespace nsol {
+
 // returns -2 if the kernel does not apply to this problem
 template <typename T>
-int fusedk_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
-                const T *p_in, T *p_out, int ndim, int64_t nz, int64_t ny,
-                int64_t nx, double wx, double wy, double wz, int k,
-                const double *sigma, const double *hden, const double *tau,
-                const double *tl, const double *theta, int flags, void *stream,
-                int64_t pitch = 0) {
+int pd_fusedk_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
+                   const T *p_in, T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                   double wx, double wy, double wz, int k, const double *sigma,
+                   const double *hden, const double *tau, const double *tl,
+                   const double *theta, int flags, void *stream, int64_t pitch) {
+  using nsol_pdk::g_tunek;
   // the footprint overlap is sized for the component-wise clamp: the isotropic
   // projection (nsol_pdi.hip) has no multi-iteration form
   if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
@@ -1432,20 +1418,31 @@ int fusedk_impl(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T 
   if (!g_tunek.enable || k > g_tunek.kmax || ndim != 3 ||
       nz * ny * nx < ((int64_t)g_tunek.min_kvox << 10) ||
       nx / VW < 8 || ny < 8 || nz < 8 || nz >= ((int64_t)1 << 30) ||
-      (!rag && (!al16(xbar_in) || !al16(xbar_out) || !al16(x_in) || !al16(x_out) ||
-                !al16(bt) || !al16(p_out) || (p_in && !al16(p_in)) ||
+      (!rag && (!aligned16(xbar_in) || !aligned16(xbar_out) || !aligned16(x_in) ||
+                !aligned16(x_out) || !aligned16(bt) || !aligned16(p_out) ||
+                (p_in && !aligned16(p_in)) ||
                 (nz * ny * nx) % VW != 0)))
     return -2;
   const Geom<T> G = make_geom_pitched<T>(ndim, nz, ny, nx, pitch, wx, wy, wz);
   hipStream_t st = as_stream(stream);
   if (k == 2)
-    return fusedk_k<T, 2>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, sigma,
+    return nsol_pdk::fusedk_k<T, 2>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, sigma,
                           hden, tau, tl, theta, flags, st);
-  return fusedk_k<T, 3>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, sigma,
+  return nsol_pdk::fusedk_k<T, 3>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, sigma,
                         hden, tau, tl, theta, flags, st);
 }
 
-}  // namespace nsol_pdk
+#define NSOL_PDK_INST(T)                                                             \
+  template int pd_fusedk_iter<T>(const T *, T *, const T *, T *, const T *, const T *, \
+                                 T *, int, int64_t, int64_t, int64_t, double, double,  \
+                                 double, int, const double *, const double *,          \
+                                 const double *, const double *, const double *, int,  \
+                                 void *, int64_t);
+NSOL_PDK_INST(float)
+NSOL_PDK_INST(double)
+#undef NSOL_PDK_INST
+
+}  // namespace nsol
 
 extern "C" {
 
@@ -1523,41 +1520,28 @@ int nsol_pd_fusedk_plan(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx
   return 0;
 }
 
-#define NSOL_PDK_PITCHED(T, SUF)                                                       \
+#define NSOL_PDK_DEF(T, SUF)                                                           \
   int nsol_pd_fusedk_iter_pitched_##SUF(                                               \
       const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt, const T *p_in, \
       T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx, int64_t pitch, double wx, \
       double wy, double wz, int k, const double *sigma, const double *hden,            \
       const double *tau, const double *tl, const double *theta, int flags,             \
       void *stream) {                                                                  \
-    return nsol_pdk::fusedk_impl<T>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out,   \
-                                    ndim, nz, ny, nx, wx, wy, wz, k, sigma, hden, tau, \
-                                    tl, theta, flags, stream, pitch);                  \
+    return pd_fusedk_iter<T>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, ndim,    \
+                             nz, ny, nx, wx, wy, wz, k, sigma, hden, tau, tl, theta,   \
+                             flags, stream, pitch);                                    \
+  }                                                                                    \
+  int nsol_pd_fusedk_iter_##SUF(                                                       \
+      const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt, const T *p_in, \
+      T *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,    \
+      double wz, int k, const double *sigma, const double *hden, const double *tau,    \
+      const double *tl, const double *theta, int flags, void *stream) {                \
+    return pd_fusedk_iter<T>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, ndim,    \
+                             nz, ny, nx, wx, wy, wz, k, sigma, hden, tau, tl, theta,   \
+                             flags, stream, 0);                                        \
   }
-NSOL_PDK_PITCHED(float, f32)
-NSOL_PDK_PITCHED(double, f64)
-#undef NSOL_PDK_PITCHED
+NSOL_PDK_DEF(float, f32)
+NSOL_PDK_DEF(double, f64)
+#undef NSOL_PDK_DEF
 
-int nsol_pd_fusedk_iter_f32(const float *xbar_in, float *xbar_out, const float *x_in,
-                            float *x_out, const float *bt, const float *p_in,
-                            float *p_out, int ndim, int64_t nz, int64_t ny,
-                            int64_t nx, double wx, double wy, double wz, int k,
-                            const double *sigma, const double *hden,
-                            const double *tau, const double *tl,
-                            const double *theta, int flags, void *stream) {
-  return nsol_pdk::fusedk_impl<float>(xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out,
-                                      ndim, nz, ny, nx, wx, wy, wz, k, sigma, hden,
-                                      tau, tl, theta, flags, stream);
-}
-int nsol_pd_fusedk_iter_f64(const double *xbar_in, double *xbar_out,
-                            const double *x_in, double *x_out, const double *bt,
-                            const double *p_in, double *p_out, int ndim, int64_t nz,
-                            int64_t ny, int64_t nx, double wx, double wy, double wz,
-                            int k, const double *sigma, const double *hden,
-                            const double *tau, const double *tl,
-                            const double *theta, int flags, void *stream) {
-  return nsol_pdk::fusedk_impl<double>(xbar_in, xbar_out, x_in, x_out, bt, p_in,
-                                       p_out, ndim, nz, ny, nx, wx, wy, wz, k, sigma,
-                                       hden, tau, tl, theta, flags, stream);
-}
-}
+}  // extern "C"

@@ -387,7 +387,7 @@ __global__ __launch_bounds__(MAXT) void k_pd_persist(
 
 // Step sizes of up to kSetupChunk iterations travel as kernel arguments (no host
 // -> device copy to wait for) and are turned into the per-iteration scalars on the
-// device with the arithmetic of make_scalars() (IEEE double, no contraction: the
+// device with the arithmetic of pd_make_scalars() (IEEE double, no contraction: the
 // same bits as on the host); the first chunk also clears the tiles' flags.
 constexpr int kSetupChunk = 128;
 struct SetupArgs {
@@ -416,26 +416,13 @@ __global__ __launch_bounds__(kBlock) void k_pdp_setup(SetupArgs A, int first, in
     for (int j = i; j < nflags; j += kBlock) flags[j] = 0u;
 }
 
-inline int cu_count_pdp() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 // lanes per tile: powers of two with 64..1024 lanes that cover the volume in at
 // most one tile per CU; among those the most tiles (the shortest latency chain per
 // iteration), then the fewest lanes
 template <int VEC>
 bool pick_tiling(int ndim, int64_t nz, int64_t ny, int64_t nx, Tiling *out) {
   const int64_t nxv = nx / VEC;
-  const int max_tiles = cu_count_pdp() < kMaxTiles ? cu_count_pdp() : kMaxTiles;
+  const int max_tiles = cu_count() < kMaxTiles ? cu_count() : kMaxTiles;
   int64_t best_tiles = -1, best_lanes = 0;
   for (int lx = 1; lx <= 256; lx *= 2)
     for (int ly = 1; ly <= (ndim >= 2 ? 256 : 1); ly *= 2)
@@ -535,7 +522,7 @@ int persist_run(const T *xbar, const T *x, const T *bt, const T *p, T *xbar_out,
     int per_cu = 0;                                                                  \
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(                               \
             &per_cu, k_pd_persist<T, VEC, ND, MT>, nthr, lds) != hipSuccess ||       \
-        (int64_t)per_cu * cu_count_pdp() < (int64_t)grid.x)                          \
+        (int64_t)per_cu * cu_count() < (int64_t)grid.x)                          \
       return -2;                                                                     \
     hipLaunchKernelGGL((k_pd_persist<T, VEC, ND, MT>), grid, dim3(nthr), lds, st, xbar, x, \
                        bt, p, xbar_out, x_out, p_out, G, scd, iterations, huber ? 1 : 0, \

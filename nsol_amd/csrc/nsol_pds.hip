@@ -12,6 +12,7 @@
 // offsets the base pointers (x[m n + i], p[m dim n + c n + i]; bt is shared) and
 // selects the row PdScalars[iteration][member] of a device table that
 // nsol_pd_sweep_run_* fills once per run.
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -20,6 +21,7 @@
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
 #include "nsol_pd_fused_body.hpp"
+#include "nsol_pd_launch.hpp"
 
 using namespace nsol;
 
@@ -45,74 +47,37 @@ __global__ __launch_bounds__(kBlock) void k_pd_sweep(
                                            zchunk);
 }
 
-template <typename T>
-struct SweepArgs {
-  const T *xbar_in;
-  T *xbar_out, *x;
-  const T *bt, *p_in;
-  T *p_out;
-  Geom<T> G;
-  const PdScalars<T> *row;
-  int members;
-  hipStream_t st;
+// The members count as tiles in the launch geometry -- 64 members of a 256 x 256
+// image fill the chip where one does not, so the stack takes two rows per lane and
+// whole z runs sooner than a single volume would.  Placement never changes a result.
+struct SweepKernel {
+  template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+  static int launch_t(const PdLaunchArgs<T> &a) {
+    const PdGridPlan g = pd_plan_grid<VEC, LX, RY>(a.G, a.members, a.tune);
+    if (g.blocks > kPdMaxBlocks) return -2;   // (the caller runs the members one by one)
+    hipLaunchKernelGGL((k_pd_sweep<T, VEC, LX, RY, NDIM, RAG>),
+                       dim3((unsigned)g.blocks, (unsigned)a.members), dim3(kBlock), 0, a.st,
+                       a.xbar_in, a.xbar_out, a.x, a.bt, a.p_in, a.p_out, a.G, a.row,
+                       g.ntx, g.nty, g.zchunk, g.slab);
+    const int rc = launch_status();
+    if (rc == 0) g_sweep_launches.fetch_add(1, std::memory_order_relaxed);
+    return rc;
+  }
+
+  template <typename T, int VEC, int LX, bool RAG>
+  static int launch(const PdLaunchArgs<T> &a) {
+    const bool two_rows = pd_auto_rows_per_lane<VEC, LX>(a.G, a.members) == 2;
+    switch (a.G.ndim) {
+      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
+      case 2:
+        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
+                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
+      default:
+        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
+                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
+    }
+  }
 };
-
-// Launch geometry: the rules of launch_fused_t / launch_fused_ry (nsol_pd.hip)
-// with the members counted as tiles -- 64 members of a 256 x 256 image fill the
-// chip where one does not, so the stack takes two rows per lane and whole z runs
-// sooner than a single volume would.  Placement never changes a result.
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
-int launch_sweep_t(const SweepArgs<T> &a) {
-  constexpr int LY = kWave / LX;
-  constexpr int TY = (kBlock / kWave) * LY * RY;
-  constexpr int TX = LX * VEC;
-  const Geom<T> &G = a.G;
-  const int64_t ntx = (G.nx + TX - 1) / TX;
-  const int64_t nty = (G.ny + TY - 1) / TY;
-  const int64_t tiles = ntx * nty * a.members;
-  const int64_t want = (4096 + tiles - 1) / tiles;
-  int64_t zchunk = (G.nz + want - 1) / want;
-  if (zchunk < 2) zchunk = 2;
-  if (zchunk > G.nz) zchunk = G.nz;
-  const int64_t nzc = (G.nz + zchunk - 1) / zchunk;
-  int64_t slab = 0;
-  int64_t blocks = ntx * nty * nzc;
-  if (nty >= 16) {
-    slab = (nty + 7) / 8;
-    blocks = 8 * slab * ntx * nzc;
-  }
-  if (blocks > 0x7fffffff) return -2;
-  hipLaunchKernelGGL((k_pd_sweep<T, VEC, LX, RY, NDIM, RAG>),
-                     dim3((unsigned)blocks, (unsigned)a.members), dim3(kBlock), 0, a.st,
-                     a.xbar_in, a.xbar_out, a.x, a.bt, a.p_in, a.p_out, G, a.row,
-                     (int)ntx, (int)nty, (int)zchunk, (int)slab);
-  const int rc = launch_status();
-  if (rc == 0) g_sweep_launches.fetch_add(1, std::memory_order_relaxed);
-  return rc;
-}
-
-template <typename T, int VEC, int LX, bool RAG>
-int launch_sweep(const SweepArgs<T> &a) {
-  const Geom<T> &G = a.G;
-  constexpr int TY2 = (kBlock / kWave) * (kWave / LX) * 2;
-  const int64_t tiles =
-      ((G.nx + LX * VEC - 1) / (LX * VEC)) * ((G.ny + TY2 - 1) / TY2) * a.members;
-  const bool two_rows = tiles * ((G.nz + 1) / 2) >= 512;
-  switch (G.ndim) {
-    case 1: return launch_sweep_t<T, VEC, LX, 1, 1, RAG>(a);
-    case 2:
-      return two_rows ? launch_sweep_t<T, VEC, LX, 2, 2, RAG>(a)
-                      : launch_sweep_t<T, VEC, LX, 1, 2, RAG>(a);
-    default:
-      return two_rows ? launch_sweep_t<T, VEC, LX, 2, 3, RAG>(a)
-                      : launch_sweep_t<T, VEC, LX, 1, 3, RAG>(a);
-  }
-}
-
-template <typename T>
-inline bool aligned16(const T *a) {
-  return (reinterpret_cast<uintptr_t>(a) & 15u) == 0;
-}
 
 // What the stacked kernel takes: a geometry fused_iter_impl (nsol_pd.hip) takes,
 // at least one member, all members together within 2^31 voxels, members within
@@ -133,29 +98,17 @@ int sweep_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p
   if (!xbar_in || !xbar_out || !x || !bt || !p_in || !p_out || !tab || iteration < 0 ||
       xbar_in == xbar_out || p_in == p_out)
     return NSOL_EINVAL;
-  SweepArgs<T> a;
-  a.xbar_in = xbar_in; a.xbar_out = xbar_out; a.x = x; a.bt = bt;
-  a.p_in = p_in; a.p_out = p_out;
-  a.G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
-  a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
-  a.members = members;
-  a.st = as_stream(stream);
-  constexpr int VW = 16 / sizeof(T);  // elements per 16-byte access
   // (every member's slice starts a whole number of vectors behind the base when
   // the volume is whole vectors)
-  const bool vec_ok = (nx % VW == 0) && aligned16(xbar_in) && aligned16(xbar_out) &&
-                      aligned16(x) && aligned16(bt) && aligned16(p_out) &&
-                      aligned16(p_in) && ((nz * ny * nx) % VW == 0);
-  if (vec_ok) {
-    if (nx / VW >= kWave) return launch_sweep<T, VW, 64, false>(a);
-    return launch_sweep<T, VW, 16, false>(a);
-  }
-  if (nx >= 2 * VW) {   // ragged rows: element-aligned 16-byte accesses
-    if ((nx + VW - 1) / VW >= kWave) return launch_sweep<T, VW, 64, true>(a);
-    return launch_sweep<T, VW, 16, true>(a);
-  }
-  if (nx >= kWave) return launch_sweep<T, 1, 64, false>(a);
-  return launch_sweep<T, 1, 16, false>(a);
+  PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
+                    make_geom<T>(ndim, nz, ny, nx, wx, wy, wz)};
+  a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
+  a.members = members;
+  // the pd_* knobs do not reach the stack: automatic z chunks and rows per lane,
+  // the XCD map and the ragged form on
+  a.tune = PdLaunchTune{0, 0, 1, 1};
+  a.st = as_stream(stream);
+  return pd_launch<SweepKernel>(a);
 }
 
 template <typename T>
@@ -173,24 +126,19 @@ int sweep_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int memb
       tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)
     return NSOL_EINVAL;
   const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
-  // the table, [iteration][member], rounded exactly as make_scalars (nsol_pd.hip)
-  // rounds the scalars of a single run
+  // the table, [iteration][member], rounded as a single run's scalars are
   PdScalars<T> *h = static_cast<PdScalars<T> *>(tab_host);
   for (int n = 0; n < iterations; ++n)
     for (int m = 0; m < members; ++m) {
       const int64_t k = (int64_t)m * iterations + n;
       const double tl = tau[k] * lmbda[m];
-      PdScalars<T> &S = h[(int64_t)n * members + m];
-      memset(&S, 0, sizeof(S));
-      S.sigma = (T)sig[k];
-      S.hden = huber_den<T>(huber ? 1.0 + sig[k] * gamma_huber : 1.0);
-      S.tau = (T)tau[k];
-      S.tl = (T)tl;
-      S.one_plus_tl = prox_den<T>(tl);
-      S.theta = (T)theta[k];
-      S.huber = huber ? 1 : 0;
-      S.l1 = (flags & NSOL_PD_DATA_L1) ? 1 : 0;
-      S.has_p = (n == 0 && p_is_zero) ? 0 : 1;
+      const PdScalars<T> S = pd_make_scalars<T>(
+          sig[k], huber ? 1.0 + sig[k] * gamma_huber : 1.0, tau[k], tl, theta[k], flags,
+          !(n == 0 && p_is_zero));
+      // the table is uploaded as bytes: no stale padding behind the last member
+      PdScalars<T> &row = h[(int64_t)n * members + m];
+      memset(&row, 0, sizeof(row));
+      memcpy(&row, &S, offsetof(PdScalars<T>, has_p) + sizeof(S.has_p));
     }
   if (iterations > 0) {
     hipError_t e = hipMemcpyAsync(tab, tab_host,

@@ -211,11 +211,6 @@ inline bool stencil_grid_ok(int64_t nz, int64_t ny, int64_t nx) {
   return ((ny + 3) / 4) * nz * outer < (int64_t)0x7fffffff;
 }
 
-template <typename T>
-inline bool ptr16(const T *p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 // Calls f(integral_constant<VEC>, integral_constant<ROWS>) with the widest
 // legal vector width; all listed pointers must be 16-byte aligned for VEC > 1.
 template <typename T, typename F>
