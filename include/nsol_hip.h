@@ -663,6 +663,63 @@ int nsol_pd_sweep_run_f64(double *xbar0, double *xbar1, double *x, const double 
                           int *final_slot_host, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * Image stack: `members` independent primal-dual runs on `members` DIFFERENT
+ * observations of one shape (the slices of a stack, a batch of images, a set of
+ * small volumes), advanced together -- one launch per iteration for all of them
+ * (nsol_pdb.hip).  Layout and table as for the sweep above, except that bt holds
+ * members * n elements, member-major (bt[m n + i]): every member has its own
+ * scaled observation.  Member m is bit-identical to a single run on that
+ * member's data with that member's scalars.
+ * flags: the sweep's, and NSOL_PD_REG_ISOTROPIC is taken (the isotropic tile
+ * body of nsol_pd_iso_body.hpp on every member's own slice).
+ * nsol_pd_batch_run_*: arguments and table as nsol_pd_sweep_run_* (entries of
+ * nsol_pd_sweep_entry_bytes(elem_size) bytes); nsol_pd_batch_iter_*: one launch,
+ * iteration `iteration` of a table filled earlier, `flags` choosing the kernel.
+ * Both return -2, having launched nothing, for what nsol_pd_sweep_* would decline
+ * for its geometry or member count.
+ * nsol_pd_batch_launches: launches of the stacked kernels this process has made.
+ *
+ * nsol_scale_rows_*: out[m n + i] = in[m n + i] / s[m] (divide = 1) or * s[m]
+ * (divide = 0), s a DEVICE array of `members` doubles, members <= 65535.  Row m
+ * is bit-identical to nsol_scale_* of that row with a = s[m] (the scale is rounded
+ * to the element type first).  nsol_scale_rows_f64_to_f32 reads float64 and writes
+ * float32: the quotient / product is formed in float64 and rounded once (how the
+ * scaled observation is made from float64 data). */
+int nsol_pd_batch_launches(void);
+int nsol_pd_batch_iter_f32(const float *xbar_in, float *xbar_out, float *x,
+                           const float *bt, const float *p_in, float *p_out,
+                           int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                           double wx, double wy, double wz, const void *tab,
+                           int iteration, int flags, void *stream);
+int nsol_pd_batch_iter_f64(const double *xbar_in, double *xbar_out, double *x,
+                           const double *bt, const double *p_in, double *p_out,
+                           int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                           double wx, double wy, double wz, const void *tab,
+                           int iteration, int flags, void *stream);
+int nsol_pd_batch_run_f32(float *xbar0, float *xbar1, float *x, const float *bt,
+                          float *p0, float *p1, int members, int ndim, int64_t nz,
+                          int64_t ny, int64_t nx, double wx, double wy, double wz,
+                          const double *lmbda_host, const double *sigma_host,
+                          const double *tau_host, const double *theta_host,
+                          int iterations, int p_is_zero, double gamma_huber, int flags,
+                          void *tab_host, void *tab, int64_t tab_bytes,
+                          int *final_slot_host, void *stream);
+int nsol_pd_batch_run_f64(double *xbar0, double *xbar1, double *x, const double *bt,
+                          double *p0, double *p1, int members, int ndim, int64_t nz,
+                          int64_t ny, int64_t nx, double wx, double wy, double wz,
+                          const double *lmbda_host, const double *sigma_host,
+                          const double *tau_host, const double *theta_host,
+                          int iterations, int p_is_zero, double gamma_huber, int flags,
+                          void *tab_host, void *tab, int64_t tab_bytes,
+                          int *final_slot_host, void *stream);
+int nsol_scale_rows_f32(float *out, const float *in, const double *s, int divide,
+                        int members, int64_t n, void *stream);
+int nsol_scale_rows_f64(double *out, const double *in, const double *s, int divide,
+                        int members, int64_t n, void *stream);
+int nsol_scale_rows_f64_to_f32(float *out, const double *in, const double *s,
+                               int divide, int members, int64_t n, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

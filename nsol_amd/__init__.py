@@ -10,3 +10,12 @@ from .device import set_default_dtype, get_default_dtype  # noqa: F401
 from ._caches import invalidate_caches  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # nsol_amd.PrimalDualBatch: resolved on first use, so that importing the package
+    # stays as light as it was
+    if name == "PrimalDualBatch":
+        from .solver_batch import PrimalDualBatch
+        return PrimalDualBatch
+    raise AttributeError("module 'nsol_amd' has no attribute '%s'" % name)

@@ -14,6 +14,11 @@ reference's sum over the components (one fused launch per iteration).
 Several values of --alpha are a parameter sweep (nsol_amd/parameter_sweep.py): the
 members run stacked, one launch per iteration for all of them; --result-dir DIR
 keeps every member (<stem>_alpha<value><ext>) next to a sweep.npz.
+
+--slice-wise: a 3-D observation is shape[0] independent 2-D images, each with its
+own x_scale = max(slice), run together through PrimalDualBatch
+(nsol_amd/solver_batch.py) -- one launch per iteration for all slices -- and
+reassembled; a slice without a positive maximum is copied through unchanged.
 """
 import argparse
 import os
@@ -132,6 +137,51 @@ def run_sweep(args, observed_nda, x_ref, reader):
     return 0
 
 
+def classify_slices(observed_nda):
+    """(indices of the slices to solve, indices copied through unchanged): a slice
+    whose maximum is not positive has no x_scale to divide by (wiring())."""
+    solve, copy = [], []
+    for k in range(observed_nda.shape[0]):
+        m = np.max(observed_nda[k])
+        (solve if np.isfinite(m) and m > 0 else copy).append(k)
+    return solve, copy
+
+
+def run_slice_wise(args, observed_nda, x_ref, reader):
+    """--slice-wise: one solver per slice, all through PrimalDualBatch."""
+    from ..solver_batch import PrimalDualBatch
+    solve, copy = classify_slices(observed_nda)
+    solvers = [build_solver(observed_nda[k], args.reconstruction_type,
+                            args.alpha[0], args.iterations, L2=args.L2,
+                            dtype=np.dtype(args.dtype).type,
+                            alg_type=args.alg_type, isotropic=args.isotropic)
+               for k in solve]
+    recon = np.array(observed_nda, dtype=np.float64)
+    execution = []
+    if solvers:
+        batch = PrimalDualBatch(solvers)
+        batch.run()
+        execution = batch.get_execution()
+        for k, solver in zip(solve, solvers):
+            recon[k] = solver.get_x().reshape(*observed_nda.shape[1:])
+        took = batch.get_computational_time()
+    else:
+        import datetime
+        took = datetime.timedelta(seconds=0)
+    print("%s alpha=%g slice-wise: %d iterations in %s (%d slices stacked, "
+          "%d copied through, %d sequential)" % (
+              args.reconstruction_type, args.alpha[0], args.iterations, took,
+              execution.count("stacked"), len(copy),
+              execution.count("sequential")))
+    if x_ref is not None:
+        flat = recon.flatten()
+        for m in args.measures:
+            print("  %s: %.6g" % (
+                m, SimilarityMeasures.similarity_measures[m](flat, x_ref)))
+    dw.DataWriter(recon, args.result, reader.get_image_sitk()).write_data()
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(
         description="Run TVL1/TVL2/HuberL1/HuberL2 denoising on an MI355X")
@@ -164,7 +214,16 @@ def main(argv=None):
                     help="with several --alpha: every member's result as "
                          "<stem>_alpha<value><ext> and the sweep's parameters "
                          "and measures as sweep.npz in DIR")
+    ap.add_argument("--slice-wise", action="store_true",
+                    help="treat a 3-D observation as shape[0] independent 2-D "
+                         "images, each scaled by its own maximum, and run them "
+                         "stacked (one launch per iteration for all slices)")
     args = ap.parse_args(argv)
+    if args.slice_wise and len(args.alpha) > 1:
+        ap.error("--slice-wise takes a single --alpha")
+    if args.slice_wise and args.observe_every is not None:
+        ap.error("--slice-wise does not take --observe-every: the measures are "
+                 "taken once, on the reassembled volume")
 
     if len(args.alpha) == 1 and args.result is None:
         raise IOError("'--result' must be specified")
@@ -177,6 +236,12 @@ def main(argv=None):
         ref_reader = dr.DataReader(args.reference)
         ref_reader.read_data()
         x_ref = ref_reader.get_data().flatten()
+
+    if args.slice_wise:
+        if observed_nda.ndim != 3:
+            ap.error("--slice-wise needs a 3-D observation, not %d-D" %
+                     observed_nda.ndim)
+        return run_slice_wise(args, observed_nda, x_ref, reader)
 
     if len(args.alpha) > 1 and not args.verbose:
         return run_sweep(args, observed_nda, x_ref, reader)

@@ -1464,6 +1464,112 @@ def pd_sweep_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, t
     return int(slot.value)
 
 
+# ----------------------------------------------------------- image stack ----
+# Independent images of one shape (nsol_amd/solver_batch.py) are stacked in one launch
+# per iteration like the members of a sweep, except that every member brings its own
+# scaled observation: a member's state is x, two xbar, two p AND bt, 4 + 2 dim arrays
+# (12 words per voxel in 3-D where a sweep member has 11 + 1/P).  The two constants
+# decide speed only, as the sweep's do; DESIGN.md section 4b has the table they come
+# from (tools/bench_batch.py --explore).
+PD_BATCH_MAX_VOXELS = 1 << 24
+PD_BATCH_GROUP_BYTES = 256 << 20
+
+
+def pd_batch_launches():
+    """Launches of the image-stacked kernels so far (for tests and tools)."""
+    return int(_lib.load().nsol_pd_batch_launches())
+
+
+def batch_group_size(members, n, dim, elem_size):
+    """Members per stacked group of independent images: as many as keep a group's
+    state, the per-member observation included, under PD_BATCH_GROUP_BYTES and within
+    the kernel's 2^31 voxels and 65535 members, at least one."""
+    per_member = (4 + 2 * int(dim)) * int(n) * int(elem_size)
+    g = min(PD_BATCH_GROUP_BYTES // per_member, (1 << 31) // int(n), 65535)
+    return int(max(1, min(int(members), g)))
+
+
+def scale_rows(x, s, members, divide=False, out=None, dtype=None):
+    """Row m of the (members, n) array x divided (divide=True) or multiplied by s[m],
+    one launch: every row the bits ops.scale gives for it alone.  s: a device
+    float64 tensor of `members` scales.  dtype=torch.float32 with a float64 x: the
+    operation in float64, rounded once (scaled_data_on_device's form)."""
+    _chk(x)
+    _chk(s)
+    members = int(members)
+    if s.dtype != torch.float64 or s.numel() != members or members < 1 or \
+            x.numel() % members:
+        raise ValueError("scale_rows needs one float64 scale per row: %d rows, "
+                         "%d scales, %d elements" % (members, s.numel(), x.numel()))
+    if members > 65535:
+        raise ValueError("scale_rows takes at most 65535 rows")
+    n = x.numel() // members
+    to = x.dtype if dtype is None else dtype
+    if out is None:
+        out = torch.empty(x.numel(), dtype=to, device=x.device).view(x.shape)
+    _chk(out)
+    if out.dtype != to or out.numel() != x.numel():
+        raise ValueError("operand mismatch: out is %s[%d]" % (out.dtype, out.numel()))
+    if to == x.dtype:
+        fn, what = _fn("scale_rows", x), "nsol_scale_rows"
+    elif x.dtype == torch.float64 and to == torch.float32:
+        fn, what = _lib.load().nsol_scale_rows_f64_to_f32, "nsol_scale_rows_f64_to_f32"
+    else:
+        raise ValueError("scale_rows converts float64 to float32 only")
+    _lib.check(fn(_p(out), _p(x), _p(s), int(bool(divide)), members, n, stream_ptr()),
+               what)
+    return _wrote(out)
+
+
+def pd_batch_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, tau,
+                 theta, p_is_zero, gamma_huber, flags):
+    """pd_sweep_run for `members` independent images: bt holds members * n elements,
+    member-major, and flags may carry PD_REG_ISOTROPIC.  Returns the slot (0/1) of
+    xbar/p that holds the final state, or None when the library declined (nothing
+    was launched).  Does not synchronise."""
+    import ctypes
+    ndim, nz, ny, nx = dims3(shape)
+    members = int(members)
+    n = nz * ny * nx
+    _same(x, xbar0, xbar1, bt)
+    _same(p0, p1)
+    if p0.dtype != x.dtype or x.numel() != members * n or \
+            p0.numel() != members * ndim * n:
+        raise ValueError("operand mismatch: %d members of %d voxels against x[%d], "
+                         "p[%d]" % (members, n, x.numel(), p0.numel()))
+    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if sigma.ndim != 2 or sigma.shape[0] != members or lmbda.size != members or \
+            tau.shape != sigma.shape or theta.shape != sigma.shape:
+        raise ValueError("schedules must be (members, iterations) arrays")
+    iters = int(sigma.shape[1])
+    if _pending_runs:
+        settle_persist_runs()
+    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
+    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
+    nbytes = max(16, entry * members * iters)
+    tab_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    tab = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    slot = ctypes.c_int(0)
+    rc = _fn("pd_batch_run", x)(
+        _p(xbar0), _p(xbar1), _p(x), _p(bt), _p(p0), _p(p1), members, ndim, nz, ny,
+        nx, w[0], w[1], w[2], lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
+        theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber),
+        int(flags), tab_host.data_ptr(), _p(tab), nbytes, ctypes.addressof(slot),
+        stream_ptr())
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_pd_batch_run")
+    _wrote(xbar0, xbar1, x, p0, p1)
+    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
+    ev = torch.cuda.Event()
+    ev.record()
+    _sweep_staging.append((ev, tab_host))
+    return int(slot.value)
+
+
 # ----------------------------------------------------------------- ADMM ----
 def admm_vw_update(x, v, w_, c, rhs, shape, w, thr, rhs_scale, want_norm=False):
     """v, w_ and the next right-hand side rhs = rhs_scale * (v - w_ + c) from one

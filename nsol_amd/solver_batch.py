@@ -1,0 +1,269 @@
+"""Many independent primal-dual problems of one shape in stacked device launches:
+the slices of a stack denoised slice by slice, a batch of 2-D images, a set of small
+volumes -- the job that is otherwise a Python loop of PrimalDualSolver objects.
+
+    solvers = [PrimalDualSolver(...), ...]       # configured exactly as today
+    batch = PrimalDualBatch(solvers)
+    batch.run()
+    x = solvers[3].get_x()                       # as if solvers[3].run() had run
+    X = batch.get_x_all_device()                 # (P, n), callers' units
+
+Solvers whose plans (PrimalDualSolver.plan()) agree in shape, inverse spacings,
+dimension, flags, Huber gamma, dtype, device, iteration count and observation
+points form a STACK: their observations and start vectors are uploaded together
+(one page-locked (P, n) array each), scaled by every member's own x_scale in one
+launch each (ops.scale_rows) and advanced together, ONE launch per iteration
+(nsol_pd_batch_run_*), in groups that keep the state under
+ops.PD_BATCH_GROUP_BYTES.  The data, x_scale, alpha, alg_type and L2 may differ
+from member to member.  Every member's result is bit-identical to its own run().
+
+Everything else runs `solver.run()`, one after the other ("sequential"): a plan
+that is None (foreign callables, deconvolution), a stack of one, members above
+ops.PD_BATCH_MAX_VOXELS, a geometry the library declines on its first launch, an
+observer that keeps iterates on the host, a verbose solver.
+"""
+import datetime
+import time
+
+import numpy as np
+
+from . import ops
+from .device import is_device_tensor, torch_dtype
+from .observer import observation_points
+from .primal_dual_solver import PrimalDualSolver, step_schedule
+
+
+def _dev_index(v):
+    return v.device.index if is_device_tensor(v) else None
+
+
+def member_key(solver, plan):
+    """What the members of one stack share, or None for a solver that runs on its
+    own: (shape, w, dim, flags, gamma, dtype, iterations, observation points,
+    device of the data, device of x0)."""
+    if plan is None:
+        return None
+    iters = int(solver._iterations)
+    n = int(np.prod(plan["shape"]))
+    if iters < 1 or n > ops.PD_BATCH_MAX_VOXELS or solver._verbose:
+        return None
+    points = None
+    obs = solver._observer
+    if obs is not None:
+        if obs.get_keep_iterates():
+            return None
+        points = tuple(observation_points(iters, obs.get_every()))
+    x0_dev = None if solver._x0_host is not None else _dev_index(solver._x0_dev)
+    return (tuple(int(s) for s in plan["shape"]),
+            tuple(float(v) for v in plan["w"]), int(plan["dim"]),
+            int(plan["flags"]), float(plan["gamma"]), np.dtype(solver._dtype).name,
+            iters, points, ("data", _dev_index(plan["data"])), ("x0", x0_dev))
+
+
+def plan_stacks(keys):
+    """[[member index, ...], ...]: the stacks of two or more members with equal
+    keys, in order of their first member; every other index runs sequentially."""
+    by_key = {}
+    for i, k in enumerate(keys):
+        if k is not None:
+            by_key.setdefault(k, []).append(i)
+    return [idx for idx in by_key.values() if len(idx) > 1]
+
+
+class PrimalDualBatch(object):
+
+    def __init__(self, solvers):
+        solvers = list(solvers)
+        if not solvers:
+            raise ValueError("a batch needs at least one solver")
+        seen = set()
+        for s in solvers:
+            if not isinstance(s, PrimalDualSolver):
+                raise ValueError("a batch takes PrimalDualSolver objects, not %s" %
+                                 type(s).__name__)
+            if id(s) in seen:
+                raise ValueError("the same solver object is in the batch twice")
+            seen.add(id(s))
+            if s._x0_ndim != 1:
+                raise ValueError("Initial value x0 must be a 1D array")
+        self._solvers = solvers
+        self._execution = None
+        self._group = None
+        self._stacks = []           # (member indices, (P * n) iterate, solver units)
+        self._computational_time = datetime.timedelta(seconds=0)
+
+    # ------------------------------------------------------------------
+    def get_solvers(self):
+        return list(self._solvers)
+
+    def get_execution(self):
+        """One of 'stacked' / 'sequential' per solver after run() (None before)."""
+        return None if self._execution is None else list(self._execution)
+
+    def get_group_size(self):
+        """Members per stacked launch of the last run's largest stack (None: no
+        stack ran)."""
+        return self._group
+
+    def get_computational_time(self):
+        return self._computational_time
+
+    # ------------------------------------------------------------------
+    def run(self):
+        import torch
+        t0 = time.time()
+        solvers = self._solvers
+        for s in solvers:
+            if s._x0_ndim != 1:
+                raise ValueError("Initial value x0 must be a 1D array")
+        plans = [s.plan() for s in solvers]
+        keys = [member_key(s, p) for s, p in zip(solvers, plans)]
+        execution = ["sequential"] * len(solvers)
+        self._stacks, self._group = [], None
+        self._staging = []
+        for idx in plan_stacks(keys):
+            t1 = time.time()
+            x_all = self._run_stack(idx, plans)
+            if x_all is None:
+                continue                       # declined: nothing was written
+            torch.cuda.synchronize()
+            ops.settle_persist_runs(synchronize=False)
+            took = datetime.timedelta(seconds=time.time() - t1)
+            n = x_all.numel() // len(idx)
+            for m, i in enumerate(idx):
+                s = solvers[i]
+                s._x = x_all[m * n:(m + 1) * n]
+                s._execution = "fused"
+                s._computational_time = took
+                if s._observer is not None:
+                    s._observer._finish()
+                    s._observer.set_computational_time(took)
+                execution[i] = "stacked"
+            self._stacks.append((list(idx), x_all))
+        del self._staging
+        for i, s in enumerate(solvers):
+            if execution[i] == "sequential":
+                s.run()
+        self._execution = execution
+        self._computational_time = datetime.timedelta(seconds=time.time() - t0)
+
+    def _upload_rows(self, rows, dtype):
+        """One page-locked (P, n) array of `dtype`, filled row by row (NumPy casts
+        as to_device does) and sent in one copy."""
+        import torch
+        from .device import device
+        P, n = len(rows), int(np.size(rows[0]))
+        host = torch.empty((P, n), dtype=torch_dtype(dtype), pin_memory=True)
+        view = host.numpy()
+        for m, r in enumerate(rows):
+            np.copyto(view[m], np.asarray(r).reshape(-1), casting="unsafe")
+        self._staging.append(host)       # alive until the run has synchronised
+        return host.to(device(), non_blocking=True)
+
+    def _scales(self, values):
+        import torch
+        from .device import device
+        return torch.from_numpy(np.asarray(values, dtype=np.float64)).to(device())
+
+    def _run_stack(self, idx, plans):
+        """The members `idx` in one launch per iteration and group.  Returns their
+        stacked iterate (P * n, solver units), or None when the library declined
+        on its first launch (nothing has been written to any solver then)."""
+        import torch
+        from .device import device
+        from .proximal_operators import scaled_data_on_device
+        solvers = [self._solvers[i] for i in idx]
+        plan = plans[idx[0]]
+        P, iters, dim = len(idx), int(solvers[0]._iterations), plan["dim"]
+        n = int(np.prod(plan["shape"]))
+        td = torch_dtype(solvers[0]._dtype)
+        dev = device()
+        lmbda = np.empty(P)
+        sig, ta, th = (np.empty((P, iters)) for _ in range(3))
+        for m, s in enumerate(solvers):
+            lmbda[m] = 1. / s._alpha
+            sig[m], ta[m], th[m] = step_schedule(s._alg_type, s._L2, lmbda[m], iters)
+        # ---- the scaled observations: float64 / x_scale, rounded once
+        datas = [plans[i]["data"] for i in idx]
+        if is_device_tensor(datas[0]):
+            bt = torch.empty(P * n, dtype=td, device=dev)
+            like = bt[:1]
+            for m, i in enumerate(idx):
+                bt[m * n:(m + 1) * n].copy_(scaled_data_on_device(
+                    datas[m], plans[i]["data_scale"], like))
+        else:
+            raw = self._upload_rows(datas, np.float64)
+            bt = ops.scale_rows(
+                raw, self._scales([plans[i]["data_scale"] for i in idx]), P,
+                divide=True, dtype=td).view(-1)
+        # ---- the start vectors: rounded to the working dtype, then / x_scale
+        if solvers[0]._x0_host is None:
+            x_all = torch.empty(P * n, dtype=td, device=dev)
+            for m, s in enumerate(solvers):
+                x_all[m * n:(m + 1) * n].copy_(s._x0_device())
+        else:
+            raw = self._upload_rows([s._x0_host for s in solvers], solvers[0]._dtype)
+            x_all = ops.scale_rows(raw, self._scales([s._x_scale for s in solvers]),
+                                   P, divide=True).view(-1)
+        G = ops.batch_group_size(P, n, dim, x_all.element_size())
+        xbar = [torch.empty(G * n, dtype=td, device=dev) for _ in range(2)]
+        p = [torch.empty(G * dim * n, dtype=td, device=dev) for _ in range(2)]
+        # ---- device-mode observers share their points (member_key): the run is
+        # enqueued in the stretches between them
+        obs = solvers[0]._observer
+        bounds = [0, iters] if obs is None else \
+            observation_points(iters, obs.get_every())
+        first_call = True
+        for a, b in ops.sweep_groups(P, G):
+            g = b - a
+            x = x_all[a * n:b * n]
+            xb = [t[:g * n] for t in xbar]
+            pp = [t[:g * dim * n] for t in p]
+            xb[0].copy_(x)
+            k = 0
+            for i0, i1 in zip(bounds[:-1], bounds[1:]):
+                slot = ops.pd_batch_run(
+                    xb[k], xb[1 - k], x, bt[a * n:b * n], pp[k], pp[1 - k], g,
+                    plan["shape"], plan["w"], lmbda[a:b], sig[a:b, i0:i1],
+                    ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0, plan["gamma"],
+                    plan["flags"])
+                if slot is None:
+                    if first_call:
+                        return None
+                    raise RuntimeError("nsol_pd_batch_run declined in mid-stack")
+                if first_call and obs is not None:
+                    # the library has taken the stack: the observation of the
+                    # start vectors, as Solver._observe_start makes it
+                    for s in solvers:
+                        s._x = None
+                        s._observe_start(iters)
+                first_call = False
+                k = k if slot == 0 else 1 - k
+                if obs is not None:
+                    for m in range(a, b):
+                        solvers[m]._observe_at(i1, x_all[m * n:(m + 1) * n])
+        self._group = max(self._group or 0, G)
+        return x_all
+
+    # ------------------------------------------------------------------
+    def get_x_device(self, i):
+        return self._solvers[i].get_x_device()
+
+    def get_x(self, i):
+        return self._solvers[i].get_x()
+
+    def get_x_all_device(self):
+        """(P, n) device tensor of every solver's result in its caller's units; one
+        ops.scale_rows when the whole list ran as one stack."""
+        import torch
+        if self._execution is None:
+            raise RuntimeError("run() first")
+        solvers = self._solvers
+        if len(self._stacks) == 1 and len(self._stacks[0][0]) == len(solvers):
+            idx, x_all = self._stacks[0]
+            s = self._scales([solvers[i]._x_scale for i in idx])
+            return ops.scale_rows(x_all, s, len(idx)).view(len(idx), -1)
+        rows = [s.get_x_device() for s in solvers]
+        if len(set(r.numel() for r in rows)) != 1:
+            raise ValueError("the solvers' results differ in length")
+        return torch.stack(rows)
