@@ -70,6 +70,13 @@ extern "C" {
  * k_pd_fused_iso, nsol_pdi.hip, per iteration); every other fused form returns -2,
  * having launched nothing. */
 #define NSOL_PD_REG_ISOTROPIC 4
+/* or-ed with NSOL_PD_DATA_L2 / _L1: the data term carries per-voxel weights w >= 0,
+ * lambda/2 sum w_i (x_i - b_i)^2 or lambda sum w_i |x_i - b_i|.  Taken by
+ * nsol_pd_weighted_* alone (nsol_pdw.hip), which have the weights pointer; every
+ * other entry that takes flags -- nsol_pd_fused_iter_*, nsol_pd_fused2_iter_*,
+ * nsol_pd_fusedk_iter_*, nsol_pd_persist_run*, nsol_pd_run*, nsol_pd_sweep_run_*,
+ * nsol_pd_batch_* -- returns -2, having launched nothing. */
+#define NSOL_PD_DATA_WEIGHTED 8
 /* nsol_pd_run_* only: the caller can take the final primal iterate from x_alt (see
  * there) -- no copy back into x after an odd number of multi-iteration launches */
 #define NSOL_PD_RUN_X_MAY_SWAP 0x100
@@ -718,6 +725,78 @@ int nsol_scale_rows_f64(double *out, const double *in, const double *s, int divi
                         int members, int64_t n, void *stream);
 int nsol_scale_rows_f64_to_f32(float *out, const double *in, const double *s,
                                int divide, int members, int64_t n, void *stream);
+
+/* ---------------------------------------------------------------------- *
+ * Weighted / masked data term (nsol_pdw.hip): lambda/2 sum w_i (x_i - b_i)^2 or
+ * lambda sum w_i |x_i - b_i| with per-voxel weights w_i >= 0 (finite; NOT scaled
+ * by x_scale).  With bt = b / x_scale and t = tau * lambda * w_i, formed in the
+ * element type as t = tl * w:
+ *   l2: out = (u + t * bt) / (1 + t)     an IEEE division in float32 and float64
+ *   l1: out = bt + max(|u - bt| - t, 0) * sign(u - bt)
+ *   w_i == 0: out = u exactly, whatever bt holds there (NaN and +-inf included).
+ * float64 with w == 1 gives the bits of the unweighted kernels; float32 does not
+ * (those multiply by a reciprocal formed on the host).
+ *
+ * nsol_prox_ell2_weighted_* / nsol_prox_ell1_weighted_*: the prox alone, `tau` the
+ * product tau * lambda; out may be x.
+ *
+ * nsol_pd_weighted_*: `members` stacked primal-dual runs, one launch per iteration
+ * for all of them, layout and table as for the image stack above (x, xbar member-
+ * major with n elements per member, p with ndim * n; table entries of
+ * nsol_pd_sweep_entry_bytes(elem_size) bytes, [iteration][member]).  bt and wt each
+ * take a MEMBER STRIDE in elements, 0 or n: member m reads bt[m * bt_stride + i] and
+ * wt[m * wt_stride + i].  A single run is members = 1; a parameter sweep shares both
+ * arrays (stride 0); a stack of images brings its own of each (stride n).  Contiguous
+ * volumes only.  Member m is bit-identical to a single run with that member's data,
+ * weights and scalars, and to the loop of nsol_grad_*, the dual prox, nsol_grad_adj_*
+ * and nsol_prox_ell*_weighted_*.
+ * flags: NSOL_PD_REG_* | NSOL_PD_DATA_* and NSOL_PD_DATA_WEIGHTED, which must be set
+ * (NSOL_EINVAL otherwise); NSOL_PD_REG_ISOTROPIC is taken.
+ * nsol_pd_weighted_table_*: fills and uploads the table (arguments as the schedules
+ * of nsol_pd_sweep_run_*); nsol_pd_weighted_iter_*: one launch, iteration `iteration`
+ * of that table; nsol_pd_weighted_run_*: the table, then `iterations` launches,
+ * *final_slot_host the xbar / p slot that holds the final state.  -2, nothing
+ * launched, for what nsol_pd_batch_* would decline for its geometry or member count.
+ * nsol_pd_weighted_launches: launches of k_pd_w / k_pd_w_iso this process has made. */
+int nsol_pd_weighted_launches(void);
+int nsol_prox_ell2_weighted_f32(float *out, const float *x, const float *bt, const float *wt,
+    double tau, int64_t n, void *stream);
+int nsol_prox_ell1_weighted_f32(float *out, const float *x, const float *bt, const float *wt,
+    double tau, int64_t n, void *stream);
+int nsol_pd_weighted_table_f32(int members, const double *lmbda_host,
+    const double *sigma_host, const double *tau_host, const double *theta_host,
+    int iterations, int p_is_zero, double gamma_huber, int flags, void *tab_host,
+    void *tab, int64_t tab_bytes, void *stream);
+int nsol_pd_weighted_iter_f32(const float *xbar_in, float *xbar_out, float *x, const float *bt,
+    int64_t bt_stride, const float *wt, int64_t wt_stride, const float *p_in, float *p_out,
+    int members, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+    double wz, const void *tab, int iteration, int flags, void *stream);
+int nsol_pd_weighted_run_f32(float *xbar0, float *xbar1, float *x, const float *bt,
+    int64_t bt_stride, const float *wt, int64_t wt_stride, float *p0, float *p1, int members,
+    int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+    const double *lmbda_host, const double *sigma_host, const double *tau_host,
+    const double *theta_host, int iterations, int p_is_zero, double gamma_huber,
+    int flags, void *tab_host, void *tab, int64_t tab_bytes, int *final_slot_host,
+    void *stream);
+int nsol_prox_ell2_weighted_f64(double *out, const double *x, const double *bt, const double *wt,
+    double tau, int64_t n, void *stream);
+int nsol_prox_ell1_weighted_f64(double *out, const double *x, const double *bt, const double *wt,
+    double tau, int64_t n, void *stream);
+int nsol_pd_weighted_table_f64(int members, const double *lmbda_host,
+    const double *sigma_host, const double *tau_host, const double *theta_host,
+    int iterations, int p_is_zero, double gamma_huber, int flags, void *tab_host,
+    void *tab, int64_t tab_bytes, void *stream);
+int nsol_pd_weighted_iter_f64(const double *xbar_in, double *xbar_out, double *x, const double *bt,
+    int64_t bt_stride, const double *wt, int64_t wt_stride, const double *p_in, double *p_out,
+    int members, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+    double wz, const void *tab, int iteration, int flags, void *stream);
+int nsol_pd_weighted_run_f64(double *xbar0, double *xbar1, double *x, const double *bt,
+    int64_t bt_stride, const double *wt, int64_t wt_stride, double *p0, double *p1, int members,
+    int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+    const double *lmbda_host, const double *sigma_host, const double *tau_host,
+    const double *theta_host, int iterations, int p_is_zero, double gamma_huber,
+    int flags, void *tab_host, void *tab, int64_t tab_bytes, int *final_slot_host,
+    void *stream);
 
 /* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253

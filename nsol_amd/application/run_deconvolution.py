@@ -119,7 +119,17 @@ def main(argv=None):
                     help="evaluate the measures on the device every K "
                          "iterations (and at the last) instead of on a host "
                          "copy of every iterate")
+    ap.add_argument("--mask", default=None, metavar="FILE",
+                    help="not supported here (see run_denoising)")
+    ap.add_argument("--weights", default=None, metavar="FILE",
+                    help="not supported here (see run_denoising)")
     args = ap.parse_args(argv)
+    if args.mask is not None or args.weights is not None:
+        ap.error("--mask / --weights are options of run_denoising: the weighted "
+                 "data term is a prox of the denoising problem, while "
+                 "deconvolution solves a linear least-squares problem per step "
+                 "(prox_linear_least_squares), where a mask belongs in the "
+                 "operator A")
 
     reader = dr.DataReader(args.observation)
     reader.read_data()

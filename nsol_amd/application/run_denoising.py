@@ -5,7 +5,7 @@ without plotting).
     python -m nsol_amd.application.run_denoising --observation in.nii.gz \\
         --result out.nii.gz --reconstruction-type TVL2 --alpha 0.03 \\
         --iterations 50 [--reference gt.nii.gz] [--L2 8] [--dtype float32]
-        [--isotropic]
+        [--isotropic] [--mask mask.nii.gz | --weights w.nii.gz]
 
 --isotropic: the regulariser is the isotropic TV / Huber norm -- the per-voxel
 vector norm that PriorMeasures reports and ADMM minimises -- instead of the
@@ -14,6 +14,14 @@ reference's sum over the components (one fused launch per iteration).
 Several values of --alpha are a parameter sweep (nsol_amd/parameter_sweep.py): the
 members run stacked, one launch per iteration for all of them; --result-dir DIR
 keeps every member (<stem>_alpha<value><ext>) next to a sweep.npz.
+
+--mask FILE / --weights FILE: a weighted data term, sum_i w_i (x_i - b_i)^2 or
+sum_i w_i |x_i - b_i| (prox_ell*_denoising_weighted).  --mask uses voxels > 0 as
+weight 1 and the rest as weight 0 (the result is inpainted there, whatever the
+observation holds); --weights takes the image's values as they are (finite, >= 0).
+The image must have the observation's shape.  Both compose with --isotropic, several
+--alpha and --slice-wise (the weights are sliced with the data; a slice whose
+weights are all zero is copied through).
 
 --slice-wise: a 3-D observation is shape[0] independent 2-D images, each with its
 own x_scale = max(slice), run together through PrimalDualBatch
@@ -35,14 +43,26 @@ from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
 
 
-def wiring(observed_nda, reconstruction_type, isotropic=False):
+def wiring(observed_nda, reconstruction_type, isotropic=False, weights=None):
     """Wiring of run_denoising.py:95-154: the callables, start and scale that
     PrimalDualSolver / PrimalDualSweep are built from.  isotropic: the dual prox
-    projects every voxel's gradient vector (prox_*_conj_isotropic)."""
+    projects every voxel's gradient vector (prox_*_conj_isotropic).  weights: an
+    array of the observation's shape, the per-voxel weights of the data term; the
+    scale is then the maximum over the voxels that count, and the start is zero
+    where a voxel that does not count holds no finite value."""
     dimension = observed_nda.ndim
     b = observed_nda.flatten()
     x0 = observed_nda.flatten()
     x_scale = np.max(observed_nda)
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.shape != observed_nda.shape:
+            raise ValueError("the weights have shape %s, the observation %s" %
+                             (weights.shape, observed_nda.shape))
+        w = weights.flatten()
+        counted = w > 0
+        x_scale = np.max(b[counted]) if counted.any() else 1.
+        x0[~counted & ~np.isfinite(x0)] = 0
     linear_operators = getattr(
         LinearOperators, "LinearOperators%dD" % dimension)()
     grad, grad_adj = linear_operators.get_gradient_operators()
@@ -54,9 +74,15 @@ def wiring(observed_nda, reconstruction_type, isotropic=False):
     if reconstruction_type in ("TVL1", "HuberL1"):
         prox_f = lambda x, tau: prox.prox_ell1_denoising(
             x, tau, x0=b, x_scale=x_scale)
+        if weights is not None:
+            prox_f = lambda x, tau: prox.prox_ell1_denoising_weighted(
+                x, tau, x0=b, weights=w, x_scale=x_scale)
     elif reconstruction_type in ("TVL2", "HuberL2"):
         prox_f = lambda x, tau: prox.prox_ell2_denoising(
             x, tau, x0=b, x_scale=x_scale)
+        if weights is not None:
+            prox_f = lambda x, tau: prox.prox_ell2_denoising_weighted(
+                x, tau, x0=b, weights=w, x_scale=x_scale)
     else:
         raise ValueError("Denoising type '%s' not known" %
                          reconstruction_type)
@@ -74,11 +100,29 @@ def wiring(observed_nda, reconstruction_type, isotropic=False):
 
 
 def build_solver(observed_nda, reconstruction_type, alpha, iterations, L2=8,
-                 verbose=0, dtype=None, alg_type="ALG2", isotropic=False):
+                 verbose=0, dtype=None, alg_type="ALG2", weights=None,
+                 isotropic=False):
     return pd.PrimalDualSolver(
         L2=L2, alpha=alpha, iterations=iterations, verbose=verbose,
         alg_type=alg_type, dtype=dtype,
-        **wiring(observed_nda, reconstruction_type, isotropic))
+        **wiring(observed_nda, reconstruction_type, isotropic, weights))
+
+
+def read_weights(args, shape):
+    """The weights that --mask / --weights name (None without either): the mask
+    as 1 where its voxel is > 0 and 0 elsewhere, the weights as they are."""
+    path = args.mask if args.mask is not None else args.weights
+    if path is None:
+        return None
+    reader = dr.DataReader(path)
+    reader.read_data()
+    nda = np.asarray(reader.get_data())
+    if nda.shape != tuple(shape):
+        raise ValueError("'%s' has shape %s, the observation %s" %
+                         (path, nda.shape, tuple(shape)))
+    if args.mask is not None:
+        return (nda > 0).astype(np.float64)
+    return nda.astype(np.float64)
 
 
 def member_result_path(result_dir, like, alpha):
@@ -90,14 +134,14 @@ def member_result_path(result_dir, like, alpha):
                                                      "." + ext if ext else ""))
 
 
-def run_sweep(args, observed_nda, x_ref, reader):
+def run_sweep(args, observed_nda, x_ref, reader, weights=None):
     """Several alphas: the members stacked through PrimalDualSweep."""
     from ..parameter_sweep import PrimalDualSweep
     sweep = PrimalDualSweep(
         L2=args.L2, parameters={"alpha": list(args.alpha)},
         iterations=args.iterations, alg_type=args.alg_type,
         dtype=np.dtype(args.dtype).type,
-        **wiring(observed_nda, args.reconstruction_type, args.isotropic))
+        **wiring(observed_nda, args.reconstruction_type, args.isotropic, weights))
     if x_ref is not None:
         sweep.set_measures({
             m: (lambda x, m=m:
@@ -137,24 +181,29 @@ def run_sweep(args, observed_nda, x_ref, reader):
     return 0
 
 
-def classify_slices(observed_nda):
+def classify_slices(observed_nda, weights=None):
     """(indices of the slices to solve, indices copied through unchanged): a slice
-    whose maximum is not positive has no x_scale to divide by (wiring())."""
+    whose maximum is not positive has no x_scale to divide by (wiring()); with
+    weights the maximum is taken over the voxels whose weight is positive, and a
+    slice without any is copied through."""
     solve, copy = [], []
     for k in range(observed_nda.shape[0]):
-        m = np.max(observed_nda[k])
+        vals = observed_nda[k] if weights is None else \
+            observed_nda[k][np.asarray(weights[k]) > 0]
+        m = np.max(vals) if np.size(vals) else 0.
         (solve if np.isfinite(m) and m > 0 else copy).append(k)
     return solve, copy
 
 
-def run_slice_wise(args, observed_nda, x_ref, reader):
+def run_slice_wise(args, observed_nda, x_ref, reader, weights=None):
     """--slice-wise: one solver per slice, all through PrimalDualBatch."""
     from ..solver_batch import PrimalDualBatch
-    solve, copy = classify_slices(observed_nda)
+    solve, copy = classify_slices(observed_nda, weights)
     solvers = [build_solver(observed_nda[k], args.reconstruction_type,
                             args.alpha[0], args.iterations, L2=args.L2,
                             dtype=np.dtype(args.dtype).type,
-                            alg_type=args.alg_type, isotropic=args.isotropic)
+                            alg_type=args.alg_type, isotropic=args.isotropic,
+                            weights=None if weights is None else weights[k])
                for k in solve]
     recon = np.array(observed_nda, dtype=np.float64)
     execution = []
@@ -218,6 +267,14 @@ def main(argv=None):
                     help="treat a 3-D observation as shape[0] independent 2-D "
                          "images, each scaled by its own maximum, and run them "
                          "stacked (one launch per iteration for all slices)")
+    wgroup = ap.add_mutually_exclusive_group()
+    wgroup.add_argument("--mask", default=None, metavar="FILE",
+                        help="image of the observation's shape: voxels > 0 count "
+                             "in the data term (weight 1), the rest do not (weight "
+                             "0) and are inpainted by the regulariser")
+    wgroup.add_argument("--weights", default=None, metavar="FILE",
+                        help="image of the observation's shape: per-voxel weights "
+                             "of the data term, finite and >= 0, taken as they are")
     args = ap.parse_args(argv)
     if args.slice_wise and len(args.alpha) > 1:
         ap.error("--slice-wise takes a single --alpha")
@@ -237,14 +294,19 @@ def main(argv=None):
         ref_reader.read_data()
         x_ref = ref_reader.get_data().flatten()
 
+    try:
+        weights = read_weights(args, observed_nda.shape)
+    except ValueError as e:
+        ap.error(str(e))
+
     if args.slice_wise:
         if observed_nda.ndim != 3:
             ap.error("--slice-wise needs a 3-D observation, not %d-D" %
                      observed_nda.ndim)
-        return run_slice_wise(args, observed_nda, x_ref, reader)
+        return run_slice_wise(args, observed_nda, x_ref, reader, weights)
 
     if len(args.alpha) > 1 and not args.verbose:
-        return run_sweep(args, observed_nda, x_ref, reader)
+        return run_sweep(args, observed_nda, x_ref, reader, weights)
 
     for alpha in args.alpha:
         solver = build_solver(observed_nda, args.reconstruction_type, alpha,
@@ -252,7 +314,7 @@ def main(argv=None):
                               verbose=args.verbose,
                               dtype=np.dtype(args.dtype).type,
                               alg_type=args.alg_type,
-                              isotropic=args.isotropic)
+                              isotropic=args.isotropic, weights=weights)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \

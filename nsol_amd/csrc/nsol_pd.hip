@@ -161,6 +161,7 @@ int fused_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt,
                     int64_t nx, double wx, double wy, double wz, double sigma,
                     double hden, double tau, double tl, double theta, int flags,
                     void *stream, int64_t pitch = 0) {
+  if (flags & NSOL_PD_DATA_WEIGHTED) return -2;   // no weights pointer here: nsol_pdw.hip
   const PdLaunchTune tune{g_tune.zchunk, g_tune.ry, g_tune.xcd_map, g_tune.rag};
   if (flags & NSOL_PD_REG_ISOTROPIC)   // k_pd_fused_iso, nsol_pdi.hip
     return pd_iso_fused_iter<T>(xbar_in, xbar_out, x, bt, p_in, p_out, ndim, nz, ny, nx,
@@ -218,6 +219,7 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
              const double *theta, int iterations, int p_is_zero,
              double gamma_huber, int flags, int *final_slot, void *stream,
              int64_t pitch = 0) {
+  if (flags & NSOL_PD_DATA_WEIGHTED) return -2;   // no weights pointer here: nsol_pdw.hip
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (iterations < 0 || !sig || !tau || !theta || !x) return NSOL_EINVAL;
   const bool pitched = pitch > nx;

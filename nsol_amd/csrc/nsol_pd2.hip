@@ -456,7 +456,7 @@ int pd_fused2_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const
   using nsol_pd2::g_tune2;
   // the isotropic projection needs a neighbour's whole dual vector: only
   // k_pd_fused_iso (nsol_pdi.hip) has that form
-  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
+  if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return -2;
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!xbar_in || !xbar_out || !x_in || !x_out || !bt || !p_out ||
       xbar_in == xbar_out || p_in == p_out || x_in == x_out)

@@ -6,6 +6,7 @@
 
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
+#include "nsol_pd_weighted.hpp"
 
 namespace nsol {
 
@@ -36,12 +37,15 @@ __device__ __forceinline__ bool pd_fused_block_tile(int bid, int ntx, int nty, i
 // One iteration on tile (tx, ty), z-chunk zc of one volume: each wave owns a
 // (LX*VEC) x (LY*RY) patch of the x-y tile and marches along z (see nsol_pd.hip).
 // RAG: rows that are not a multiple of VEC elements / arrays that are not 16-byte
-// aligned.
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+// aligned.  WGT: the data term carries per-voxel weights wt (nsol_pd_weighted.hpp),
+// one more row load per plane and prox_data_w in place of prox_data (k_pd_w,
+// nsol_pdw.hip); the unweighted kernels leave it off and are compiled as before.
+template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false>
 __device__ __forceinline__ void pd_fused_tile(
     const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
     const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
-    const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk) {
+    const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk,
+    const T *__restrict__ wt = nullptr) {
   constexpr int LY = kWave / LX;
   constexpr int WAVES = kBlock / kWave;
   constexpr int TY = WAVES * LY * RY;
@@ -119,17 +123,20 @@ __device__ __forceinline__ void pd_fused_tile(
   for (int64_t z = zbeg; z < zend; ++z, off += G.sz) {
     // ---------------- loads of plane z (and xbar of plane z+1) ------------
     T xn[RY][VEC], xv[RY][VEC], bv[RY][VEC];
+    T wv[RY][VEC];      // WGT: the weights of the data term (zero outside the row)
     T pxo[RY][VEC], pyo[RY][VEC], pzo[RY][VEC];
     const bool znext = (NDIM >= 3) && (z + 1 < G.nz);
 #pragma unroll
     for (int r = 0; r < RY; ++r) {
       zero(xn[r]); zero(xv[r]); zero(bv[r]);
+      if constexpr (WGT) zero(wv[r]);
       zero(pxo[r]); zero(pyo[r]); zero(pzo[r]);
       if (rin[r]) {
         const int64_t o = off + r * G.sy;
         if (znext) ld(xbar_in + o + G.sz, xn[r]);
         ld(x + o, xv[r]);
         ld(bt + o, bv[r]);
+        if constexpr (WGT) ld(wt + o, wv[r]);
         if (S.has_p) {
           ld(pin_x + o, pxo[r]);
           if constexpr (NDIM >= 2) ld(pin_y + o, pyo[r]);
@@ -233,7 +240,9 @@ __device__ __forceinline__ void pd_fused_tile(
         if constexpr (NDIM >= 3)
           kt += pzn[r][k] * (-G.wz) + pzprev[r][k] * G.wz;
         const T u = xv[r][k] - S.tau * kt;
-        const T xnew = prox_data(u, bv[r][k], S.tl, S.one_plus_tl, S.l1 != 0);
+        T xnew;
+        if constexpr (WGT) xnew = prox_data_w(u, bv[r][k], wv[r][k], S.tl, S.l1 != 0);
+        else xnew = prox_data(u, bv[r][k], S.tl, S.one_plus_tl, S.l1 != 0);
         xo_new[k] = xnew;
         xb_new[k] = xnew + S.theta * (xnew - xv[r][k]);
       }

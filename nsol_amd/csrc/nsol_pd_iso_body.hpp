@@ -14,6 +14,7 @@
 
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
+#include "nsol_pd_weighted.hpp"
 #include "nsol_pd_fused_body.hpp"
 
 namespace nsol {
@@ -45,12 +46,13 @@ __device__ __forceinline__ void dual_project(T &q0, T &q1, T &q2, bool huber, T 
 }
 
 // One iteration on tile (tx, ty), z-chunk zc of one volume; arguments as
-// pd_fused_tile.
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+// pd_fused_tile (WGT / wt included).
+template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false>
 __device__ __forceinline__ void pd_fused_iso_tile(
     const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
     const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
-    const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk) {
+    const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk,
+    const T *__restrict__ wt = nullptr) {
   constexpr int LY = kWave / LX;
   constexpr int WAVES = kBlock / kWave;
   constexpr int TY = WAVES * LY * RY;
@@ -169,15 +171,18 @@ __device__ __forceinline__ void pd_fused_iso_tile(
 
   for (int64_t z = zbeg; z < zend; ++z, off += G.sz) {
     T xn[RY][VEC], xv[RY][VEC], bv[RY][VEC];
+    T wv[RY][VEC];      // WGT: the weights of the data term (zero outside the row)
     const bool znext = (NDIM >= 3) && (z + 1 < G.nz);
 #pragma unroll
     for (int r = 0; r < RY; ++r) {
       zero(xn[r]); zero(xv[r]); zero(bv[r]);
+      if constexpr (WGT) zero(wv[r]);
       if (rin[r]) {
         const int64_t o = off + r * G.sy;
         if (znext) ld(xbar_in + o + G.sz, xn[r]);
         ld(x + o, xv[r]);
         ld(bt + o, bv[r]);
+        if constexpr (WGT) ld(wt + o, wv[r]);
       }
     }
 
@@ -268,7 +273,9 @@ __device__ __forceinline__ void pd_fused_iso_tile(
         if constexpr (NDIM >= 3)
           kt += pzn[r][k] * (-G.wz) + pzprev[r][k] * G.wz;
         const T u = xv[r][k] - S.tau * kt;
-        const T xnew = prox_data(u, bv[r][k], S.tl, S.one_plus_tl, S.l1 != 0);
+        T xnew;
+        if constexpr (WGT) xnew = prox_data_w(u, bv[r][k], wv[r][k], S.tl, S.l1 != 0);
+        else xnew = prox_data(u, bv[r][k], S.tl, S.one_plus_tl, S.l1 != 0);
         xo_new[k] = xnew;
         xb_new[k] = xnew + S.theta * (xnew - xv[r][k]);
       }

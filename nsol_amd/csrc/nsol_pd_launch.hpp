@@ -1,6 +1,6 @@
 // Host-side launch path of the kernels that do ONE Chambolle-Pock iteration in one
-// pass: k_pd_fused (nsol_pd.hip), k_pd_fused_iso (nsol_pdi.hip) and the
-// member-stacked k_pd_sweep (nsol_pds.hip).  They share the wave layout of
+// pass: k_pd_fused (nsol_pd.hip), k_pd_fused_iso (nsol_pdi.hip), the member-stacked
+// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip) and k_pd_w (nsol_pdw.hip).  They share the wave layout of
 // nsol_pd_fused_body.hpp -- a wave owns (LX*VEC) x (LY*RY) of an x-y tile and
 // marches along z -- so the rounding of the scalars, the grid, the automatic rows
 // per lane and the access form are chosen here, once.  A new kernel of the family
@@ -42,6 +42,8 @@ struct PdLaunchArgs {
   int members = 1;                    // volumes stacked along gridDim.y
   PdLaunchTune tune{0, 0, 1, 1};
   hipStream_t st = nullptr;
+  const T *wt = nullptr;              // the weighted kernel's per-voxel weights and
+  int64_t bt_stride = 0, wt_stride = 0;  // its member strides of bt / wt (0 or G.n)
 };
 
 struct PdGridPlan {
@@ -99,7 +101,8 @@ int pd_launch(const PdLaunchArgs<T> &a) {
   const Geom<T> &G = a.G;
   const bool vec_ok = (G.nx % VW == 0) && aligned16(a.xbar_in) && aligned16(a.xbar_out) &&
                       aligned16(a.x) && aligned16(a.bt) && aligned16(a.p_out) &&
-                      (!a.p_in || aligned16(a.p_in)) && ((G.nz * G.ny * G.nx) % VW == 0);
+                      (!a.p_in || aligned16(a.p_in)) && (!a.wt || aligned16(a.wt)) &&
+                      ((G.nz * G.ny * G.nx) % VW == 0);
   const bool rag_ok = a.tune.rag && G.nx >= 2 * VW;
   // rows at a pitch need a vector form (the stacked kernel takes contiguous
   // volumes only: its G.padded is never set)

@@ -126,6 +126,7 @@ int batch_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p
                     T *p_out, int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
                     double wx, double wy, double wz, const void *tab, int iteration,
                     int flags, void *stream) {
+  if (flags & NSOL_PD_DATA_WEIGHTED) return -2;   // no weights pointer here: nsol_pdw.hip
   if (!batch_takes(members, ndim, nz, ny, nx)) return -2;
   if (!xbar_in || !xbar_out || !x || !bt || !p_in || !p_out || !tab || iteration < 0 ||
       xbar_in == xbar_out || p_in == p_out)
@@ -149,6 +150,7 @@ int batch_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int memb
                    const double *theta, int iterations, int p_is_zero, double gamma_huber,
                    int flags, void *tab_host, void *tab, int64_t tab_bytes,
                    int *final_slot, void *stream) {
+  if (flags & NSOL_PD_DATA_WEIGHTED) return -2;   // no weights pointer here: nsol_pdw.hip
   if (!batch_takes(members, ndim, nz, ny, nx)) return -2;
   if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
       tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)

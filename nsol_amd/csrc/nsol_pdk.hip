@@ -1404,7 +1404,7 @@ int pd_fusedk_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const
   using nsol_pdk::g_tunek;
   // the footprint overlap is sized for the component-wise clamp: the isotropic
   // projection (nsol_pdi.hip) has no multi-iteration form
-  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
+  if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return -2;
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   if (!xbar_in || !xbar_out || !x_in || !x_out || !bt || !p_out || !sigma ||
       !hden || !tau || !tl || !theta || xbar_in == xbar_out || p_in == p_out ||

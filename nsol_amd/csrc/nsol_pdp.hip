@@ -470,7 +470,7 @@ int persist_run(const T *xbar, const T *x, const T *bt, const T *p, T *xbar_out,
                 unsigned int *err_word, void *stream) {
   // the faces handed between workgroups carry one dual component each: the
   // isotropic projection (nsol_pdi.hip) has no persistent form
-  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
+  if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return -2;
   NSOL_CHECK_GEOM(ndim, nz, ny, nx);
   constexpr int VEC = 16 / (int)sizeof(T);
   if (!xbar || !x || !bt || !p || !xbar_out || !x_out || !p_out || !sig || !tau ||

@@ -120,7 +120,7 @@ int sweep_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int memb
                    int *final_slot, void *stream) {
   // the stacked kernel shares pd_fused_tile, the component-wise clamp: isotropic
   // sweeps run their members one after the other (nsol_pdi.hip)
-  if (flags & NSOL_PD_REG_ISOTROPIC) return -2;
+  if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return -2;
   if (!sweep_takes(members, ndim, nz, ny, nx)) return -2;
   if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
       tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)

@@ -16,6 +16,9 @@ PD_REG_TV, PD_REG_HUBER, PD_DATA_L2, PD_DATA_L1 = 0, 1, 0, 2
 # or-ed with PD_REG_TV / PD_REG_HUBER: the dual projection divides the voxel's
 # whole gradient vector by max(1, its Euclidean norm) (NSOL_PD_REG_ISOTROPIC)
 PD_REG_ISOTROPIC = 4
+# or-ed with PD_DATA_L2 / PD_DATA_L1: the data term carries per-voxel weights
+# (NSOL_PD_DATA_WEIGHTED); pd_weighted_run / pd_weighted_iter alone take it
+PD_DATA_WEIGHTED = 8
 
 
 def _fn(name, t):
@@ -521,6 +524,32 @@ def prox_ell1(x, bt, tau, out=None):
         out = empty_like(x)
     _lib.check(_fn("prox_ell1", x)(_p(out), _p(x), _p(bt), float(tau),
                                    x.numel(), stream_ptr()), "nsol_prox_ell1")
+    return _wrote(out)
+
+
+def prox_ell2_weighted(x, bt, wt, tau, out=None):
+    """(x + t bt) / (1 + t) with t = tau * wt per element; x where wt == 0."""
+    _same(x, bt, wt)
+    if out is None:
+        out = empty_like(x)
+    else:
+        _same(x, out)
+    _lib.check(_fn("prox_ell2_weighted", x)(_p(out), _p(x), _p(bt), _p(wt), float(tau),
+                                            x.numel(), stream_ptr()),
+               "nsol_prox_ell2_weighted")
+    return _wrote(out)
+
+
+def prox_ell1_weighted(x, bt, wt, tau, out=None):
+    """Soft threshold of x - bt by t = tau * wt per element; x where wt == 0."""
+    _same(x, bt, wt)
+    if out is None:
+        out = empty_like(x)
+    else:
+        _same(x, out)
+    _lib.check(_fn("prox_ell1_weighted", x)(_p(out), _p(x), _p(bt), _p(wt), float(tau),
+                                            x.numel(), stream_ptr()),
+               "nsol_prox_ell1_weighted")
     return _wrote(out)
 
 
@@ -1568,6 +1597,141 @@ def pd_batch_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, t
     ev.record()
     _sweep_staging.append((ev, tab_host))
     return int(slot.value)
+
+
+# ------------------------------------------------- weighted data term ----
+# Runs whose data term carries per-voxel weights (PD_DATA_WEIGHTED; nsol_pdw.hip): one
+# stacked kernel family for the single run (members = 1), the parameter sweep (bt and
+# wt shared by all members) and the stack of images (every member its own of each).
+def pd_weighted_launches():
+    """Launches of the weighted kernels so far (for tests and tools)."""
+    return int(_lib.load().nsol_pd_weighted_launches())
+
+
+def weighted_batch_group_size(members, n, dim, elem_size):
+    """batch_group_size with the member's own weights counted: 5 + 2 dim arrays."""
+    per_member = (5 + 2 * int(dim)) * int(n) * int(elem_size)
+    g = min(PD_BATCH_GROUP_BYTES // per_member, (1 << 31) // int(n), 65535)
+    return int(max(1, min(int(members), g)))
+
+
+def _weighted_operands(x, xbar0, xbar1, bt, wt, p0, p1, members, shape):
+    """(ndim, nz, ny, nx, bt_stride, wt_stride) after the checks that keep the
+    kernel inside its arrays."""
+    ndim, nz, ny, nx = dims3(shape)
+    n = nz * ny * nx
+    _same(x, xbar0, xbar1)
+    _same(p0, p1)
+    _chk(bt)
+    _chk(wt)
+    if p0.dtype != x.dtype or bt.dtype != x.dtype or wt.dtype != x.dtype or \
+            members < 1 or x.numel() != members * n or \
+            p0.numel() != members * ndim * n or \
+            bt.numel() not in (n, members * n) or wt.numel() not in (n, members * n):
+        raise ValueError("operand mismatch: %d members of %d voxels against x[%d], "
+                         "bt[%d], wt[%d], p[%d]" % (members, n, x.numel(), bt.numel(),
+                                                    wt.numel(), p0.numel()))
+    return (ndim, nz, ny, nx, 0 if bt.numel() == n else n,
+            0 if wt.numel() == n else n)
+
+
+def _weighted_schedules(members, lmbda, sigma, tau, theta):
+    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64).reshape(members, -1)
+    tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(members, -1)
+    theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(members, -1)
+    if lmbda.size != members or tau.shape != sigma.shape or \
+            theta.shape != sigma.shape:
+        raise ValueError("schedules must be (members, iterations) arrays")
+    return lmbda, sigma, tau, theta
+
+
+def _weighted_table_buffers(x, members, iters):
+    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
+    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
+    nbytes = max(16, entry * members * iters)
+    return (torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+            torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes)
+
+
+def _weighted_table_keep(tab_host):
+    # the upload is stream-ordered: its pinned source lives until the event has passed
+    ev = torch.cuda.Event()
+    ev.record()
+    _sweep_staging.append((ev, tab_host))
+
+
+def pd_weighted_run(xbar0, xbar1, x, bt, wt, p0, p1, members, shape, w, lmbda, sigma,
+                    tau, theta, p_is_zero, gamma_huber, flags):
+    """Enqueue the iterations of `members` stacked primal-dual runs with a weighted
+    data term (flags carry PD_DATA_WEIGHTED): one launch per iteration for all of
+    them.  Layout as pd_batch_run; bt and wt hold n elements (shared by the members)
+    or members * n (member-major), each on its own.  lmbda is (members,),
+    sigma/tau/theta (members, iterations) -- or 1-D for one member.  Returns the slot
+    (0/1) of xbar/p that holds the final state, or None when the library declined
+    (nothing was launched).  Does not synchronise."""
+    import ctypes
+    members = int(members)
+    ndim, nz, ny, nx, bts, wts = _weighted_operands(x, xbar0, xbar1, bt, wt, p0, p1,
+                                                    members, shape)
+    lmbda, sigma, tau, theta = _weighted_schedules(members, lmbda, sigma, tau, theta)
+    iters = int(sigma.shape[1])
+    if _pending_runs:
+        settle_persist_runs()     # as pd_run: an earlier persistent run may feed this
+    tab_host, tab, nbytes = _weighted_table_buffers(x, members, iters)
+    slot = ctypes.c_int(0)
+    rc = _fn("pd_weighted_run", x)(
+        _p(xbar0), _p(xbar1), _p(x), _p(bt), bts, _p(wt), wts, _p(p0), _p(p1), members,
+        ndim, nz, ny, nx, w[0], w[1], w[2], lmbda.ctypes.data, sigma.ctypes.data,
+        tau.ctypes.data, theta.ctypes.data, iters, int(bool(p_is_zero)),
+        float(gamma_huber), int(flags), tab_host.data_ptr(), _p(tab), nbytes,
+        ctypes.addressof(slot), stream_ptr())
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_pd_weighted_run")
+    _wrote(xbar0, xbar1, x, p0, p1)
+    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
+    _weighted_table_keep(tab_host)
+    return int(slot.value)
+
+
+def pd_weighted_table(like, members, lmbda, sigma, tau, theta, p_is_zero, gamma_huber,
+                      flags):
+    """The device table of a weighted run's scalars ([iteration][member], the element
+    type of `like`) for pd_weighted_iter; schedules as in pd_weighted_run."""
+    members = int(members)
+    lmbda, sigma, tau, theta = _weighted_schedules(members, lmbda, sigma, tau, theta)
+    iters = int(sigma.shape[1])
+    tab_host, tab, nbytes = _weighted_table_buffers(like, members, iters)
+    _lib.check(_fn("pd_weighted_table", like)(
+        members, lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
+        theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber), int(flags),
+        tab_host.data_ptr(), _p(tab), nbytes, stream_ptr()), "nsol_pd_weighted_table")
+    _weighted_table_keep(tab_host)
+    return tab
+
+
+def pd_weighted_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, members, shape, w, tab,
+                     iteration, flags):
+    """One launch: iteration `iteration` of the table pd_weighted_table made.  p_in
+    is not read where the table says that p is zero, but must be given.  Returns
+    False when the library declined (nothing was launched)."""
+    members = int(members)
+    ndim, nz, ny, nx, bts, wts = _weighted_operands(x, xbar_in, xbar_out, bt, wt, p_in,
+                                                    p_out, members, shape)
+    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
+    if int(iteration) < 0 or tab.numel() < entry * members * (int(iteration) + 1):
+        raise ValueError("the table has no iteration %d for %d members" %
+                         (iteration, members))
+    rc = _fn("pd_weighted_iter", x)(
+        _p(xbar_in), _p(xbar_out), _p(x), _p(bt), bts, _p(wt), wts, _p(p_in), _p(p_out),
+        members, ndim, nz, ny, nx, w[0], w[1], w[2], _p(tab), int(iteration), int(flags),
+        stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pd_weighted_iter")
+    _wrote(xbar_out, x, p_out)
+    return True
 
 
 # ----------------------------------------------------------------- ADMM ----

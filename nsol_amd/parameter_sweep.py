@@ -14,7 +14,8 @@ the order the dictionary gives them (solver_parameter_study.py, _run).  Two
 execution forms, the same results and the same interface:
   stacked     a natively fused configuration (PrimalDualSolver.plan()): the
               observation is uploaded and scaled once and all members advance
-              together, ONE launch per iteration (nsol_pd_sweep_run_*), in
+              together, ONE launch per iteration (nsol_pd_sweep_run_*; with a
+              weighted data term nsol_pd_weighted_run_*, the weights shared), in
               groups that keep the state under ops.PD_SWEEP_GROUP_BYTES; the
               measures are taken on the device from each member's slice of the
               stacked iterate;
@@ -157,7 +158,7 @@ class PrimalDualSweep(object):
         declined (nothing has run then)."""
         import torch
         from .device import to_device
-        from .proximal_operators import scaled_data_on_device
+        from .proximal_operators import scaled_data_on_device, weights_on_device
         members, iters = self._members, self._iterations
         P = len(members)
         x0 = template._x0_device()
@@ -171,6 +172,8 @@ class PrimalDualSweep(object):
             sig[m], ta[m], th[m] = step_schedule(kw["alg_type"], float(kw["L2"]),
                                                  lmbda[m], iters)
         bt = scaled_data_on_device(plan["data"], plan["data_scale"], x0)
+        wt = weights_on_device(plan["weights"], x0) \
+            if plan["flags"] & ops.PD_DATA_WEIGHTED else None
         G = ops.sweep_group_size(P, n, dim, x0.element_size())
         x_all = torch.empty(P * n, dtype=x0.dtype, device=x0.device)
         x_all.view(P, n).copy_(x0)
@@ -203,10 +206,19 @@ class PrimalDualSweep(object):
             xb[0].view(g, n).copy_(x0)
             k = 0
             for i0, i1 in zip(bounds[:-1], bounds[1:]):
-                slot = ops.pd_sweep_run(
-                    xb[k], xb[1 - k], x, bt, pp[k], pp[1 - k], g, plan["shape"],
-                    plan["w"], lmbda[a:b], sig[a:b, i0:i1], ta[a:b, i0:i1],
-                    th[a:b, i0:i1], i0 == 0, plan["gamma"], plan["flags"])
+                if wt is not None:
+                    # a weighted data term: observation and weights shared by
+                    # the members, both at member stride 0 (nsol_pd_weighted_run_*)
+                    slot = ops.pd_weighted_run(
+                        xb[k], xb[1 - k], x, bt, wt, pp[k], pp[1 - k], g,
+                        plan["shape"], plan["w"], lmbda[a:b], sig[a:b, i0:i1],
+                        ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0, plan["gamma"],
+                        plan["flags"])
+                else:
+                    slot = ops.pd_sweep_run(
+                        xb[k], xb[1 - k], x, bt, pp[k], pp[1 - k], g, plan["shape"],
+                        plan["w"], lmbda[a:b], sig[a:b, i0:i1], ta[a:b, i0:i1],
+                        th[a:b, i0:i1], i0 == 0, plan["gamma"], plan["flags"])
                 if slot is None:
                     if first_call:
                         return False

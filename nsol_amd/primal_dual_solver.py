@@ -6,7 +6,10 @@ nsol/primal_dual_solver.py:26-403).
           in {prox_tv_conj, prox_huber_conj} or their isotropic forms
           {prox_tv_conj_isotropic, prox_huber_conj_isotropic} (one single-pass
           kernel per iteration, k_pd_fused_iso), prox_f in {prox_ell1_denoising,
-          prox_ell2_denoising} -- recognised THROUGH caller-side lambdas with
+          prox_ell2_denoising} or their per-voxel weighted forms
+          {prox_ell1_denoising_weighted, prox_ell2_denoising_weighted} (masks,
+          confidence maps: one single-pass kernel per iteration, k_pd_w, 48 bytes
+          per voxel instead of 44) -- recognised THROUGH caller-side lambdas with
           a symbolic probe; nsol_pd_run_* enqueues the whole run: three
           iterations per pass over memory on large 3-D volumes (11 words of
           HBM traffic per voxel for all three; bit-identical to one
@@ -26,7 +29,8 @@ import numpy as np
 from . import ops
 from .bridge import BridgedCallable
 from .device import is_device_tensor
-from .proximal_operators import scaled_data_on_device
+from .proximal_operators import (check_weights, scaled_data_on_device,
+                                 weights_on_device)
 from .solver import Solver
 from ._accessors import add_accessors
 from .symbolic import TauSym, trace_operator, trace_prox
@@ -146,7 +150,8 @@ class PrimalDualSolver(Solver):
             return None
         n = dual["n"]
         df = trace_prox(self._prox_f, n)
-        if df is None or df[0] not in ("prox_ell1", "prox_ell2") \
+        if df is None or df[0] not in ("prox_ell1", "prox_ell2", "prox_ell1_w",
+                                       "prox_ell2_w") \
                 or not isinstance(df[3], TauSym):
             return None
         data = df[1]
@@ -154,10 +159,16 @@ class PrimalDualSolver(Solver):
         if dsize != n:
             return None
         flags = dual["flags"]
-        flags |= ops.PD_DATA_L1 if df[0] == "prox_ell1" else ops.PD_DATA_L2
-        return dict(shape=dual["shape"], w=dual["w"], dim=dual["dim"],
+        flags |= ops.PD_DATA_L1 if df[0].startswith("prox_ell1") else ops.PD_DATA_L2
+        plan = dict(shape=dual["shape"], w=dual["w"], dim=dual["dim"],
                     flags=flags, gamma=dual["gamma"], data=data,
                     data_scale=df[2])
+        if df[0].endswith("_w"):
+            # wrong weights are an error, not a reason for a slower path
+            check_weights(df[4], n)
+            plan["flags"] |= ops.PD_DATA_WEIGHTED
+            plan["weights"] = df[4]
+        return plan
 
     def _run(self):
         self._points = self._observe_start(self._iterations)
@@ -180,6 +191,9 @@ class PrimalDualSolver(Solver):
         p = [torch.empty(plan["dim"] * n, dtype=x.dtype, device=x.device)
              for _ in range(2)]
         bt = scaled_data_on_device(plan["data"], plan["data_scale"], x)
+        if plan["flags"] & ops.PD_DATA_WEIGHTED:
+            self._run_weighted(plan, lmbda, sig, ta, th, x, xbar, p, bt)
+            return
         # a device-mode observer (observer.py) keeps the multi-iteration kernels
         # and the row pitch: the run is enqueued in chunks between its
         # observation points, nsol_observe_* reads the pitched x as it is
@@ -225,6 +239,46 @@ class PrimalDualSolver(Solver):
                               None if i == 0 else p[k], p[1 - k],
                               plan["shape"], plan["w"], sig[i], hden, ta[i],
                               ta[i] * lmbda, th[i], plan["flags"])
+            self._x = x
+            self._observe_iteration(i + 1, x)
+        self._x = x
+
+    def _run_weighted(self, plan, lmbda, sig, ta, th, x, xbar, p, bt):
+        """The fused run with a weighted data term (k_pd_w, nsol_pdw.hip): one
+        iteration per launch, contiguous arrays -- no row pitch, no multi-iteration
+        kernels and never the persistent kernel, which have no weighted form.  The
+        weights are converted to the working dtype once per run."""
+        wt = weights_on_device(plan["weights"], x)
+        shape, w, flags = plan["shape"], plan["w"], plan["flags"]
+        unobserved = self._observer is None or self._points is not None
+        if unobserved and not self._verbose:
+            # the whole run, or the stretches between a device-mode observer's points
+            pts = self._points
+            bounds = [0, self._iterations] if pts is None else pts
+            k = 0
+            for a, b in zip(bounds[:-1], bounds[1:]):
+                slot = ops.pd_weighted_run(
+                    xbar[k], xbar[1 - k], x, bt, wt, p[k], p[1 - k], 1, shape, w,
+                    [lmbda], sig[a:b], ta[a:b], th[a:b], a == 0, plan["gamma"], flags)
+                if slot is None:
+                    raise ValueError("nsol_pd_weighted_run does not take a volume "
+                                     "of shape %r" % (tuple(shape),))
+                k = k if slot == 0 else 1 - k
+                if pts is not None:
+                    self._observe_at(b, x, None)
+            self._x = x
+            return
+        tab = ops.pd_weighted_table(x, 1, [lmbda], sig, ta, th, True, plan["gamma"],
+                                    flags)
+        for i in range(self._iterations):      # observed / verbose: stepwise
+            if self._verbose:
+                print("Primal-Dual iteration %d/%d" % (i + 1,
+                                                       self._iterations))
+            k = i & 1
+            if not ops.pd_weighted_iter(xbar[k], xbar[1 - k], x, bt, wt, p[k],
+                                        p[1 - k], 1, shape, w, tab, i, flags):
+                raise ValueError("nsol_pd_weighted_iter does not take a volume of "
+                                 "shape %r" % (tuple(shape),))
             self._x = x
             self._observe_iteration(i + 1, x)
         self._x = x

@@ -68,6 +68,92 @@ def scaled_tensor(src, x_scale, dtype):
     return val
 
 
+# validated weights of the weighted data terms on the device, per working dtype
+_wt_cache = []
+_caches._registered.append(_wt_cache)
+_wt_dev_cache = _caches.DataCache(4)
+
+
+def check_weights(weights, n):
+    """ValueError unless `weights` holds n finite, non-negative real (or bool)
+    values.  Device tensors are checked on the device (one reduction, one
+    synchronisation)."""
+    if is_device_tensor(weights):
+        size = int(weights.numel())
+        kind = "b" if str(weights.dtype) == "torch.bool" else \
+            ("c" if weights.is_complex() else "f")
+    else:
+        weights = np.asarray(weights)
+        size, kind = int(weights.size), weights.dtype.kind
+    if kind not in "biuf":
+        raise ValueError("weights must be real or bool, not %s" % (weights.dtype,))
+    if size != int(n):
+        raise ValueError("weights hold %d values for %d voxels" % (size, int(n)))
+    if size == 0 or kind == "b":
+        return
+    if is_device_tensor(weights):
+        import torch
+        flat = weights.contiguous().view(-1)
+        if flat.dtype not in (torch.float32, torch.float64):
+            flat = flat.to(torch.float64)
+        lo, _, _, _, bad = ops.pair_range(flat, flat)
+    else:
+        bad = int(weights.size - np.count_nonzero(np.isfinite(weights)))
+        lo = float(np.min(weights)) if not bad else 0.
+    if bad:
+        raise ValueError("weights must be finite (%d are not)" % bad)
+    if lo < 0:
+        raise ValueError("weights must not be negative (minimum %g)" % lo)
+
+
+def weights_on_device(weights, like):
+    """The weights (NumPy array or device tensor of any real or bool dtype), checked
+    (check_weights) and converted once to a flat device tensor with the dtype of
+    `like`; remembered like the scaled observation while the caller's array is
+    unchanged."""
+    n = int(weights.numel() if is_device_tensor(weights) else np.size(weights))
+    if is_device_tensor(weights):
+        val = _wt_dev_cache.lookup((weights,), str(like.dtype))
+        if val is None:
+            check_weights(weights, n)
+            flat = weights.to(like.dtype).contiguous().view(-1)
+            # (the caller's own memory is not kept alive by the cache: only that
+            # it has been checked is remembered)
+            own = flat.data_ptr() == weights.data_ptr()
+            val = _wt_dev_cache.store((weights,), str(like.dtype),
+                                      True if own else flat)
+        return weights.contiguous().view(-1) if val is True else val
+    arr = np.asarray(weights)
+    key = (id(weights), arr.__array_interface__["data"][0], arr.size, str(arr.dtype),
+           like.dtype, like.device.index, _fingerprint(arr))
+    for k, ref, val in _wt_cache:
+        if k == key and ref is weights:
+            return val
+    check_weights(arr, n)
+    dt = np.float32 if "32" in str(like.dtype) else np.float64
+    wt = to_device(arr.reshape(-1).astype(dt), dt)
+    _wt_cache.append((key, weights, wt))
+    del _wt_cache[:-4]
+    return wt
+
+
+def _weighted(x, tau, x0, weights, x_scale, op, name):
+    if isinstance(x, Sym):
+        # (the probe is answered unchecked: PrimalDualSolver.plan() checks the
+        # weights, where a ValueError reaches the caller instead of the tracer)
+        return _elementwise(x, None, (name, x0, float(x_scale), tau, weights))
+    n = int(x0.numel() if is_device_tensor(x0) else np.size(x0))
+    size = int(x.numel() if is_device_tensor(x) else np.size(x))
+    if size != n:
+        raise ValueError("x holds %d values, x0 %d" % (size, n))
+    check = int(weights.numel() if is_device_tensor(weights) else np.size(weights))
+    if check != n:
+        raise ValueError("weights hold %d values for %d voxels" % (check, n))
+    return _elementwise(
+        x, lambda d: op(d, scaled_data_on_device(x0, x_scale, d),
+                        weights_on_device(weights, d), tau), None)
+
+
 def _elementwise(x, fn, desc):
     if isinstance(x, Sym):
         if x.desc is not None:
@@ -153,6 +239,24 @@ class ProximalOperators(object):
             x, lambda d: ops.prox_ell2(
                 d, scaled_data_on_device(x0, x_scale, d), tau),
             ("prox_ell2", x0, float(x_scale), tau))
+
+    @staticmethod
+    def prox_ell1_denoising_weighted(x, tau, x0, weights, x_scale=1.):
+        """prox of tau * lambda sum_i w_i |x_i - x0_i|: the soft threshold of
+        proximal_operators.py:95-98 with the per-voxel threshold tau * w_i.
+        weights: NumPy array or device tensor of any real or bool dtype with x0's
+        size, finite and >= 0 (ValueError otherwise), not scaled by x_scale.  Where
+        w_i == 0 the result is x_i exactly, whatever x0 holds there."""
+        return _weighted(x, tau, x0, weights, x_scale, ops.prox_ell1_weighted,
+                         "prox_ell1_w")
+
+    @staticmethod
+    def prox_ell2_denoising_weighted(x, tau, x0, weights, x_scale=1.):
+        """prox of tau * lambda / 2 sum_i w_i (x_i - x0_i)^2:
+        (x + tau w x0 / x_scale) / (1 + tau w), proximal_operators.py:117-120 with
+        per-voxel weights (see prox_ell1_denoising_weighted)."""
+        return _weighted(x, tau, x0, weights, x_scale, ops.prox_ell2_weighted,
+                         "prox_ell2_w")
 
     @staticmethod
     def prox_tv_conj(x, sigma):

@@ -13,7 +13,8 @@ dimension, flags, Huber gamma, dtype, device, iteration count and observation
 points form a STACK: their observations and start vectors are uploaded together
 (one page-locked (P, n) array each), scaled by every member's own x_scale in one
 launch each (ops.scale_rows) and advanced together, ONE launch per iteration
-(nsol_pd_batch_run_*), in groups that keep the state under
+(nsol_pd_batch_run_*; with a weighted data term nsol_pd_weighted_run_*, every
+member bringing its own weights), in groups that keep the state under
 ops.PD_BATCH_GROUP_BYTES.  The data, x_scale, alpha, alg_type and L2 may differ
 from member to member.  Every member's result is bit-identical to its own run().
 
@@ -40,7 +41,8 @@ def _dev_index(v):
 def member_key(solver, plan):
     """What the members of one stack share, or None for a solver that runs on its
     own: (shape, w, dim, flags, gamma, dtype, iterations, observation points,
-    device of the data, device of x0)."""
+    device of the data, device of x0, device of the weights).  The flags carry
+    ops.PD_DATA_WEIGHTED: a weighted and an unweighted solver never share a stack."""
     if plan is None:
         return None
     iters = int(solver._iterations)
@@ -57,7 +59,8 @@ def member_key(solver, plan):
     return (tuple(int(s) for s in plan["shape"]),
             tuple(float(v) for v in plan["w"]), int(plan["dim"]),
             int(plan["flags"]), float(plan["gamma"]), np.dtype(solver._dtype).name,
-            iters, points, ("data", _dev_index(plan["data"])), ("x0", x0_dev))
+            iters, points, ("data", _dev_index(plan["data"])), ("x0", x0_dev),
+            ("weights", _dev_index(plan.get("weights"))))
 
 
 def plan_stacks(keys):
@@ -205,7 +208,20 @@ class PrimalDualBatch(object):
             raw = self._upload_rows([s._x0_host for s in solvers], solvers[0]._dtype)
             x_all = ops.scale_rows(raw, self._scales([s._x_scale for s in solvers]),
                                    P, divide=True).view(-1)
-        G = ops.batch_group_size(P, n, dim, x_all.element_size())
+        # ---- a weighted data term: every member's own weights, checked by plan(),
+        # converted to the working dtype and uploaded once like the observations
+        wt = None
+        if plan["flags"] & ops.PD_DATA_WEIGHTED:
+            wts = [plans[i]["weights"] for i in idx]
+            if is_device_tensor(wts[0]):
+                wt = torch.empty(P * n, dtype=td, device=dev)
+                for m, v in enumerate(wts):
+                    wt[m * n:(m + 1) * n].copy_(v.reshape(-1))
+            else:
+                wt = self._upload_rows(wts, solvers[0]._dtype).view(-1)
+            G = ops.weighted_batch_group_size(P, n, dim, x_all.element_size())
+        else:
+            G = ops.batch_group_size(P, n, dim, x_all.element_size())
         xbar = [torch.empty(G * n, dtype=td, device=dev) for _ in range(2)]
         p = [torch.empty(G * dim * n, dtype=td, device=dev) for _ in range(2)]
         # ---- device-mode observers share their points (member_key): the run is
@@ -222,11 +238,18 @@ class PrimalDualBatch(object):
             xb[0].copy_(x)
             k = 0
             for i0, i1 in zip(bounds[:-1], bounds[1:]):
-                slot = ops.pd_batch_run(
-                    xb[k], xb[1 - k], x, bt[a * n:b * n], pp[k], pp[1 - k], g,
-                    plan["shape"], plan["w"], lmbda[a:b], sig[a:b, i0:i1],
-                    ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0, plan["gamma"],
-                    plan["flags"])
+                if wt is not None:
+                    slot = ops.pd_weighted_run(
+                        xb[k], xb[1 - k], x, bt[a * n:b * n], wt[a * n:b * n], pp[k],
+                        pp[1 - k], g, plan["shape"], plan["w"], lmbda[a:b],
+                        sig[a:b, i0:i1], ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0,
+                        plan["gamma"], plan["flags"])
+                else:
+                    slot = ops.pd_batch_run(
+                        xb[k], xb[1 - k], x, bt[a * n:b * n], pp[k], pp[1 - k], g,
+                        plan["shape"], plan["w"], lmbda[a:b], sig[a:b, i0:i1],
+                        ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0, plan["gamma"],
+                        plan["flags"])
                 if slot is None:
                     if first_call:
                         return None
