@@ -799,6 +799,53 @@ int nsol_pd_weighted_run_f64(double *xbar0, double *xbar1, double *x, const doub
     void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * Stopping rule of the primal-dual solver (nsol_pdc.hip): how much one iteration
+ * changed the iterates, as four float64 sums in row[0..3] (device):
+ *   row[0] = sum (x_new - x_old)^2    row[1] = sum x_new^2      over the n voxels
+ *   row[2] = sum (p_new - p_old)^2    row[3] = sum p_new^2      over ndim * n values
+ * Every term is formed in float64 from the stored values, ((double)new - (double)old)^2,
+ * which is exact for float32 inputs.  The relative changes are
+ * r_x = sqrt(row[0] / row[1]) and r_p = sqrt(row[2] / row[3]).  Reduced per wave, per
+ * workgroup into ws, then by one closing workgroup in a fixed order: no atomics, the
+ * same input gives the same bits on every run.  The row is written on `stream`; the
+ * entries do not synchronise.
+ *
+ * nsol_pd_check_iter_*: ONE iteration as nsol_pd_fused_iter_* (flags without
+ * NSOL_PD_DATA_WEIGHTED, wt = NULL) or as nsol_pd_weighted_iter_* with one member
+ * (flags with it, wt the n weights) -- xbar_out, x and p_out are bit-identical to
+ * theirs -- and the sums of that iteration beside it, at no extra memory traffic.
+ * p_in = NULL: p is zero (the first iteration).  sigma, hden = 1 + sigma * gamma_huber
+ * (1 for TV), tau, tl = tau * lambda, theta as for nsol_pd_fused_iter_*;
+ * NSOL_PD_REG_ISOTROPIC is taken.  Contiguous volumes only.
+ * ws: caller-owned device scratch of ws_doubles doubles, at least
+ * nsol_pd_check_ws_doubles(elem_size, ...) for the geometry (-1: a geometry the
+ * kernels do not take); NSOL_EINVAL when it is too small.  Returns -2, nothing
+ * launched, for a geometry the kernels do not take (bad extents, more than 2^31
+ * voxels).
+ *
+ * nsol_pd_change_*: the same sums from arrays in memory, for loops of separate
+ * kernels: x_old, x_new of n elements, p_new of np = ndim * n, p_old of np or NULL
+ * (p counts as zero).  ws: at least 4 doubles; 4 * 4096 lets it use its whole grid. */
+int64_t nsol_pd_check_ws_doubles(int elem_size, int ndim, int64_t nz, int64_t ny,
+                                 int64_t nx);
+int nsol_pd_check_iter_f32(const float *xbar_in, float *xbar_out, float *x, const float *bt,
+    const float *wt, const float *p_in, float *p_out, int ndim, int64_t nz, int64_t ny,
+    int64_t nx, double wx, double wy, double wz, double sigma, double hden, double tau,
+    double tl, double theta, int flags, double *ws, int64_t ws_doubles, double *row,
+    void *stream);
+int nsol_pd_check_iter_f64(const double *xbar_in, double *xbar_out, double *x, const double *bt,
+    const double *wt, const double *p_in, double *p_out, int ndim, int64_t nz, int64_t ny,
+    int64_t nx, double wx, double wy, double wz, double sigma, double hden, double tau,
+    double tl, double theta, int flags, double *ws, int64_t ws_doubles, double *row,
+    void *stream);
+int nsol_pd_change_f32(const float *x_old, const float *x_new, int64_t n, const float *p_old,
+    const float *p_new, int64_t np, double *ws, int64_t ws_doubles, double *row,
+    void *stream);
+int nsol_pd_change_f64(const double *x_old, const double *x_new, int64_t n,
+    const double *p_old, const double *p_new, int64_t np, double *ws, int64_t ws_doubles,
+    double *row, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

@@ -6,6 +6,10 @@ deconvolution_solver_parameter_study_interface.py:217-325, without plotting).
     python -m nsol_amd.application.run_deconvolution --observation blurred.png \\
         --result out.png --blur 2 --reconstruction-type TVL2 --solver ADMM \\
         [--reference gt.png] [--measures PSNR RMSE SSIM NCC NMI]
+        [--tolerance 1e-3 [--check-every 10]]
+
+--solver PD takes --tolerance T / --check-every K, the stopping rule of
+PrimalDualSolver (see run_denoising); the iterations actually done are printed.
 
 With --reference, the measures are evaluated through an Observer on the flat
 iterates against the flat reference (as run_denoising does and as the
@@ -25,13 +29,14 @@ from .. import data_writer as dw
 from .. import observer as Observer
 from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
+from .run_denoising import last_observed, print_stop
 
 
 def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  tv_solver="PD", alpha=0.01, iterations=10, iter_max=10,
                  rho=0.1, minimizer="lsmr", data_loss="linear",
                  data_loss_scale=1., L2=8, verbose=0, dtype=None,
-                 isotropic=False):
+                 tolerance=None, check_every=10, isotropic=False):
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -82,7 +87,8 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                                    B_conj=D_adj_1D, L2=L2, alpha=alpha,
                                    x0=x0, iterations=iterations,
                                    x_scale=x_scale, verbose=verbose,
-                                   dtype=dtype)
+                                   dtype=dtype, tolerance=tolerance,
+                                   check_every=check_every)
     raise ValueError("Reconstruction type '%s' not known" %
                      reconstruction_type)
 
@@ -123,7 +129,23 @@ def main(argv=None):
                     help="not supported here (see run_denoising)")
     ap.add_argument("--weights", default=None, metavar="FILE",
                     help="not supported here (see run_denoising)")
+    ap.add_argument("--tolerance", type=float, default=None, metavar="T",
+                    help="--solver PD, TVL2 / HuberL2: stop once the relative change "
+                         "of the primal and of the dual iterate in one iteration is "
+                         "<= T (default: run all --iterations)")
+    ap.add_argument("--check-every", type=int, default=10, metavar="K",
+                    help="with --tolerance: evaluate the change every K iterations "
+                         "and at the last")
     args = ap.parse_args(argv)
+    primal_dual = args.solver == "PD" and \
+        args.reconstruction_type in ("TVL2", "HuberL2")
+    if args.tolerance is not None and not primal_dual:
+        ap.error("--tolerance is the stopping rule of the primal-dual solver "
+                 "(--solver PD with TVL2 or HuberL2)")
+    if args.tolerance is not None and not args.tolerance >= 0:
+        ap.error("--tolerance must be >= 0")
+    if args.check_every < 1:
+        ap.error("--check-every must be >= 1")
     if args.mask is not None or args.weights is not None:
         ap.error("--mask / --weights are options of run_denoising: the weighted "
                  "data term is a prox of the denoising problem, while "
@@ -147,7 +169,8 @@ def main(argv=None):
             observed_nda, spacing, args.blur, args.reconstruction_type,
             args.solver, alpha, args.iterations, args.iter_max, args.rho,
             args.minimizer, args.data_loss, args.data_loss_scale, args.L2,
-            args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic)
+            args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic,
+            tolerance=args.tolerance, check_every=args.check_every)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \
@@ -161,10 +184,12 @@ def main(argv=None):
         recon = np.array(solver.get_x().reshape(*observed_nda.shape))
         print("%s alpha=%g: %s" % (args.reconstruction_type, alpha,
                                    solver.get_computational_time()))
+        if args.tolerance is not None:
+            print_stop(solver, args.iterations)
         if obs is not None:
             obs.compute_measures()
             for m, vals in obs.get_measures().items():
-                print("  %s: %.6g -> %.6g" % (m, vals[0], vals[-1]))
+                print("  %s: %.6g -> %.6g" % (m, vals[0], last_observed(vals)))
         dw.DataWriter(recon, args.result, info).write_data()
     return 0
 

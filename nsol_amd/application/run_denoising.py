@@ -6,6 +6,14 @@ without plotting).
         --result out.nii.gz --reconstruction-type TVL2 --alpha 0.03 \\
         --iterations 50 [--reference gt.nii.gz] [--L2 8] [--dtype float32]
         [--isotropic] [--mask mask.nii.gz | --weights w.nii.gz]
+        [--tolerance 1e-3 [--check-every 10]]
+
+--tolerance T: stop before --iterations once the iterates have stopped changing --
+max(r_x, r_p) <= T with r the relative change of the primal and of the dual iterate
+in one iteration, evaluated every --check-every iterations and at the last
+(PrimalDualSolver); the iterations actually done are printed.  Tolerances below
+about 1e-6 are not met in float32.  Several --alpha and --slice-wise then run their
+members one after the other, each to its own stopping iteration.
 
 --isotropic: the regulariser is the isotropic TV / Huber norm -- the per-voxel
 vector norm that PriorMeasures reports and ADMM minimises -- instead of the
@@ -101,10 +109,10 @@ def wiring(observed_nda, reconstruction_type, isotropic=False, weights=None):
 
 def build_solver(observed_nda, reconstruction_type, alpha, iterations, L2=8,
                  verbose=0, dtype=None, alg_type="ALG2", weights=None,
-                 isotropic=False):
+                 tolerance=None, check_every=10, isotropic=False):
     return pd.PrimalDualSolver(
         L2=L2, alpha=alpha, iterations=iterations, verbose=verbose,
-        alg_type=alg_type, dtype=dtype,
+        alg_type=alg_type, dtype=dtype, tolerance=tolerance, check_every=check_every,
         **wiring(observed_nda, reconstruction_type, isotropic, weights))
 
 
@@ -140,7 +148,8 @@ def run_sweep(args, observed_nda, x_ref, reader, weights=None):
     sweep = PrimalDualSweep(
         L2=args.L2, parameters={"alpha": list(args.alpha)},
         iterations=args.iterations, alg_type=args.alg_type,
-        dtype=np.dtype(args.dtype).type,
+        dtype=np.dtype(args.dtype).type, tolerance=args.tolerance,
+        check_every=args.check_every,
         **wiring(observed_nda, args.reconstruction_type, args.isotropic, weights))
     if x_ref is not None:
         sweep.set_measures({
@@ -155,8 +164,11 @@ def run_sweep(args, observed_nda, x_ref, reader, weights=None):
         print("%s alpha=%g: %d iterations in %s (%s)" % (
             args.reconstruction_type, alpha, args.iterations,
             sweep.get_computational_time(), sweep.get_execution()))
+        if args.tolerance is not None:
+            print("  stopped after %d of %d iterations" % (
+                sweep.get_iterations_done()[k], args.iterations))
         for m, vals in measures.items():
-            print("  %s: %.6g -> %.6g" % (m, vals[k, 0], vals[k, -1]))
+            print("  %s: %.6g -> %.6g" % (m, vals[k, 0], last_observed(vals[k])))
         if args.result is not None or args.result_dir is not None:
             recon = np.array(sweep.get_x(k).reshape(*observed_nda.shape))
         if args.result is not None:
@@ -181,6 +193,22 @@ def run_sweep(args, observed_nda, x_ref, reader, weights=None):
     return 0
 
 
+def last_observed(vals):
+    """The last value a measure took: a run that a tolerance stopped leaves the
+    observation points behind its stop empty (NaN) in a device-mode observer."""
+    vals = np.asarray(vals, dtype=np.float64)
+    seen = np.flatnonzero(~np.isnan(vals))
+    return vals[seen[-1]] if seen.size else vals[-1]
+
+
+def print_stop(solver, iterations):
+    """The line a run with --tolerance adds: the iterations actually done."""
+    changes = solver.get_changes()
+    print("  stopped after %d of %d iterations (%s%s)" % (
+        solver.get_iterations_done(), iterations, solver.get_stop_reason(),
+        "; last change %.3g" % max(changes[-1, 1:]) if len(changes) else ""))
+
+
 def classify_slices(observed_nda, weights=None):
     """(indices of the slices to solve, indices copied through unchanged): a slice
     whose maximum is not positive has no x_scale to divide by (wiring()); with
@@ -203,7 +231,8 @@ def run_slice_wise(args, observed_nda, x_ref, reader, weights=None):
                             args.alpha[0], args.iterations, L2=args.L2,
                             dtype=np.dtype(args.dtype).type,
                             alg_type=args.alg_type, isotropic=args.isotropic,
-                            weights=None if weights is None else weights[k])
+                            weights=None if weights is None else weights[k],
+                            tolerance=args.tolerance, check_every=args.check_every)
                for k in solve]
     recon = np.array(observed_nda, dtype=np.float64)
     execution = []
@@ -222,6 +251,10 @@ def run_slice_wise(args, observed_nda, x_ref, reader, weights=None):
               args.reconstruction_type, args.alpha[0], args.iterations, took,
               execution.count("stacked"), len(copy),
               execution.count("sequential")))
+    if args.tolerance is not None and solvers:
+        done = [s.get_iterations_done() for s in solvers]
+        print("  stopped after %d to %d of %d iterations" % (
+            min(done), max(done), args.iterations))
     if x_ref is not None:
         flat = recon.flatten()
         for m in args.measures:
@@ -275,7 +308,18 @@ def main(argv=None):
     wgroup.add_argument("--weights", default=None, metavar="FILE",
                         help="image of the observation's shape: per-voxel weights "
                              "of the data term, finite and >= 0, taken as they are")
+    ap.add_argument("--tolerance", type=float, default=None, metavar="T",
+                    help="stop once the relative change of the primal and of the "
+                         "dual iterate in one iteration is <= T (default: run all "
+                         "--iterations); not met below about 1e-6 in float32")
+    ap.add_argument("--check-every", type=int, default=10, metavar="K",
+                    help="with --tolerance: evaluate the change every K iterations "
+                         "and at the last")
     args = ap.parse_args(argv)
+    if args.tolerance is not None and not args.tolerance >= 0:
+        ap.error("--tolerance must be >= 0")
+    if args.check_every < 1:
+        ap.error("--check-every must be >= 1")
     if args.slice_wise and len(args.alpha) > 1:
         ap.error("--slice-wise takes a single --alpha")
     if args.slice_wise and args.observe_every is not None:
@@ -314,7 +358,9 @@ def main(argv=None):
                               verbose=args.verbose,
                               dtype=np.dtype(args.dtype).type,
                               alg_type=args.alg_type,
-                              isotropic=args.isotropic, weights=weights)
+                              isotropic=args.isotropic, weights=weights,
+                              tolerance=args.tolerance,
+                              check_every=args.check_every)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \
@@ -329,10 +375,12 @@ def main(argv=None):
         print("%s alpha=%g: %d iterations in %s (%s)" % (
             args.reconstruction_type, alpha, args.iterations,
             solver.get_computational_time(), solver.get_execution()))
+        if args.tolerance is not None:
+            print_stop(solver, args.iterations)
         if obs is not None:
             obs.compute_measures()
             for m, vals in obs.get_measures().items():
-                print("  %s: %.6g -> %.6g" % (m, vals[0], vals[-1]))
+                print("  %s: %.6g -> %.6g" % (m, vals[0], last_observed(vals)))
         if args.result is not None:
             dw.DataWriter(recon, args.result,
                           reader.get_image_sitk()).write_data()

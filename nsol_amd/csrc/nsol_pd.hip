@@ -320,6 +320,12 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
 
 }  // namespace
 
+namespace nsol {
+PdLaunchTune pd_current_tune() {
+  return PdLaunchTune{g_tune.zchunk, g_tune.ry, g_tune.xcd_map, g_tune.rag};
+}
+}  // namespace nsol
+
 extern "C" {
 
 /* tuning knobs for experiments: "pd_zchunk", "pd_ry", "pd_two_pass" */

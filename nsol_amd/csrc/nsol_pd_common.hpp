@@ -76,6 +76,18 @@ __device__ __forceinline__ void zero(T (&v)[V]) {
   for (int k = 0; k < V; ++k) v[k] = T(0);
 }
 
+// One term of the stopping rule's sums (nsol_pdc.hip): num += (new - old)^2 and
+// den += new^2, formed in float64 from the stored values -- exact for float32
+// inputs, so the float32 and float64 kernels add the same kind of summand and only
+// the order of the sums differs between the forms.
+template <typename T>
+__device__ __forceinline__ void chk_add(double &num, double &den, T old_v, T new_v) {
+  const double nv = (double)new_v;
+  const double d = nv - (double)old_v;
+  num += d * d;
+  den += nv * nv;
+}
+
 template <typename T>
 struct PdScalars {
   T sigma, hden, tau, tl, one_plus_tl, theta;
@@ -125,6 +137,8 @@ __device__ __forceinline__ T adj_term(T p, T p_prev, T w) {
 struct PdLaunchTune {
   int zchunk, ry, xcd_map, rag;
 };
+// the knobs as they stand (nsol_pd.hip), for the checking kernel of nsol_pdc.hip
+PdLaunchTune pd_current_tune();
 // What nsol_pd.hip's entries call in the other units; each is instantiated for
 // float and double where it is defined.
 // One iteration through k_pd_fused_iso / the isotropic dual step of the two-pass

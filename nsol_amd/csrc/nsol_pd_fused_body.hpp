@@ -40,12 +40,18 @@ __device__ __forceinline__ bool pd_fused_block_tile(int bid, int ntx, int nty, i
 // aligned.  WGT: the data term carries per-voxel weights wt (nsol_pd_weighted.hpp),
 // one more row load per plane and prox_data_w in place of prox_data (k_pd_w,
 // nsol_pdw.hip); the unweighted kernels leave it off and are compiled as before.
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false>
+// CHK: the lane adds the four float64 sums of the stopping rule (chk_add,
+// nsol_pd_common.hpp) over the voxels it STORES -- not the elements behind a ragged
+// row's end, not the rows outside the volume, not the dual values it recomputes on
+// the lower halo -- to chk[0..3] (k_pd_check, nsol_pdc.hip); off by default, and the
+// other kernels are compiled as before.
+template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false,
+          bool CHK = false>
 __device__ __forceinline__ void pd_fused_tile(
     const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
     const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
     const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk,
-    const T *__restrict__ wt = nullptr) {
+    const T *__restrict__ wt = nullptr, double *chk = nullptr) {
   constexpr int LY = kWave / LX;
   constexpr int WAVES = kBlock / kWave;
   constexpr int TY = WAVES * LY * RY;
@@ -253,6 +259,16 @@ __device__ __forceinline__ void pd_fused_tile(
         if constexpr (NDIM >= 3) st(pout_z + o, pzn[r]);
         st(x + o, xo_new);
         st(xbar_out + o, xb_new);
+        if constexpr (CHK) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k)
+            if (k < nval) {
+              chk_add(chk[0], chk[1], xv[r][k], xo_new[k]);
+              chk_add(chk[2], chk[3], pxo[r][k], pxn[r][k]);
+              if constexpr (NDIM >= 2) chk_add(chk[2], chk[3], pyo[r][k], pyn[r][k]);
+              if constexpr (NDIM >= 3) chk_add(chk[2], chk[3], pzo[r][k], pzn[r][k]);
+            }
+        }
       }
       if constexpr (NDIM >= 3) {
 #pragma unroll

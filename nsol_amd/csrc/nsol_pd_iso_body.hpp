@@ -46,13 +46,14 @@ __device__ __forceinline__ void dual_project(T &q0, T &q1, T &q2, bool huber, T 
 }
 
 // One iteration on tile (tx, ty), z-chunk zc of one volume; arguments as
-// pd_fused_tile (WGT / wt included).
-template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false>
+// pd_fused_tile (WGT / wt and CHK / chk included).
+template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false,
+          bool CHK = false>
 __device__ __forceinline__ void pd_fused_iso_tile(
     const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
     const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
     const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk,
-    const T *__restrict__ wt = nullptr) {
+    const T *__restrict__ wt = nullptr, double *chk = nullptr) {
   constexpr int LY = kWave / LX;
   constexpr int WAVES = kBlock / kWave;
   constexpr int TY = WAVES * LY * RY;
@@ -101,9 +102,11 @@ __device__ __forceinline__ void pd_fused_iso_tile(
 
   // The projected dual vector of the lane's own voxels on the plane at offset o0
   // (its xbar in xa, the next plane's -- zeros behind the volume -- in xb).
+  // CHK and `count`: the old and new dual values of the voxels this plane stores go
+  // into the sums of the stopping rule (not the plane before a z chunk).
   auto dual_own = [&](int64_t o0, const T (&xa)[RY][VEC], const T (&xb)[RY][VEC],
-                      T (&px)[RY][VEC], T (&py)[RY][VEC],
-                      T (&pz)[RY][VEC]) __attribute__((always_inline)) {
+                      T (&px)[RY][VEC], T (&py)[RY][VEC], T (&pz)[RY][VEC],
+                      bool count) __attribute__((always_inline)) {
     T xdown[VEC];
     zero(xdown);
     if constexpr (NDIM >= 2) {
@@ -141,6 +144,13 @@ __device__ __forceinline__ void pd_fused_iso_tile(
         }
         if constexpr (NDIM >= 3) q2 = dual_q(pz[r][k], xb[r][k], c, G.wz, S.sigma);
         dual_project<NDIM>(q0, q1, q2, huber, S.hden);
+        if constexpr (CHK) {
+          if (count && rin[r] && k < nval) {
+            chk_add(chk[2], chk[3], px[r][k], q0);
+            if constexpr (NDIM >= 2) chk_add(chk[2], chk[3], py[r][k], q1);
+            if constexpr (NDIM >= 3) chk_add(chk[2], chk[3], pz[r][k], q2);
+          }
+        }
         px[r][k] = q0; py[r][k] = q1; pz[r][k] = q2;
       }
     }
@@ -165,7 +175,7 @@ __device__ __forceinline__ void pd_fused_iso_tile(
         zero(xm[r]);
         if (rin[r]) ld(xbar_in + off - G.sz + r * G.sy, xm[r]);
       }
-      dual_own(off - G.sz, xm, xc, tx_, ty_, pzprev);
+      dual_own(off - G.sz, xm, xc, tx_, ty_, pzprev, false);
     }
   }
 
@@ -188,7 +198,7 @@ __device__ __forceinline__ void pd_fused_iso_tile(
 
     // ---------------- dual update at the lane's own voxels ----------------
     T pxn[RY][VEC], pyn[RY][VEC], pzn[RY][VEC];
-    dual_own(off, xc, xn, pxn, pyn, pzn);
+    dual_own(off, xc, xn, pxn, pyn, pzn, true);
 
     // ---------------- new dual values on the lower halo -------------------
     // left of the wave patch: voxel (x0-1, y0+r, z), its x-difference against the
@@ -286,6 +296,11 @@ __device__ __forceinline__ void pd_fused_iso_tile(
         if constexpr (NDIM >= 3) st(pout_z + o, pzn[r]);
         st(x + o, xo_new);
         st(xbar_out + o, xb_new);
+        if constexpr (CHK) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k)
+            if (k < nval) chk_add(chk[0], chk[1], xv[r][k], xo_new[k]);
+        }
       }
       if constexpr (NDIM >= 3) {
 #pragma unroll

@@ -1,6 +1,6 @@
 // Host-side launch path of the kernels that do ONE Chambolle-Pock iteration in one
 // pass: k_pd_fused (nsol_pd.hip), k_pd_fused_iso (nsol_pdi.hip), the member-stacked
-// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip) and k_pd_w (nsol_pdw.hip).  They share the wave layout of
+// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip), k_pd_w (nsol_pdw.hip) and k_pd_check (nsol_pdc.hip).  They share the wave layout of
 // nsol_pd_fused_body.hpp -- a wave owns (LX*VEC) x (LY*RY) of an x-y tile and
 // marches along z -- so the rounding of the scalars, the grid, the automatic rows
 // per lane and the access form are chosen here, once.  A new kernel of the family
@@ -44,6 +44,9 @@ struct PdLaunchArgs {
   hipStream_t st = nullptr;
   const T *wt = nullptr;              // the weighted kernel's per-voxel weights and
   int64_t bt_stride = 0, wt_stride = 0;  // its member strides of bt / wt (0 or G.n)
+  double *chk_ws = nullptr;           // the checking kernel's partial sums (one per
+  int64_t chk_ws_doubles = 0;         // workgroup and sum) and the board row its
+  double *chk_row = nullptr;          // closing workgroup writes (nsol_pdc.hip)
 };
 
 struct PdGridPlan {

@@ -1734,6 +1734,91 @@ def pd_weighted_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, members, shape, 
     return True
 
 
+# ------------------------------------------------------ stopping rule ----
+# (nsol_pdc.hip; the rule itself is primal_dual_solver.py's)
+PD_CHECK_SUMS = 4
+
+
+def pd_check_launches():
+    """Calls of pd_check_iter so far (for tests and tools)."""
+    return _check_launches
+
+
+_check_launches = 0
+
+
+def pd_check_workspace(like, shape):
+    """The float64 device scratch pd_check_iter and pd_change need for a volume of
+    `shape` in the element type of `like` (nsol_pd_check_ws_doubles)."""
+    ndim, nz, ny, nx = dims3(shape)
+    need = int(_lib.load().nsol_pd_check_ws_doubles(int(like.element_size()), ndim, nz,
+                                                    ny, nx))
+    if need < 0:
+        raise ValueError("nsol_pd_check does not take a volume of shape %r" %
+                         (tuple(shape),))
+    return torch.empty(need, dtype=torch.float64, device=like.device)
+
+
+def _check_row(ws, row):
+    _chk(ws)
+    _chk(row)
+    if ws.dtype != torch.float64 or row.dtype != torch.float64 or \
+            row.numel() < PD_CHECK_SUMS or ws.numel() < PD_CHECK_SUMS:
+        raise ValueError("ws, row: float64 device tensors of at least %d elements" %
+                         PD_CHECK_SUMS)
+
+
+def pd_check_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, shape, w, sigma, hden, tau,
+                  tl, theta, flags, ws, row):
+    """One iteration as pd_fused_iter (wt None) or as pd_weighted_iter with one member
+    (wt the weights, flags with PD_DATA_WEIGHTED) -- the same bits in xbar_out, x and
+    p_out -- and the four sums of the stopping rule, {sum dx^2, sum x^2, sum dp^2,
+    sum p^2} of that iteration, in row[0:4] (float64, device).  p_in None: p is zero.
+    ws: pd_check_workspace().  Returns False when the library declined (nothing was
+    launched).  Does not synchronise."""
+    global _check_launches
+    ndim, nz, ny, nx = dims3(shape)
+    n = nz * ny * nx
+    _same(x, xbar_in, xbar_out, bt)
+    _chk(p_out)
+    _check_row(ws, row)
+    weighted = bool(int(flags) & PD_DATA_WEIGHTED)
+    if weighted != (wt is not None):
+        raise ValueError("weights go with PD_DATA_WEIGHTED, and only with it")
+    for t, size in ((wt, n), (p_in, ndim * n), (p_out, ndim * n)):
+        if t is not None and (_chk(t).dtype != x.dtype or t.numel() != size):
+            raise ValueError("operand mismatch: %s[%d] where %s[%d] is expected" %
+                             (str(t.dtype), t.numel(), str(x.dtype), size))
+    if x.numel() != n:
+        raise ValueError("x does not hold a volume of shape %r" % (tuple(shape),))
+    rc = _fn("pd_check_iter", x)(
+        _p(xbar_in), _p(xbar_out), _p(x), _p(bt), _p(wt), _p(p_in), _p(p_out), ndim, nz,
+        ny, nx, w[0], w[1], w[2], float(sigma), float(hden), float(tau), float(tl),
+        float(theta), int(flags), _p(ws), ws.numel(), _p(row), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pd_check_iter")
+    _wrote(xbar_out, x, p_out, row)
+    _check_launches += 1
+    return True
+
+
+def pd_change(x_old, x_new, p_old, p_new, ws, row):
+    """The four sums of the stopping rule from the iterates before and after an
+    iteration (p_old None: p was zero) into row[0:4]; for the loops of separate
+    kernels.  Does not synchronise."""
+    _same(x_new, x_old)
+    _chk(p_new)
+    _check_row(ws, row)
+    if p_new.dtype != x_new.dtype or (p_old is not None and (
+            _chk(p_old).dtype != p_new.dtype or p_old.numel() != p_new.numel())):
+        raise ValueError("operand mismatch between x and p, or p_old and p_new")
+    _lib.check(_fn("pd_change", x_new)(
+        _p(x_old), _p(x_new), x_new.numel(), _p(p_old), _p(p_new), p_new.numel(),
+        _p(ws), ws.numel(), _p(row), stream_ptr()), "nsol_pd_change")
+    return _wrote(row)
+
+
 # ----------------------------------------------------------------- ADMM ----
 def admm_vw_update(x, v, w_, c, rhs, shape, w, thr, rhs_scale, want_norm=False):
     """v, w_ and the next right-hand side rhs = rhs_scale * (v - w_ + c) from one

@@ -20,8 +20,9 @@ execution forms, the same results and the same interface:
               measures are taken on the device from each member's slice of the
               stacked iterate;
   sequential  anything else (foreign callables, deconvolution, members larger
-              than ops.PD_SWEEP_MAX_VOXELS, a geometry the library declines):
-              one PrimalDualSolver after the other.
+              than ops.PD_SWEEP_MAX_VOXELS, a geometry the library declines, a
+              `tolerance`: every member then stops at an iteration of its own,
+              get_iterations_done()): one PrimalDualSolver after the other.
 """
 import datetime
 import itertools
@@ -31,7 +32,8 @@ import numpy as np
 
 from . import ops
 from .observer import Observer
-from .primal_dual_solver import PrimalDualSolver, step_schedule
+from .primal_dual_solver import (PrimalDualSolver, checked_check_every,
+                                 checked_tolerance, step_schedule)
 
 PARAMETER_KEYS = ("alpha", "alg_type", "L2")
 
@@ -60,13 +62,18 @@ class PrimalDualSweep(object):
 
     def __init__(self, prox_f, prox_g_conj, B, B_conj, L2, x0, parameters,
                  iterations=50, x_scale=1., dtype=None, alpha=0.01,
-                 alg_type="ALG2"):
+                 alg_type="ALG2", tolerance=None, check_every=10):
         self._callables = dict(prox_f=prox_f, prox_g_conj=prox_g_conj, B=B,
                                B_conj=B_conj)
         self._x0 = x0
         self._defaults = dict(alpha=alpha, alg_type=alg_type, L2=L2)
         self._members = member_parameters(parameters)
         self._iterations = int(iterations)
+        # a tolerance (PrimalDualSolver's stopping rule): every member stops at an
+        # iteration of its own, so the members run one after the other
+        self._tolerance = checked_tolerance(tolerance)
+        self._check_every = checked_check_every(check_every)
+        self._iterations_done = None
         self._x_scale = float(x_scale)
         self._dtype = dtype
         self._functions = {}
@@ -104,7 +111,8 @@ class PrimalDualSweep(object):
         return PrimalDualSolver(
             x0=self._x0, iterations=self._iterations, x_scale=self._x_scale,
             dtype=self._dtype, alpha=kw["alpha"], alg_type=kw["alg_type"],
-            L2=kw["L2"], **self._callables)
+            L2=kw["L2"], tolerance=self._tolerance, check_every=self._check_every,
+            **self._callables)
 
     def _observer(self):
         if not self._functions:
@@ -125,7 +133,8 @@ class PrimalDualSweep(object):
         self._observers = []
         plan = template.plan()
         stacked = False
-        if plan is not None and self._iterations > 0 and \
+        self._iterations_done = None
+        if plan is not None and self._iterations > 0 and self._tolerance is None and \
                 int(np.prod(plan["shape"])) <= ops.PD_SWEEP_MAX_VOXELS:
             stacked = self._run_stacked(template, plan)
         if not stacked:
@@ -143,6 +152,7 @@ class PrimalDualSweep(object):
     def _run_sequential(self):
         """One solver after the other, as the command-line tools loop."""
         self._x_list, self._observers = [], []
+        self._iterations_done = []
         for member in self._members:
             solver = self._solver(member)
             obs = self._observer()
@@ -152,6 +162,7 @@ class PrimalDualSweep(object):
             solver.run()
             self._n = solver._x.numel()
             self._x_list.append(solver.get_x_device())
+            self._iterations_done.append(solver.get_iterations_done())
 
     def _run_stacked(self, template, plan):
         """All members in one launch per iteration; False when the library
@@ -234,6 +245,15 @@ class PrimalDualSweep(object):
         return True
 
     _group = None
+
+    def get_iterations_done(self):
+        """Iterations every member did in the last run(): fewer than `iterations`
+        where a tolerance stopped it (None before a run)."""
+        if self._execution is None:
+            return None
+        if self._iterations_done is None:
+            return [max(self._iterations, 0)] * len(self._members)
+        return list(self._iterations_done)
 
     def get_group_size(self):
         """Members per stacked launch of the last run (None: sequential)."""

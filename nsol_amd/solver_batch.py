@@ -19,7 +19,8 @@ ops.PD_BATCH_GROUP_BYTES.  The data, x_scale, alpha, alg_type and L2 may differ
 from member to member.  Every member's result is bit-identical to its own run().
 
 Everything else runs `solver.run()`, one after the other ("sequential"): a plan
-that is None (foreign callables, deconvolution), a stack of one, members above
+that is None (foreign callables, deconvolution), a solver with a tolerance (it stops
+at an iteration of its own), a stack of one, members above
 ops.PD_BATCH_MAX_VOXELS, a geometry the library declines on its first launch, an
 observer that keeps iterates on the host, a verbose solver.
 """
@@ -49,6 +50,8 @@ def member_key(solver, plan):
     n = int(np.prod(plan["shape"]))
     if iters < 1 or n > ops.PD_BATCH_MAX_VOXELS or solver._verbose:
         return None
+    if solver._tolerance is not None:
+        return None         # its own stopping iteration: no stacked form
     points = None
     obs = solver._observer
     if obs is not None:
@@ -137,6 +140,8 @@ class PrimalDualBatch(object):
                 s = solvers[i]
                 s._x = x_all[m * n:(m + 1) * n]
                 s._execution = "fused"
+                s._iterations_done, s._stop_reason = int(s._iterations), "iterations"
+                s._rule = None
                 s._computational_time = took
                 if s._observer is not None:
                     s._observer._finish()
