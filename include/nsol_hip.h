@@ -846,6 +846,49 @@ int nsol_pd_change_f64(const double *x_old, const double *x_new, int64_t n,
     double *row, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * Stacked runs that stop member by member (nsol_pdm.hip): ONE iteration of the
+ * ACTIVE members of a group of `members` stacked primal-dual runs in one launch.
+ * Layout, table and member strides as nsol_pd_weighted_iter_* (x, xbar member-major
+ * with n elements per member, p with ndim * n; bt and wt at a member stride of 0 or
+ * n; table entries of nsol_pd_sweep_entry_bytes(elem_size) bytes, [iteration][member],
+ * the row stride `members` whatever `active` is).
+ * map: DEVICE array of `active` int32 member indices, strictly increasing, each in
+ * [0, members); grid row r advances member map[r].  A member that is not in the map
+ * is not touched: no byte of its x, xbar, p or board row.  An entry outside
+ * [0, members) advances nothing.
+ * flags: NSOL_PD_REG_* | NSOL_PD_DATA_*, NSOL_PD_REG_ISOTROPIC taken;
+ * NSOL_PD_DATA_WEIGHTED set exactly when wt is given (wt = NULL, wt_stride ignored
+ * otherwise).  The arrays written for member m are bit-identical to
+ * nsol_pd_batch_iter_* / nsol_pd_weighted_iter_* and to a single run.
+ * rows = NULL: the plain form; ws is neither read nor written.
+ * rows != NULL: the checking form -- the four sums of the stopping rule above of
+ * every active member m in rows[4 m .. 4 m + 3] (device, float64; 4 * members
+ * doubles), reduced per wave, per workgroup into ws and by one closing workgroup per
+ * member in a fixed order: no atomics, the same input gives the same bits on every
+ * run.  ws: caller-owned device scratch, at least
+ * nsol_pd_stack_ws_doubles(elem_size, ..., members) doubles serve every `active`
+ * (-1: a geometry or member count the kernels do not take).
+ * Returns 0 with nothing launched for active = 0; -2, nothing launched, for what
+ * nsol_pd_batch_iter_* would decline for its geometry or member count; NSOL_EINVAL
+ * for a missing pointer, a stride that is neither 0 nor n, active > members or a
+ * workspace too small for 4 * active * workgroups doubles.
+ * nsol_pd_stack_launches: launches of k_pd_stack / k_pd_stack_iso this process has
+ * made. */
+int nsol_pd_stack_launches(void);
+int64_t nsol_pd_stack_ws_doubles(int elem_size, int ndim, int64_t nz, int64_t ny,
+                                 int64_t nx, int members);
+int nsol_pd_stack_iter_f32(const float *xbar_in, float *xbar_out, float *x, const float *bt,
+    int64_t bt_stride, const float *wt, int64_t wt_stride, const float *p_in, float *p_out,
+    int members, const int *map, int active, int ndim, int64_t nz, int64_t ny, int64_t nx,
+    double wx, double wy, double wz, const void *tab, int iteration, int flags, double *ws,
+    int64_t ws_doubles, double *rows, void *stream);
+int nsol_pd_stack_iter_f64(const double *xbar_in, double *xbar_out, double *x,
+    const double *bt, int64_t bt_stride, const double *wt, int64_t wt_stride,
+    const double *p_in, double *p_out, int members, const int *map, int active, int ndim,
+    int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz, const void *tab,
+    int iteration, int flags, double *ws, int64_t ws_doubles, double *rows, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

@@ -78,6 +78,8 @@ def load():
                                              c_int]
     lib.nsol_pd_check_ws_doubles.restype = c_i64
     lib.nsol_pd_check_ws_doubles.argtypes = [c_int, c_int, c_i64, c_i64, c_i64]
+    lib.nsol_pd_stack_ws_doubles.restype = c_i64
+    lib.nsol_pd_stack_ws_doubles.argtypes = [c_int, c_int, c_i64, c_i64, c_i64, c_int]
     lib.nsol_hip_set_param_conv.restype = c_int
     lib.nsol_hip_set_param_conv.argtypes = [ctypes.c_char_p, c_int]
     lib.nsol_hip_set_param_pd2.restype = c_int

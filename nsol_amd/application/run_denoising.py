@@ -12,8 +12,9 @@ without plotting).
 max(r_x, r_p) <= T with r the relative change of the primal and of the dual iterate
 in one iteration, evaluated every --check-every iterations and at the last
 (PrimalDualSolver); the iterations actually done are printed.  Tolerances below
-about 1e-6 are not met in float32.  Several --alpha and --slice-wise then run their
-members one after the other, each to its own stopping iteration.
+about 1e-6 are not met in float32.  Several --alpha and --slice-wise then keep their
+members stacked, one launch per iteration for those still running, and every member
+stops at its own iteration (stacked_stopping of PrimalDualSweep / PrimalDualBatch).
 
 --isotropic: the regulariser is the isotropic TV / Huber norm -- the per-voxel
 vector norm that PriorMeasures reports and ADMM minimises -- instead of the
@@ -149,7 +150,7 @@ def run_sweep(args, observed_nda, x_ref, reader, weights=None):
         L2=args.L2, parameters={"alpha": list(args.alpha)},
         iterations=args.iterations, alg_type=args.alg_type,
         dtype=np.dtype(args.dtype).type, tolerance=args.tolerance,
-        check_every=args.check_every,
+        check_every=args.check_every, stacked_stopping=args.tolerance is not None,
         **wiring(observed_nda, args.reconstruction_type, args.isotropic, weights))
     if x_ref is not None:
         sweep.set_measures({
@@ -237,7 +238,7 @@ def run_slice_wise(args, observed_nda, x_ref, reader, weights=None):
     recon = np.array(observed_nda, dtype=np.float64)
     execution = []
     if solvers:
-        batch = PrimalDualBatch(solvers)
+        batch = PrimalDualBatch(solvers, stacked_stopping=args.tolerance is not None)
         batch.run()
         execution = batch.get_execution()
         for k, solver in zip(solve, solvers):

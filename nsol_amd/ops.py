@@ -1819,6 +1819,83 @@ def pd_change(x_old, x_new, p_old, p_new, ws, row):
     return _wrote(row)
 
 
+# ------------------------------------- stacks that stop member by member ----
+# (nsol_pdm.hip; the host loop is nsol_amd/stacked_stopping.py)
+def pd_stack_launches():
+    """Launches of the member-mapped stacked kernels so far (for tests and tools)."""
+    return int(_lib.load().nsol_pd_stack_launches())
+
+
+def pd_stack_workspace(like, shape, members):
+    """The float64 device scratch pd_stack_iter's checking form needs for a group of
+    `members` volumes of `shape` in the element type of `like`, whatever number of
+    them is active (nsol_pd_stack_ws_doubles)."""
+    ndim, nz, ny, nx = dims3(shape)
+    need = int(_lib.load().nsol_pd_stack_ws_doubles(int(like.element_size()), ndim, nz,
+                                                    ny, nx, int(members)))
+    if need < 0:
+        raise ValueError("nsol_pd_stack does not take %d volumes of shape %r" %
+                         (int(members), tuple(shape)))
+    return torch.empty(need, dtype=torch.float64, device=like.device)
+
+
+def pd_stack_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, members, map, active,
+                  shape, w, tab, iteration, flags, ws=None, rows=None):
+    """One launch: iteration `iteration` of the table (pd_weighted_table's layout, row
+    stride `members`) for the `active` members map[0:active] of a group of `members`
+    stacked runs.  map: an int32 device tensor of strictly increasing member indices in
+    [0, members); a member that is not in it is not touched.  Layout as
+    pd_weighted_iter: bt and wt hold n elements (shared) or members * n (member-major);
+    wt goes with PD_DATA_WEIGHTED, and only with it.  rows None: the plain form.  rows
+    a float64 device tensor of 4 * members: the checking form, the four sums of the
+    stopping rule of every active member m in rows[4 m : 4 m + 4], ws from
+    pd_stack_workspace().  Returns False when the library declined (nothing was
+    launched).  Does not synchronise."""
+    members, active = int(members), int(active)
+    ndim, nz, ny, nx = dims3(shape)
+    n = nz * ny * nx
+    _same(x, xbar_in, xbar_out)
+    _same(p_in, p_out)
+    _chk(bt)
+    _chk(map)
+    weighted = bool(int(flags) & PD_DATA_WEIGHTED)
+    if weighted != (wt is not None):
+        raise ValueError("weights go with PD_DATA_WEIGHTED, and only with it")
+    if p_in.dtype != x.dtype or bt.dtype != x.dtype or members < 1 or \
+            x.numel() != members * n or p_in.numel() != members * ndim * n or \
+            bt.numel() not in (n, members * n) or (wt is not None and (
+                _chk(wt).dtype != x.dtype or wt.numel() not in (n, members * n))):
+        raise ValueError("operand mismatch: %d members of %d voxels against x[%d], "
+                         "bt[%d], p[%d]" % (members, n, x.numel(), bt.numel(),
+                                            p_in.numel()))
+    if map.dtype != torch.int32 or not 0 <= active <= members or map.numel() < active:
+        raise ValueError("map: an int32 device tensor of at least `active` entries, "
+                         "0 <= active <= members")
+    if rows is not None:
+        _chk(rows)
+        if ws is None or _chk(ws).dtype != torch.float64 or \
+                rows.dtype != torch.float64 or rows.numel() < PD_CHECK_SUMS * members:
+            raise ValueError("rows: a float64 device tensor of %d per member, with a "
+                             "float64 workspace" % PD_CHECK_SUMS)
+    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
+    if int(iteration) < 0 or tab.numel() < entry * members * (int(iteration) + 1):
+        raise ValueError("the table has no iteration %d for %d members" %
+                         (iteration, members))
+    bts = 0 if bt.numel() == n else n
+    wts = 0 if wt is None or wt.numel() == n else n
+    rc = _fn("pd_stack_iter", x)(
+        _p(xbar_in), _p(xbar_out), _p(x), _p(bt), bts, _p(wt), wts, _p(p_in), _p(p_out),
+        members, _p(map), active, ndim, nz, ny, nx, w[0], w[1], w[2], _p(tab),
+        int(iteration), int(flags), _p(ws) if rows is not None else None,
+        ws.numel() if rows is not None else 0, _p(rows), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pd_stack_iter")
+    if active:
+        _wrote(xbar_out, x, p_out, rows)
+    return True
+
+
 # ----------------------------------------------------------------- ADMM ----
 def admm_vw_update(x, v, w_, c, rhs, shape, w, thr, rhs_scale, want_norm=False):
     """v, w_ and the next right-hand side rhs = rhs_scale * (v - w_ + c) from one

@@ -23,6 +23,12 @@ execution forms, the same results and the same interface:
               than ops.PD_SWEEP_MAX_VOXELS, a geometry the library declines, a
               `tolerance`: every member then stops at an iteration of its own,
               get_iterations_done()): one PrimalDualSolver after the other.
+
+PrimalDualSweep(..., tolerance=, stacked_stopping=True) keeps a sweep with a
+tolerance stacked: the members advance in one launch per iteration over a device
+map of the members still running, observation and weights shared, and every member
+leaves the map at the check that meets the tolerance
+(nsol_amd/stacked_stopping.py, nsol_pdm.hip).  The default is off.
 """
 import datetime
 import itertools
@@ -34,6 +40,7 @@ from . import ops
 from .observer import Observer
 from .primal_dual_solver import (PrimalDualSolver, checked_check_every,
                                  checked_tolerance, step_schedule)
+from .stacked_stopping import run_group, stretch_bounds
 
 PARAMETER_KEYS = ("alpha", "alg_type", "L2")
 
@@ -62,7 +69,8 @@ class PrimalDualSweep(object):
 
     def __init__(self, prox_f, prox_g_conj, B, B_conj, L2, x0, parameters,
                  iterations=50, x_scale=1., dtype=None, alpha=0.01,
-                 alg_type="ALG2", tolerance=None, check_every=10):
+                 alg_type="ALG2", tolerance=None, check_every=10,
+                 stacked_stopping=False):
         self._callables = dict(prox_f=prox_f, prox_g_conj=prox_g_conj, B=B,
                                B_conj=B_conj)
         self._x0 = x0
@@ -70,8 +78,10 @@ class PrimalDualSweep(object):
         self._members = member_parameters(parameters)
         self._iterations = int(iterations)
         # a tolerance (PrimalDualSolver's stopping rule): every member stops at an
-        # iteration of its own, so the members run one after the other
+        # iteration of its own, so the members run one after the other -- or, with
+        # stacked_stopping, stacked over a map of the members still running
         self._tolerance = checked_tolerance(tolerance)
+        self._stacked_stopping = bool(stacked_stopping)
         self._check_every = checked_check_every(check_every)
         self._iterations_done = None
         self._x_scale = float(x_scale)
@@ -134,7 +144,8 @@ class PrimalDualSweep(object):
         plan = template.plan()
         stacked = False
         self._iterations_done = None
-        if plan is not None and self._iterations > 0 and self._tolerance is None and \
+        if plan is not None and self._iterations > 0 and \
+                (self._tolerance is None or self._stacked_stopping) and \
                 int(np.prod(plan["shape"])) <= ops.PD_SWEEP_MAX_VOXELS:
             stacked = self._run_stacked(template, plan)
         if not stacked:
@@ -209,6 +220,7 @@ class PrimalDualSweep(object):
                 for obs in observers:
                     obs._observe(0, start, scale)
         first_call = True
+        done = []
         for a, b in ops.sweep_groups(P, G):
             g = b - a
             x = x_all[a * n:b * n]
@@ -216,6 +228,25 @@ class PrimalDualSweep(object):
             pp = [t[:g * dim * n] for t in p]
             xb[0].view(g, n).copy_(x0)
             k = 0
+            if self._tolerance is not None:
+                # every member stops at a check of its own (stacked_stopping)
+                res = run_group(
+                    x, xb, pp, bt, wt, g, plan["shape"], plan["w"],
+                    ops.pd_weighted_table(x, g, lmbda[a:b], sig[a:b], ta[a:b], th[a:b],
+                                          True, plan["gamma"], plan["flags"]),
+                    plan["flags"], [self._tolerance] * g, self._check_every, iters,
+                    stretch_bounds(iters, self._check_every,
+                                   bounds if observers else None),
+                    observe=(lambda m, it, a=a: observers[a + m]._observe(
+                        it, x_all[(a + m) * n:(a + m + 1) * n], self._x_scale))
+                    if observers else None)
+                if res is None:
+                    if first_call:
+                        return False
+                    raise RuntimeError("nsol_pd_stack_iter declined in mid-sweep")
+                first_call = False
+                done += res.iterations_done
+                continue
             for i0, i1 in zip(bounds[:-1], bounds[1:]):
                 if wt is not None:
                     # a weighted data term: observation and weights shared by
@@ -241,6 +272,8 @@ class PrimalDualSweep(object):
                         observers[m]._observe(i1, x_all[m * n:(m + 1) * n],
                                               self._x_scale)
         self._x_all, self._n, self._observers = x_all, n, observers
+        if self._tolerance is not None:
+            self._iterations_done = done
         self._group = G
         return True
 

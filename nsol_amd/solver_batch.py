@@ -23,6 +23,14 @@ that is None (foreign callables, deconvolution), a solver with a tolerance (it s
 at an iteration of its own), a stack of one, members above
 ops.PD_BATCH_MAX_VOXELS, a geometry the library declines on its first launch, an
 observer that keeps iterates on the host, a verbose solver.
+
+PrimalDualBatch(solvers, stacked_stopping=True) also stacks the solvers that have a
+tolerance, among themselves: members that agree in stopping_member_key() -- the
+fields above and check_every; the tolerance may differ -- advance in one launch per
+iteration over a device map of the members still running, and every member leaves
+the map at the check that meets its own tolerance (nsol_amd/stacked_stopping.py,
+nsol_pdm.hip).  Every member then answers get_x(), get_iterations_done(),
+get_stop_reason() and get_changes() as after its own run().  The default is off.
 """
 import datetime
 import time
@@ -33,6 +41,7 @@ from . import ops
 from .device import is_device_tensor, torch_dtype
 from .observer import observation_points
 from .primal_dual_solver import PrimalDualSolver, step_schedule
+from .stacked_stopping import GroupResult, StoppedRule, run_group, stretch_bounds
 
 
 def _dev_index(v):
@@ -66,6 +75,30 @@ def member_key(solver, plan):
             ("weights", _dev_index(plan.get("weights"))))
 
 
+class _WithoutTolerance(object):
+    """A solver as member_key() would see it without its tolerance."""
+    _tolerance = None
+
+    def __init__(self, solver):
+        self._solver = solver
+
+    def __getattr__(self, name):
+        return getattr(self._solver, name)
+
+
+def stopping_member_key(solver, plan):
+    """What the members of one stack WITH per-member stopping share, or None:
+    member_key's fields and check_every.  The tolerance itself may differ from
+    member to member; a solver without one never has this key, so it never shares a
+    stack with one that stops."""
+    if solver._tolerance is None:
+        return None
+    key = member_key(_WithoutTolerance(solver), plan)
+    if key is None:
+        return None
+    return key + (("check_every", int(solver._check_every)),)
+
+
 def plan_stacks(keys):
     """[[member index, ...], ...]: the stacks of two or more members with equal
     keys, in order of their first member; every other index runs sequentially."""
@@ -78,7 +111,7 @@ def plan_stacks(keys):
 
 class PrimalDualBatch(object):
 
-    def __init__(self, solvers):
+    def __init__(self, solvers, stacked_stopping=False):
         solvers = list(solvers)
         if not solvers:
             raise ValueError("a batch needs at least one solver")
@@ -93,6 +126,8 @@ class PrimalDualBatch(object):
             if s._x0_ndim != 1:
                 raise ValueError("Initial value x0 must be a 1D array")
         self._solvers = solvers
+        # True: solvers with a tolerance stack among themselves and stop one by one
+        self._stacked_stopping = bool(stacked_stopping)
         self._execution = None
         self._group = None
         self._stacks = []           # (member indices, (P * n) iterate, solver units)
@@ -127,11 +162,16 @@ class PrimalDualBatch(object):
         execution = ["sequential"] * len(solvers)
         self._stacks, self._group = [], None
         self._staging = []
-        for idx in plan_stacks(keys):
+        stacks = [(idx, False) for idx in plan_stacks(keys)]
+        if self._stacked_stopping:
+            stacks += [(idx, True) for idx in plan_stacks(
+                [stopping_member_key(s, p) for s, p in zip(solvers, plans)])]
+        for idx, stopping in stacks:
             t1 = time.time()
-            x_all = self._run_stack(idx, plans)
+            x_all = self._run_stack(idx, plans, stopping)
             if x_all is None:
                 continue                       # declined: nothing was written
+            stopped = self._stopped
             torch.cuda.synchronize()
             ops.settle_persist_runs(synchronize=False)
             took = datetime.timedelta(seconds=time.time() - t1)
@@ -142,6 +182,10 @@ class PrimalDualBatch(object):
                 s._execution = "fused"
                 s._iterations_done, s._stop_reason = int(s._iterations), "iterations"
                 s._rule = None
+                if stopping:
+                    s._iterations_done = stopped.iterations_done[m]
+                    s._stop_reason = stopped.stop_reason[m]
+                    s._rule = StoppedRule(s._tolerance, stopped.changes[m])
                 s._computational_time = took
                 if s._observer is not None:
                     s._observer._finish()
@@ -154,6 +198,8 @@ class PrimalDualBatch(object):
                 s.run()
         self._execution = execution
         self._computational_time = datetime.timedelta(seconds=time.time() - t0)
+
+    _stopped = None     # GroupResult of the last stack that ran with stopping=True
 
     def _upload_rows(self, rows, dtype):
         """One page-locked (P, n) array of `dtype`, filled row by row (NumPy casts
@@ -173,10 +219,12 @@ class PrimalDualBatch(object):
         from .device import device
         return torch.from_numpy(np.asarray(values, dtype=np.float64)).to(device())
 
-    def _run_stack(self, idx, plans):
+    def _run_stack(self, idx, plans, stopping=False):
         """The members `idx` in one launch per iteration and group.  Returns their
         stacked iterate (P * n, solver units), or None when the library declined
-        on its first launch (nothing has been written to any solver then)."""
+        on its first launch (nothing has been written to any solver then).
+        stopping: the members have tolerances and stop one by one
+        (stacked_stopping.run_group); self._stopped then holds what each did."""
         import torch
         from .device import device
         from .proximal_operators import scaled_data_on_device
@@ -235,6 +283,10 @@ class PrimalDualBatch(object):
         bounds = [0, iters] if obs is None else \
             observation_points(iters, obs.get_every())
         first_call = True
+        if stopping:
+            bounds = stretch_bounds(iters, solvers[0]._check_every,
+                                    None if obs is None else bounds)
+            self._stopped = GroupResult(0)
         for a, b in ops.sweep_groups(P, G):
             g = b - a
             x = x_all[a * n:b * n]
@@ -242,6 +294,34 @@ class PrimalDualBatch(object):
             pp = [t[:g * dim * n] for t in p]
             xb[0].copy_(x)
             k = 0
+            if stopping:
+                def observe(m, it, a=a):
+                    if not observe.started:
+                        # the library has taken the stack: the observation of the
+                        # start vectors, as Solver._observe_start makes it
+                        for s in solvers:
+                            s._x = None
+                            s._observe_start(iters)
+                        observe.started = True
+                    solvers[a + m]._observe_at(
+                        it, x_all[(a + m) * n:(a + m + 1) * n])
+                observe.started = not first_call
+                res = run_group(
+                    x, xb, pp, bt[a * n:b * n],
+                    None if wt is None else wt[a * n:b * n], g, plan["shape"],
+                    plan["w"], ops.pd_weighted_table(
+                        x, g, lmbda[a:b], sig[a:b], ta[a:b], th[a:b], True,
+                        plan["gamma"], plan["flags"]),
+                    plan["flags"], [s._tolerance for s in solvers[a:b]],
+                    solvers[0]._check_every, iters, bounds,
+                    observe=None if obs is None else observe)
+                if res is None:
+                    if first_call:
+                        return None
+                    raise RuntimeError("nsol_pd_stack_iter declined in mid-stack")
+                first_call = False
+                self._stopped.extend(res)
+                continue
             for i0, i1 in zip(bounds[:-1], bounds[1:]):
                 if wt is not None:
                     slot = ops.pd_weighted_run(
