@@ -889,6 +889,49 @@ int nsol_pd_stack_iter_f64(const double *xbar_in, double *xbar_out, double *x,
     int iteration, int flags, double *ws, int64_t ws_doubles, double *rows, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * Primal-dual iteration with the data term behind a linear operator A
+ * (nsol_pdl.hip): lambda D_w(A x, b) + R(grad x) + the indicator of [lo, hi], the
+ * saddle-point problem over K = (grad, A) with a dual variable p for the regulariser
+ * and q for the data term.  A and A^T are applied by the caller.
+ *
+ * nsol_pdl_dual_data_*: the update of q in place, n elements.
+ *   t != NULL: t holds A xbar,            v = q + sigma * (t - bt);
+ *   t == NULL: q holds q + sigma A xbar,  v = q - sigma * bt (the blur's epilogue
+ *              nsol_corr3_wrap_axpby_* wrote it);
+ *   c = lmbda * w, w = 1 where wt == NULL;
+ *   l1 == 0: q = (v * c) / (c + sigma);   l1 != 0: q = min(max(v, -c), c);
+ *   w_i == 0: q = 0 exactly, whatever bt holds there (NaN and +-inf included).
+ * NSOL_EINVAL: a missing q or bt, t == q, sigma <= 0, lmbda < 0, n < 0.
+ *
+ * nsol_pdl_iter_*: the regulariser's dual update and the explicit primal step of ONE
+ * iteration in one pass over a single contiguous volume (k_pd_lin / k_pd_lin_iso,
+ * the tile bodies of nsol_pd_fused_iter_*):
+ *   p_out = prox_{sigma R*}(p_in + sigma grad xbar_in)    (has_p == 0: p_in counts as
+ *                                                          zero and is not read)
+ *   x = min(max(x - tau * (grad^T p_out + g), lo), hi);  xbar_out = x + theta (x - x_old)
+ * g = A^T q, n elements.  hden = 1 + sigma * gamma_huber (1 for TV).
+ * flags: NSOL_PD_REG_TV / _HUBER, NSOL_PD_REG_ISOTROPIC taken; any data flag is
+ * NSOL_EINVAL (the data term is nsol_pdl_dual_data_*'s).  lo <= hi, infinities allowed;
+ * float32 rounds the box towards its inside.
+ * Returns -2, nothing launched, for a geometry the kernels do not take (bad extents,
+ * more than 2^31 voxels); NSOL_EINVAL for a missing pointer (p_in included),
+ * xbar_in == xbar_out, p_in == p_out, lo > hi or a NaN among them.
+ * nsol_pdl_launches: launches of k_pd_lin / k_pd_lin_iso this process has made. */
+int nsol_pdl_launches(void);
+int nsol_pdl_dual_data_f32(float *q, const float *t, const float *bt, const float *wt,
+    double sigma, double lmbda, int l1, int64_t n, void *stream);
+int nsol_pdl_dual_data_f64(double *q, const double *t, const double *bt, const double *wt,
+    double sigma, double lmbda, int l1, int64_t n, void *stream);
+int nsol_pdl_iter_f32(const float *xbar_in, float *xbar_out, float *x, const float *g,
+    const float *p_in, float *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx,
+    double wx, double wy, double wz, double sigma, double hden, double tau, double theta,
+    double lo, double hi, int flags, int has_p, void *stream);
+int nsol_pdl_iter_f64(const double *xbar_in, double *xbar_out, double *x, const double *g,
+    const double *p_in, double *p_out, int ndim, int64_t nz, int64_t ny, int64_t nx,
+    double wx, double wy, double wz, double sigma, double hden, double tau, double theta,
+    double lo, double hi, int flags, int has_p, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

@@ -13,9 +13,12 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # nsol_amd.PrimalDualBatch: resolved on first use, so that importing the package
+    # nsol_amd.PrimalDualBatch / PrimalDualLinearSolver: resolved on first use, so that importing the package
     # stays as light as it was
     if name == "PrimalDualBatch":
         from .solver_batch import PrimalDualBatch
         return PrimalDualBatch
+    if name == "PrimalDualLinearSolver":
+        from .primal_dual_linear_solver import PrimalDualLinearSolver
+        return PrimalDualLinearSolver
     raise AttributeError("module 'nsol_amd' has no attribute '%s'" % name)

@@ -11,6 +11,16 @@ deconvolution_solver_parameter_study_interface.py:217-325, without plotting).
 --solver PD takes --tolerance T / --check-every K, the stopping rule of
 PrimalDualSolver (see run_denoising); the iterations actually done are printed.
 
+--solver PDL (TVL2 / HuberL2) is PrimalDualLinearSolver: the blur is part of the
+saddle-point problem's linear map instead of the primal prox, so no iteration solves a
+linear system (one blur, one adjoint blur and two element-wise / stencil passes per
+iteration).  It takes --isotropic, --tolerance / --check-every, --observe-every,
+--mask FILE (voxels > 0 count) or --weights FILE (per-voxel weights of the data term,
+as in run_denoising), --data-loss ell1 for sum w_i |(A x - b)_i| ("linear" is the l2
+data term) and --nonnegative for the exact projection onto x >= 0.  --L2 is not used:
+the step sizes come from the operator norms.  PDL needs more iterations than PD, each
+of them far cheaper.
+
 With --reference, the measures are evaluated through an Observer on the flat
 iterates against the flat reference (as run_denoising does and as the
 reference's tool does) and printed as first -> last value.
@@ -22,6 +32,7 @@ import numpy as np
 
 from .. import linear_operators as LinearOperators
 from .. import primal_dual_solver as pd
+from .. import primal_dual_linear_solver as pdl
 from .. import admm_linear_solver as admm
 from .. import tikhonov_linear_solver as tk
 from .. import data_reader as dr
@@ -29,14 +40,17 @@ from .. import data_writer as dw
 from .. import observer as Observer
 from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
-from .run_denoising import last_observed, print_stop
+from .run_denoising import last_observed, print_stop, read_weights
 
 
 def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  tv_solver="PD", alpha=0.01, iterations=10, iter_max=10,
                  rho=0.1, minimizer="lsmr", data_loss="linear",
                  data_loss_scale=1., L2=8, verbose=0, dtype=None,
-                 tolerance=None, check_every=10, isotropic=False):
+                 tolerance=None, check_every=10, weights=None, pdl_data_loss="ell2",
+                 nonnegative=False, isotropic=False):
+    """weights, pdl_data_loss ("ell2" | "ell1") and nonnegative belong to
+    tv_solver="PDL" (PrimalDualLinearSolver)."""
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -60,6 +74,27 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                   x_scale=x_scale, data_loss=data_loss,
                   data_loss_scale=data_loss_scale, iter_max=iter_max,
                   verbose=verbose, dtype=dtype)
+    if reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL":
+        if weights is not None:
+            # as run_denoising.wiring: the scale is the maximum over the voxels that
+            # count, the start is zero where a voxel that does not count is not finite
+            weights = np.asarray(weights)
+            if weights.shape != observed_nda.shape:
+                raise ValueError("the weights have shape %s, the observation %s" %
+                                 (weights.shape, observed_nda.shape))
+            counted = weights.flatten() > 0
+            x_scale = np.max(b[counted]) if counted.any() else 1.
+            x0[~counted & ~np.isfinite(x0)] = 0
+            weights = weights.flatten()
+        return pdl.PrimalDualLinearSolver(
+            A=A_1D, A_adj=A_adj_1D, b=b, x0=x0, dimension=dimension, spacing=spacing,
+            alpha=alpha, iterations=iterations,
+            reg_type="TV" if reconstruction_type == "TVL2" else "huber",
+            isotropic=isotropic, data_loss=pdl_data_loss, weights=weights,
+            bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
+            verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every)
+    if weights is not None or nonnegative:
+        raise ValueError("weights and nonnegative belong to tv_solver='PDL'")
     if reconstruction_type == "TK0L2":
         return tk.TikhonovLinearSolver(B=I_1D, B_adj=I_1D,
                                        minimizer=minimizer, **common)
@@ -105,7 +140,7 @@ def main(argv=None):
     ap.add_argument("--blur", type=float, default=1.2)
     ap.add_argument("--reconstruction-type", default="TVL2",
                     choices=["TK0L2", "TK1L2", "TVL2", "HuberL2"])
-    ap.add_argument("--solver", default="PD", choices=["PD", "ADMM"])
+    ap.add_argument("--solver", default="PD", choices=["PD", "ADMM", "PDL"])
     ap.add_argument("--alpha", type=float, nargs="+", default=[0.01])
     ap.add_argument("--rho", type=float, default=0.1)
     ap.add_argument("--iterations", type=int, default=10)
@@ -125,33 +160,48 @@ def main(argv=None):
                     help="evaluate the measures on the device every K "
                          "iterations (and at the last) instead of on a host "
                          "copy of every iterate")
-    ap.add_argument("--mask", default=None, metavar="FILE",
-                    help="not supported here (see run_denoising)")
-    ap.add_argument("--weights", default=None, metavar="FILE",
-                    help="not supported here (see run_denoising)")
+    wgroup = ap.add_mutually_exclusive_group()
+    wgroup.add_argument("--mask", default=None, metavar="FILE",
+                        help="--solver PDL: image of the observation's shape, voxels "
+                             "> 0 count in the data term (weight 1), the rest do not "
+                             "and are inpainted by the regulariser")
+    wgroup.add_argument("--weights", default=None, metavar="FILE",
+                        help="--solver PDL: image of the observation's shape, "
+                             "per-voxel weights of the data term, finite and >= 0")
+    ap.add_argument("--nonnegative", action="store_true",
+                    help="--solver PDL: x >= 0 as an exact projection in every "
+                         "iteration")
     ap.add_argument("--tolerance", type=float, default=None, metavar="T",
-                    help="--solver PD, TVL2 / HuberL2: stop once the relative change "
+                    help="--solver PD or PDL, TVL2 / HuberL2: stop once the relative change "
                          "of the primal and of the dual iterate in one iteration is "
                          "<= T (default: run all --iterations)")
     ap.add_argument("--check-every", type=int, default=10, metavar="K",
                     help="with --tolerance: evaluate the change every K iterations "
                          "and at the last")
     args = ap.parse_args(argv)
-    primal_dual = args.solver == "PD" and \
+    primal_dual = args.solver in ("PD", "PDL") and \
         args.reconstruction_type in ("TVL2", "HuberL2")
+    linear = args.solver == "PDL"
+    if linear and not primal_dual:
+        ap.error("--solver PDL applies to --reconstruction-type TVL2 or HuberL2")
+    if linear and args.data_loss not in ("linear", "ell2", "ell1"):
+        ap.error("--solver PDL takes --data-loss linear (the l2 data term) or ell1, "
+                 "not '%s'" % args.data_loss)
+    if args.nonnegative and not linear:
+        ap.error("--nonnegative is an option of --solver PDL")
     if args.tolerance is not None and not primal_dual:
-        ap.error("--tolerance is the stopping rule of the primal-dual solver "
-                 "(--solver PD with TVL2 or HuberL2)")
+        ap.error("--tolerance is the stopping rule of the primal-dual solvers "
+                 "(--solver PD or PDL with TVL2 or HuberL2)")
     if args.tolerance is not None and not args.tolerance >= 0:
         ap.error("--tolerance must be >= 0")
     if args.check_every < 1:
         ap.error("--check-every must be >= 1")
-    if args.mask is not None or args.weights is not None:
+    if (args.mask is not None or args.weights is not None) and not linear:
         ap.error("--mask / --weights are options of run_denoising: the weighted "
                  "data term is a prox of the denoising problem, while "
-                 "deconvolution solves a linear least-squares problem per step "
-                 "(prox_linear_least_squares), where a mask belongs in the "
-                 "operator A")
+                 "deconvolution with --solver %s solves a linear least-squares "
+                 "problem per step (prox_linear_least_squares), where a mask belongs "
+                 "in the operator A -- or use --solver PDL" % args.solver)
 
     reader = dr.DataReader(args.observation)
     reader.read_data()
@@ -164,13 +214,21 @@ def main(argv=None):
         ref_reader = dr.DataReader(args.reference)
         ref_reader.read_data()
         x_ref = ref_reader.get_data().flatten()
+    weights = None
+    if linear:
+        try:
+            weights = read_weights(args, observed_nda.shape)
+        except ValueError as e:
+            ap.error(str(e))
     for alpha in args.alpha:
         solver = build_solver(
             observed_nda, spacing, args.blur, args.reconstruction_type,
             args.solver, alpha, args.iterations, args.iter_max, args.rho,
             args.minimizer, args.data_loss, args.data_loss_scale, args.L2,
             args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic,
-            tolerance=args.tolerance, check_every=args.check_every)
+            tolerance=args.tolerance, check_every=args.check_every, weights=weights,
+            pdl_data_loss="ell1" if args.data_loss == "ell1" else "ell2",
+            nonnegative=args.nonnegative)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \

@@ -34,6 +34,16 @@ __device__ __forceinline__ bool pd_fused_block_tile(int bid, int ntx, int nty, i
   return true;
 }
 
+// LIN: the explicit primal step of the iteration whose data term sits behind a linear
+// operator A (k_pd_lin, nsol_pdl.hip): kt = grad^T p as the tile formed it, g = A^T q,
+// their sum before the one multiplication by tau, then the projection onto [lo, hi].
+template <typename T>
+__device__ __forceinline__ T lin_step(T x, T kt, T g, T tau, T lo, T hi) {
+  const T u = x - tau * (kt + g);
+  const T c = u < lo ? lo : u;
+  return c > hi ? hi : c;
+}
+
 // One iteration on tile (tx, ty), z-chunk zc of one volume: each wave owns a
 // (LX*VEC) x (LY*RY) patch of the x-y tile and marches along z (see nsol_pd.hip).
 // RAG: rows that are not a multiple of VEC elements / arrays that are not 16-byte
@@ -45,13 +55,17 @@ __device__ __forceinline__ bool pd_fused_block_tile(int bid, int ntx, int nty, i
 // row's end, not the rows outside the volume, not the dual values it recomputes on
 // the lower halo -- to chk[0..3] (k_pd_check, nsol_pdc.hip); off by default, and the
 // other kernels are compiled as before.
+// LIN: the array in bt's place holds g = A^T q and the data prox is lin_step with the
+// box [lo, hi] (k_pd_lin, nsol_pdl.hip); off by default, the other kernels are
+// compiled as before.
 template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false,
-          bool CHK = false>
+          bool CHK = false, bool LIN = false>
 __device__ __forceinline__ void pd_fused_tile(
     const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
     const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
     const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk,
-    const T *__restrict__ wt = nullptr, double *chk = nullptr) {
+    const T *__restrict__ wt = nullptr, double *chk = nullptr, T lo = T(0),
+    T hi = T(0)) {
   constexpr int LY = kWave / LX;
   constexpr int WAVES = kBlock / kWave;
   constexpr int TY = WAVES * LY * RY;
@@ -247,7 +261,9 @@ __device__ __forceinline__ void pd_fused_tile(
           kt += pzn[r][k] * (-G.wz) + pzprev[r][k] * G.wz;
         const T u = xv[r][k] - S.tau * kt;
         T xnew;
-        if constexpr (WGT) xnew = prox_data_w(u, bv[r][k], wv[r][k], S.tl, S.l1 != 0);
+        if constexpr (LIN) xnew = lin_step(xv[r][k], kt, bv[r][k], S.tau, lo, hi);
+        else if constexpr (WGT)
+          xnew = prox_data_w(u, bv[r][k], wv[r][k], S.tl, S.l1 != 0);
         else xnew = prox_data(u, bv[r][k], S.tl, S.one_plus_tl, S.l1 != 0);
         xo_new[k] = xnew;
         xb_new[k] = xnew + S.theta * (xnew - xv[r][k]);

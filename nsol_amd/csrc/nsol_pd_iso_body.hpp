@@ -46,14 +46,15 @@ __device__ __forceinline__ void dual_project(T &q0, T &q1, T &q2, bool huber, T 
 }
 
 // One iteration on tile (tx, ty), z-chunk zc of one volume; arguments as
-// pd_fused_tile (WGT / wt and CHK / chk included).
+// pd_fused_tile (WGT / wt, CHK / chk and LIN / lo, hi included).
 template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT = false,
-          bool CHK = false>
+          bool CHK = false, bool LIN = false>
 __device__ __forceinline__ void pd_fused_iso_tile(
     const T *__restrict__ xbar_in, T *__restrict__ xbar_out, T *x,
     const T *__restrict__ bt, const T *__restrict__ p_in, T *__restrict__ p_out,
     const Geom<T> &G, const PdScalars<T> &S, int tx, int ty, int zc, int zchunk,
-    const T *__restrict__ wt = nullptr, double *chk = nullptr) {
+    const T *__restrict__ wt = nullptr, double *chk = nullptr, T lo = T(0),
+    T hi = T(0)) {
   constexpr int LY = kWave / LX;
   constexpr int WAVES = kBlock / kWave;
   constexpr int TY = WAVES * LY * RY;
@@ -284,7 +285,9 @@ __device__ __forceinline__ void pd_fused_iso_tile(
           kt += pzn[r][k] * (-G.wz) + pzprev[r][k] * G.wz;
         const T u = xv[r][k] - S.tau * kt;
         T xnew;
-        if constexpr (WGT) xnew = prox_data_w(u, bv[r][k], wv[r][k], S.tl, S.l1 != 0);
+        if constexpr (LIN) xnew = lin_step(xv[r][k], kt, bv[r][k], S.tau, lo, hi);
+        else if constexpr (WGT)
+          xnew = prox_data_w(u, bv[r][k], wv[r][k], S.tl, S.l1 != 0);
         else xnew = prox_data(u, bv[r][k], S.tl, S.one_plus_tl, S.l1 != 0);
         xo_new[k] = xnew;
         xb_new[k] = xnew + S.theta * (xnew - xv[r][k]);

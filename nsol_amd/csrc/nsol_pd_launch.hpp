@@ -1,6 +1,7 @@
 // Host-side launch path of the kernels that do ONE Chambolle-Pock iteration in one
 // pass: k_pd_fused (nsol_pd.hip), k_pd_fused_iso (nsol_pdi.hip), the member-stacked
-// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip), k_pd_w (nsol_pdw.hip) and k_pd_check (nsol_pdc.hip).  They share the wave layout of
+// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip), k_pd_w (nsol_pdw.hip), k_pd_check (nsol_pdc.hip) and
+// k_pd_lin (nsol_pdl.hip).  They share the wave layout of
 // nsol_pd_fused_body.hpp -- a wave owns (LX*VEC) x (LY*RY) of an x-y tile and
 // marches along z -- so the rounding of the scalars, the grid, the automatic rows
 // per lane and the access form are chosen here, once.  A new kernel of the family
@@ -47,6 +48,7 @@ struct PdLaunchArgs {
   double *chk_ws = nullptr;           // the checking kernel's partial sums (one per
   int64_t chk_ws_doubles = 0;         // workgroup and sum) and the board row its
   double *chk_row = nullptr;          // closing workgroup writes (nsol_pdc.hip)
+  T lo = T(0), hi = T(0);             // the box of the linear kernels (nsol_pdl.hip)
 };
 
 struct PdGridPlan {

@@ -1734,6 +1734,56 @@ def pd_weighted_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, members, shape, 
     return True
 
 
+# ------------------------------------ data term behind a linear operator ----
+# (nsol_pdl.hip; the loop is primal_dual_linear_solver.py's)
+def pdl_launches():
+    """Launches of k_pd_lin / k_pd_lin_iso so far (for tests and tools)."""
+    return int(_lib.load().nsol_pdl_launches())
+
+
+def pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1=False):
+    """The data term's dual variable q in place: v = q + sigma * (t - bt) with t = A xbar,
+    or, t None, v = q - sigma * bt with q already holding q + sigma A xbar (the blur's
+    epilogue); then q = v c / (c + sigma) (l2) or clamp(v, -c, c) (l1) with
+    c = lmbda * wt (wt None: 1), and exactly 0 where wt is 0.  Does not synchronise."""
+    _same(q, bt)
+    if t is not None:
+        _same(q, t)
+    if wt is not None:
+        _same(q, wt)
+    _lib.check(_fn("pdl_dual_data", q)(
+        _p(q), _p(t), _p(bt), _p(wt), float(sigma), float(lmbda), int(bool(l1)),
+        q.numel(), stream_ptr()), "nsol_pdl_dual_data")
+    return _wrote(q)
+
+
+def pdl_iter(xbar_in, xbar_out, x, g, p_in, p_out, shape, w, sigma, hden, tau, theta,
+             lo, hi, flags, has_p=True):
+    """One iteration's regulariser side and explicit primal step in one pass:
+    p_out = prox(p_in + sigma grad xbar_in), x = clip(x - tau (grad^T p_out + g), lo, hi),
+    xbar_out = x + theta (x - x_old); g = A^T q.  has_p False: p_in counts as zero (it
+    must still be given).  flags: PD_REG_TV / PD_REG_HUBER, PD_REG_ISOTROPIC.  Returns
+    False when the library declined the geometry (nothing was launched).  Does not
+    synchronise."""
+    ndim, nz, ny, nx = dims3(shape)
+    n = nz * ny * nx
+    _same(x, xbar_in, xbar_out, g)
+    _same(p_out, p_in)
+    if p_out.dtype != x.dtype or x.numel() != n or p_out.numel() != ndim * n:
+        raise ValueError("operand mismatch: x %s[%d], p %s[%d] for shape %r" %
+                         (str(x.dtype), x.numel(), str(p_out.dtype), p_out.numel(),
+                          tuple(shape)))
+    rc = _fn("pdl_iter", x)(
+        _p(xbar_in), _p(xbar_out), _p(x), _p(g), _p(p_in), _p(p_out), ndim, nz, ny, nx,
+        w[0], w[1], w[2], float(sigma), float(hden), float(tau), float(theta), float(lo),
+        float(hi), int(flags), int(bool(has_p)), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pdl_iter")
+    _wrote(xbar_out, x, p_out)
+    return True
+
+
 # ------------------------------------------------------ stopping rule ----
 # (nsol_pdc.hip; the rule itself is primal_dual_solver.py's)
 PD_CHECK_SUMS = 4

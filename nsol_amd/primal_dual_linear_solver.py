@@ -1,0 +1,342 @@
+"""Chambolle-Pock primal-dual solver for a data term behind a linear operator A on
+MI355X -- deconvolution without inner solves:
+
+    min_x  lambda D_w(A x, b~) + R(grad x) + indicator_[lo, hi](x),   lambda = 1/alpha,
+
+in the scaled variable x / x_scale (b~ = b / x_scale; the box is the scaled
+variable's, as TikhonovLinearSolver's bounds are), with
+  D_w   1/2 sum w_i (.)^2 (data_loss="ell2") or sum w_i |.| ("ell1"), per-voxel
+        weights w_i >= 0 (a mask, a confidence map; None: all 1),
+  R     TV or Huber(gamma), anisotropic or isotropic,
+  grad  the zero-padded forward difference of GradientOperator.
+
+PrimalDualSolver deconvolves through prox_linear_least_squares: every iteration is a
+whole Tikhonov / LSMR solve.  Here A is part of the saddle-point problem's linear map
+K = (grad, A), with a dual variable p for the regulariser and q for the data term, and
+one iteration (constant steps, theta = 1: Chambolle-Pock's basic algorithm -- G is an
+indicator, so the accelerated schedules do not apply) is
+
+    p <- prox_{sigma R*}(p + sigma grad xbar)
+    v  = q + sigma (A xbar - b~)
+    q <- l2: v c / (c + sigma), c = lambda w;   l1: clamp(v, -c, c);   w = 0: 0
+    x+ = clip(x - tau (grad^T p + A^T q), lo, hi);  xbar <- x+ + theta (x+ - x);  x <- x+
+
+one application of A, one of A^T, one element-wise kernel (ops.pdl_dual_data) and one
+pass of the fused primal-dual tile (ops.pdl_iter, nsol_pdl.hip).  Weights, masks, the
+l1 data term and the box cost nothing extra.
+
+`run()` picks one of three execution forms for A and A^T; the regulariser side is
+nsol_pdl_iter_* in all of them:
+  fused   A, A_adj are device operators of this package, recognised THROUGH
+          caller-side lambdas (symbolic.trace_operator).  Where A is a
+          ConvolutionOperator whose one-pass blur has the axpby epilogue, A xbar is
+          never stored: q <- sigma A xbar + q is the blur's epilogue;
+  device  callables on torch HIP tensors;
+  host    NumPy-only callables: their argument is copied to the host for the call only.
+
+Stopping rule: PrimalDualSolver's, with the dual ratio taken over the stacked dual
+(p, q): r_dual = sqrt((sum dp^2 + sum dq^2) / (sum p^2 + sum q^2)); one read-back per
+check, none without a tolerance.
+"""
+import numpy as np
+
+from . import linear_operators, ops
+from .bridge import BridgedCallable
+from .device import is_device_tensor
+from .linear_operators import ConvolutionOperator, DeviceOperator
+from .primal_dual_solver import (_StopRule, checked_check_every, checked_tolerance,
+                                 criterion_met, relative_changes)
+from .proximal_operators import (check_weights, scaled_data_on_device,
+                                 weights_on_device)
+from .solver import Solver
+from .symbolic import trace_operator
+from ._accessors import add_accessors
+
+REG_TYPES = ("TV", "huber")
+DATA_LOSSES = ("ell2", "ell1")
+
+
+def step_sizes(L2, tau=None, sigma=None):
+    """(tau, sigma): 1/sqrt(L2) each by default; with one given, the other is
+    1 / (L2 * it).  ValueError unless both are positive and tau sigma L2 <= 1."""
+    L2 = float(L2)
+    if not (np.isfinite(L2) and L2 > 0):
+        raise ValueError("L2 must be a positive number")
+    if tau is None and sigma is None:
+        tau = sigma = 1. / np.sqrt(L2)
+    elif tau is None:
+        sigma = float(sigma)
+        tau = 1. / (L2 * sigma) if sigma > 0 else sigma
+    elif sigma is None:
+        tau = float(tau)
+        sigma = 1. / (L2 * tau) if tau > 0 else tau
+    tau, sigma = float(tau), float(sigma)
+    if not (np.isfinite(tau) and np.isfinite(sigma) and tau > 0 and sigma > 0):
+        raise ValueError("tau and sigma must be positive numbers")
+    if tau * sigma * L2 > 1. + 1e-12:
+        raise ValueError("tau * sigma * L2 = %g > 1: the iteration need not converge" %
+                         (tau * sigma * L2))
+    return tau, sigma
+
+
+def checked_bounds(bounds):
+    """(lo, hi) as floats with lo <= hi, infinities allowed; None: (-inf, inf)."""
+    if bounds is None:
+        return -np.inf, np.inf
+    try:
+        lo, hi = bounds
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError("bounds must be None or a pair (lo, hi)")
+    if not lo <= hi:
+        raise ValueError("bounds must satisfy lo <= hi")
+    return lo, hi
+
+
+class _LinearStopRule(_StopRule):
+    """_StopRule with two rows of sums per check: nsol_pd_change_* over (x, p) and
+    over q; the dual ratio is taken over the stacked dual (p, q)."""
+
+    def allocate(self, like, shape=None):
+        import torch
+        self.ws = torch.empty(ops.PD_CHECK_SUMS * 4096, dtype=torch.float64,
+                              device=like.device)
+        self.board = torch.empty((max(len(self.points), 1), 2 * ops.PD_CHECK_SUMS),
+                                 dtype=torch.float64, device=like.device)
+
+    def decide(self, it):
+        s = self.row(it).cpu().numpy()         # the one read-back of this check
+        r_x, r_d = relative_changes((s[0], s[1], s[2] + s[4], s[3] + s[5]))
+        self.rows.append((float(it), r_x, r_d))
+        return criterion_met(r_x, r_d, self.tolerance)
+
+
+class PrimalDualLinearSolver(Solver):
+
+    def __init__(self, A, A_adj, b, x0, dimension, spacing=None, alpha=0.01,
+                 iterations=10, reg_type="TV", huber_gamma=0.05, isotropic=False,
+                 data_loss="ell2", weights=None, bounds=None, A_norm2=None, L2=None,
+                 tau=None, sigma=None, x_scale=1., verbose=0, dtype=None,
+                 tolerance=None, check_every=10, shape=None):
+        Solver.__init__(self, x0=x0, verbose=verbose, x_scale=x_scale, dtype=dtype)
+        if reg_type not in REG_TYPES:
+            raise ValueError("reg_type must be one of %r" % (REG_TYPES,))
+        if data_loss not in DATA_LOSSES:
+            raise ValueError("data_loss must be one of %r" % (DATA_LOSSES,))
+        dimension = int(dimension)
+        if dimension not in (1, 2, 3):
+            raise ValueError("dimension must be 1, 2 or 3")
+        self._A, self._A_adj, self._b = A, A_adj, b
+        self._dimension = dimension
+        self._spacing = np.ones(dimension) if spacing is None else \
+            np.atleast_1d(spacing).astype(float)
+        if self._spacing.size != dimension or not np.all(self._spacing > 0):
+            raise ValueError("spacing must hold %d positive values" % dimension)
+        self._alpha = float(alpha)
+        if not self._alpha > 0:
+            raise ValueError("alpha must be positive")
+        self._iterations = iterations
+        self._reg_type, self._huber_gamma = reg_type, float(huber_gamma)
+        self._isotropic = bool(isotropic)
+        self._data_loss = data_loss
+        self._bounds = checked_bounds(bounds)
+        self._tolerance = checked_tolerance(tolerance)
+        self._check_every = checked_check_every(check_every)
+        self._iterations_done = self._stop_reason = self._rule = None
+
+        n = int(x0.numel() if is_device_tensor(x0) else np.size(x0))
+        m = int(b.numel() if is_device_tensor(b) else np.size(b))
+        self._n, self._m = n, m
+        # the operators behind the caller's lambdas
+        dA, dAt = trace_operator(A, n), trace_operator(A_adj, m)
+        self._op = self._op_adj = None
+        if self._is_own(dA, n, m, dimension) and self._is_own(dAt, m, n, dimension):
+            self._op, self._op_shape = dA[1], tuple(dA[2])
+            self._op_adj, self._op_adj_shape = dAt[1], tuple(dAt[2])
+        self._shape = self._volume_shape(shape, b, n)
+        self._weights = weights
+        if weights is not None:
+            check_weights(weights, m)
+
+        if A_norm2 is None:
+            if not isinstance(self._op, ConvolutionOperator):
+                raise ValueError("A_norm2 (an upper bound of ||A||^2) is required "
+                                 "unless A is a ConvolutionOperator of this package")
+            # Young's bound, exact for non-negative taps
+            A_norm2 = float(np.sum(np.abs(self._op.kernel))) ** 2
+        self._A_norm2 = float(A_norm2)
+        if not (np.isfinite(self._A_norm2) and self._A_norm2 >= 0):
+            raise ValueError("A_norm2 must be a finite number >= 0")
+        if L2 is None:
+            L2 = float(np.sum(4. / self._spacing ** 2)) + self._A_norm2
+        self._L2 = float(L2)
+        self._tau, self._sigma = step_sizes(self._L2, tau, sigma)
+        self._theta = 1.
+        self._execution = "fused" if self._op is not None else None
+
+    @staticmethod
+    def _is_own(desc, n_in, n_out, dimension):
+        """desc is (kind, operator, in_shape) of a device operator of this package that
+        maps n_in elements on `dimension` axes to n_out."""
+        if desc is None or len(desc) < 3 or not isinstance(desc[1], DeviceOperator):
+            return False
+        shape = tuple(desc[2])
+        return len(shape) == dimension and int(np.prod(shape)) == n_in and \
+            int(np.prod(desc[1]._out_shape(shape))) == n_out
+
+    def _volume_shape(self, shape, b, n):
+        """The volume the gradient acts on: `shape`, else the traced operator's, else
+        b's own when it is an array of `dimension` axes (1-D: the flat vector)."""
+        d = self._dimension
+        if shape is None and self._op is not None and len(self._op_shape) == d:
+            shape = self._op_shape
+        if shape is None and d == 1:
+            shape = (n,)
+        if shape is None and len(getattr(b, "shape", ())) == d:
+            shape = tuple(b.shape)
+        if shape is None:
+            raise ValueError("the volume's shape is not known: pass shape=, or an A "
+                             "of this package, or b with %d axes" % d)
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != d or int(np.prod(shape)) != n or min(shape) < 1:
+            raise ValueError("shape %r does not hold the %d values of x0 in %d-D" %
+                             (shape, n, d))
+        return shape
+
+    # ------------------------------------------------------------------
+    def get_execution(self):
+        """'fused' (known from construction), 'device' or 'host' after run()."""
+        return self._execution
+
+    def print_statistics(self, fmt="%.3e"):
+        pass
+
+    def set_tolerance(self, tolerance):
+        self._tolerance = checked_tolerance(tolerance)
+
+    def set_check_every(self, check_every):
+        self._check_every = checked_check_every(check_every)
+
+    def get_iterations_done(self):
+        """Iterations the last run() did (None before one)."""
+        return self._iterations_done
+
+    def get_stop_reason(self):
+        """'tolerance' or 'iterations' after run() (None before)."""
+        return self._stop_reason
+
+    def get_changes(self):
+        """One row (k, r_x, r_dual) per check of the last run()."""
+        rows = self._rule.rows if self._rule is not None else []
+        return np.array(rows, dtype=np.float64).reshape(-1, 3)
+
+    # ------------------------------------------------------------------
+    def _flags(self):
+        flags = ops.PD_REG_HUBER if self._reg_type == "huber" else ops.PD_REG_TV
+        if self._isotropic:
+            flags |= ops.PD_REG_ISOTROPIC
+        return flags
+
+    def _run(self):
+        import torch
+        iters = max(int(self._iterations), 0)
+        self._points = self._observe_start(iters)
+        self._rule = rule = None if self._tolerance is None else _LinearStopRule(
+            self._tolerance, iters, self._check_every)
+        self._iterations_done, self._stop_reason = 0, "iterations"
+
+        x = self._x0_device().clone()
+        n, m = self._n, self._m
+        xbar = [x.clone(), torch.empty_like(x)]
+        p = [torch.empty(self._dimension * n, dtype=x.dtype, device=x.device)
+             for _ in range(2)]
+        q = torch.zeros(m, dtype=x.dtype, device=x.device)
+        bt = scaled_data_on_device(self._b, self._x_scale, x)
+        if bt.numel() != m:
+            raise ValueError("b holds %d values, not %d" % (bt.numel(), m))
+        wt = None if self._weights is None else weights_on_device(self._weights, x)
+        if rule is not None:
+            rule.allocate(x)
+
+        fused = self._op is not None
+        if fused:
+            A = lambda t: self._op._apply(t, self._op_shape)
+            At = lambda t: self._op_adj._apply(t, self._op_adj_shape)
+        else:
+            A = BridgedCallable(self._A, self._dtype)
+            At = BridgedCallable(self._A_adj, self._dtype)
+        # q <- sigma A xbar + q as the epilogue of the one-pass blur, while it applies
+        epilogue = fused and isinstance(self._op, ConvolutionOperator) and m == n and \
+            linear_operators.USE_BLUR_EPILOGUE
+        slot = torch.empty(1, dtype=torch.float64, device=x.device) if epilogue else None
+
+        shape, w = self._shape, ops.inv_spacing(self._spacing, self._dimension)
+        flags = self._flags()
+        tau, sigma, theta = self._tau, self._sigma, self._theta
+        hden = 1. + sigma * self._huber_gamma if self._reg_type == "huber" else 1.
+        lmbda = 1. / self._alpha
+        l1 = self._data_loss == "ell1"
+        lo, hi = self._bounds
+
+        for i in range(iters):
+            if self._verbose:
+                print("Primal-Dual (linear) iteration %d/%d" % (i + 1, iters))
+            k = i & 1
+            check = rule is not None and rule.is_point(i + 1)
+            if check:
+                x_old, q_old = x.clone(), q.clone()
+            if epilogue and self._op.apply_axpby(xbar[k], q, self._op_shape, sigma, 1.,
+                                                 result=slot) is None:
+                epilogue = False       # the kernel declined: nothing ran, q is intact
+            if epilogue:
+                ops.pdl_dual_data(q, None, bt, wt, sigma, lmbda, l1)
+            else:
+                t = A(xbar[k])
+                if t.numel() != m:
+                    raise ValueError("A returned %d values, b holds %d" %
+                                     (t.numel(), m))
+                ops.pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1)
+            g = At(q)
+            if g.numel() != n:
+                raise ValueError("A_adj returned %d values, x holds %d" % (g.numel(), n))
+            if not ops.pdl_iter(xbar[k], xbar[1 - k], x, g, p[k], p[1 - k], shape, w,
+                                sigma, hden, tau, theta, lo, hi, flags, has_p=i > 0):
+                raise ValueError("nsol_pdl_iter does not take a volume of shape %r" %
+                                 (tuple(shape),))
+            if check:
+                row = rule.row(i + 1)
+                # (p's old slot is still intact: the kernel wrote the other one)
+                ops.pd_change(x_old, x, None if i == 0 else p[k], p[1 - k], rule.ws,
+                              row[:ops.PD_CHECK_SUMS])
+                ops.pd_change(q_old, q, q_old, q, rule.ws, row[ops.PD_CHECK_SUMS:])
+            self._x = x
+            self._observe_iteration(i + 1, x)
+            if rule is not None:
+                self._iterations_done = i + 1
+                if check and rule.decide(i + 1):
+                    self._stop_reason = "tolerance"
+                    break
+        self._x = x
+        if rule is None:
+            self._iterations_done = iters
+        if not fused:
+            self._execution = "device" if (A.on_device in (True, None) and
+                                           At.on_device in (True, None)) else "host"
+
+    _points = None
+
+    def _observe_iteration(self, it, x):
+        if self._observer is None:
+            return
+        if self._points is None:
+            self._observer.add_x(self.get_x())
+        else:
+            self._observe_at(it, x)
+
+
+add_accessors(PrimalDualLinearSolver,
+              ["alpha", "iterations", "huber_gamma", "reg_type", "data_loss"])
+add_accessors(PrimalDualLinearSolver,
+              ["A", "A_adj", "dimension", "spacing", "isotropic", "bounds", "A_norm2",
+               "L2", "tau", "sigma", "theta", "tolerance", "check_every", "shape"],
+              setters=False)
