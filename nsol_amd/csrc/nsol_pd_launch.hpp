@@ -1,19 +1,30 @@
 // Host-side launch path of the kernels that do ONE Chambolle-Pock iteration in one
 // pass: k_pd_fused (nsol_pd.hip), k_pd_fused_iso (nsol_pdi.hip), the member-stacked
-// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip), k_pd_w (nsol_pdw.hip), k_pd_check (nsol_pdc.hip) and
-// k_pd_lin (nsol_pdl.hip).  They share the wave layout of
-// nsol_pd_fused_body.hpp -- a wave owns (LX*VEC) x (LY*RY) of an x-y tile and
-// marches along z -- so the rounding of the scalars, the grid, the automatic rows
-// per lane and the access form are chosen here, once.  A new kernel of the family
-// supplies its __global__ function and a launcher struct K with
+// k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip), k_pd_w (nsol_pdw.hip),
+// k_pd_stack (nsol_pdm.hip), k_pd_check (nsol_pdc.hip) and k_pd_lin (nsol_pdl.hip).
+// They share the wave layout of nsol_pd_fused_body.hpp -- a wave owns
+// (LX*VEC) x (LY*RY) of an x-y tile and marches along z -- so everything that does
+// not depend on the kernel's arguments lives here, once: the rounding of the
+// scalars, what geometry a launch takes (pd_stack_takes), the access form
+// (pd_launch), the (RY, NDIM) forms (pd_launch_forms), the grid (pd_plan_grid,
+// pd_max_blocks), the table PdScalars[iteration][member] of the stacked runs
+// (pd_table_fill_upload) and their ping-pong loop (pd_ping_pong).  A new kernel of
+// the family supplies its __global__ function and a launcher struct K with
 //
+//   template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
+//   static int launch_t(const PdLaunchArgs<T> &);   // plan the grid, launch
 //   template <typename T, int VEC, int LX, bool RAG>
-//   static int launch(const PdLaunchArgs<T> &);
+//   static int launch(const PdLaunchArgs<T> &);     // pick the rows per lane
 //
-// which picks the (RY, NDIM) forms the kernel has (pd_auto_rows_per_lane), plans the
-// grid (pd_plan_grid) and launches; its entry calls pd_launch<K>(args) after its own
-// checks.
+// `launch` is the kernel's policy for the rows per lane (pd_auto_rows_per_lane, a
+// knob) and a call of pd_launch_forms; the kernel's entry calls pd_launch<K>(args)
+// after its own checks.  (FusedKernel and IsoKernel spell their forms out: k_pd_fused
+// has four rows per lane as well, and the order in which either unit instantiates its
+// forms is the order of the kernels in its code object, which stays as it is.)
 #pragma once
+
+#include <stddef.h>
+#include <string.h>
 
 #include "nsol_pd_common.hpp"
 
@@ -34,6 +45,10 @@ PdScalars<T> pd_make_scalars(double sigma, double hden, double tau, double tl,
   return S;
 }
 
+// The tune of every kernel the pd_* knobs do not reach (the stacked and the linear
+// ones): automatic z chunks and rows per lane, the XCD map and the ragged form on.
+constexpr PdLaunchTune kPdStackTune{0, 0, 1, 1};
+
 template <typename T>
 struct PdLaunchArgs {
   const T *xbar_in; T *xbar_out; T *x; const T *bt; const T *p_in; T *p_out;
@@ -41,7 +56,7 @@ struct PdLaunchArgs {
   PdScalars<T> S;                     // the single-volume kernels' scalars, or
   const PdScalars<T> *row = nullptr;  // the stacked kernel's table row (device)
   int members = 1;                    // volumes stacked along gridDim.y
-  PdLaunchTune tune{0, 0, 1, 1};
+  PdLaunchTune tune = kPdStackTune;   // the single-volume entries put the knobs here
   hipStream_t st = nullptr;
   const T *wt = nullptr;              // the weighted kernel's per-voxel weights and
   int64_t bt_stride = 0, wt_stride = 0;  // its member strides of bt / wt (0 or G.n)
@@ -96,6 +111,52 @@ int pd_auto_rows_per_lane(const Geom<T> &G, int members) {
   return (tiles * ((G.nz + 1) / 2) < 512) ? 1 : 2;
 }
 
+// The most workgroups along gridDim.x any access form and rows-per-lane choice of
+// pd_launch can ask for on this geometry: with ONE member, as the z chunks only grow
+// with the tiles the members add.  VW: elements per 16-byte access.
+template <int VW>
+int64_t pd_max_blocks(const Geom<float> &G, const PdLaunchTune &tune) {
+  int64_t b = 0;
+  auto take = [&](const PdGridPlan &g) { if (g.blocks > b) b = g.blocks; };
+  take(pd_plan_grid<VW, 64, 1>(G, 1, tune)); take(pd_plan_grid<VW, 64, 2>(G, 1, tune));
+  take(pd_plan_grid<VW, 16, 1>(G, 1, tune)); take(pd_plan_grid<VW, 16, 2>(G, 1, tune));
+  take(pd_plan_grid<1, 64, 1>(G, 1, tune));  take(pd_plan_grid<1, 64, 2>(G, 1, tune));
+  take(pd_plan_grid<1, 16, 1>(G, 1, tune));  take(pd_plan_grid<1, 16, 2>(G, 1, tune));
+  return b;
+}
+
+// What the kernels take: a geometry of the single-volume kernels, at least one
+// member and no more than the grid's y extent, all members together within 2^31
+// voxels.  A single volume is members = 1.
+inline bool pd_members_ok(int members) { return members >= 1 && members <= 65535; }
+inline bool pd_stack_takes(int members, int ndim, int64_t nz, int64_t ny, int64_t nx) {
+  if (!pd_members_ok(members)) return false;
+  if (!geom_ok(ndim, nz, ny, nx)) return false;
+  // (step by step: the product of three extents near 2^31 does not fit an int64)
+  const int64_t cap = (int64_t(1) << 31) / members;
+  return nx <= cap && ny <= cap / nx && nz <= cap / (nx * ny);
+}
+
+// a member stride is 0 (one array for all members) or n (member-major rows)
+inline bool pd_stride_ok(int64_t stride, int64_t n) { return stride == 0 || stride == n; }
+
+// The (RY, NDIM) forms every kernel of the family has: one or two rows per lane in
+// 2-D and 3-D, one in 1-D.  ry (1 or 2) is the launcher's choice; A is PdLaunchArgs
+// or what the launcher derives from it.
+template <typename K, typename T, int VEC, int LX, bool RAG, typename A>
+int pd_launch_forms(const A &a, int ry) {
+  const bool two_rows = ry == 2;
+  switch (a.G.ndim) {
+    case 1: return K::template launch_t<T, VEC, LX, 1, 1, RAG>(a);
+    case 2:
+      return two_rows ? K::template launch_t<T, VEC, LX, 2, 2, RAG>(a)
+                      : K::template launch_t<T, VEC, LX, 1, 2, RAG>(a);
+    default:
+      return two_rows ? K::template launch_t<T, VEC, LX, 2, 3, RAG>(a)
+                      : K::template launch_t<T, VEC, LX, 1, 3, RAG>(a);
+  }
+}
+
 // Access form: whole 16-byte vectors when every row and array allows them, else
 // element-aligned 16-byte accesses with the row's last vector ragged (knob
 // "pd_rag" = 0 restores the 4-byte form, for the tests), else single elements;
@@ -122,6 +183,54 @@ int pd_launch(const PdLaunchArgs<T> &a) {
   }
   if (G.nx >= kWave) return K::template launch<T, 1, 64, false>(a);
   return K::template launch<T, 1, 16, false>(a);
+}
+
+// The table of a stacked run, [iteration][member], from the host schedules
+// (lmbda[member], sig/tau/theta[member][iteration]): rounded as a single run's
+// scalars are, written to the pinned tab_host and uploaded once on the stream.
+// members is the caller's to check (pd_stack_takes, pd_members_ok).
+template <typename T>
+int pd_table_fill_upload(int members, const double *lmbda, const double *sig,
+                         const double *tau, const double *theta, int iterations,
+                         int p_is_zero, double gamma_huber, int flags, void *tab_host,
+                         void *tab, int64_t tab_bytes, hipStream_t st) {
+  if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
+      tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)
+    return NSOL_EINVAL;
+  const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
+  PdScalars<T> *h = static_cast<PdScalars<T> *>(tab_host);
+  for (int n = 0; n < iterations; ++n)
+    for (int m = 0; m < members; ++m) {
+      const int64_t k = (int64_t)m * iterations + n;
+      const double tl = tau[k] * lmbda[m];
+      const PdScalars<T> S = pd_make_scalars<T>(
+          sig[k], huber ? 1.0 + sig[k] * gamma_huber : 1.0, tau[k], tl, theta[k], flags,
+          !(n == 0 && p_is_zero));
+      // the table is uploaded as bytes: no stale padding behind the last member
+      PdScalars<T> &row = h[(int64_t)n * members + m];
+      memset(&row, 0, sizeof(row));
+      memcpy(&row, &S, offsetof(PdScalars<T>, has_p) + sizeof(S.has_p));
+    }
+  if (iterations > 0) {
+    hipError_t e = hipMemcpyAsync(tab, tab_host,
+                                  sizeof(PdScalars<T>) * (size_t)members * iterations,
+                                  hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+// The iterations of a run over its ping-pong buffers: iter(n, slot) reads slot and
+// writes slot ^ 1; *final_slot is the slot that holds the final state.
+template <typename F>
+int pd_ping_pong(int iterations, int *final_slot, F iter) {
+  int slot = 0;
+  for (int n = 0; n < iterations; ++n, slot ^= 1) {
+    const int rc = iter(n, slot);
+    if (rc) return rc;     // (-2 can only come from the first launch: nothing ran)
+  }
+  if (final_slot) *final_slot = slot;
+  return 0;
 }
 
 }  // namespace nsol

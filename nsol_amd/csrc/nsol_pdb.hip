@@ -19,10 +19,6 @@
 //
 // k_scale_rows is the set-up's companion: row m of a (P, n) array divided or
 // multiplied by the member's own scale s[m], one launch for the stack.
-#include <stddef.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <atomic>
 
 #include "nsol_common.hpp"
@@ -72,8 +68,8 @@ __global__ __launch_bounds__(kBlock) void k_pd_batch_iso(
                                                ty, zc, zchunk);
 }
 
-// The launcher structs of nsol_pd_launch.hpp: the (RY, NDIM) forms of SweepKernel /
-// IsoKernel, the members counted as tiles in the grid and in the rows per lane.
+// The launcher structs of nsol_pd_launch.hpp: the members count as tiles in the grid
+// and in the rows per lane.
 template <bool ISO>
 struct BatchLauncher {
   template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
@@ -96,30 +92,12 @@ struct BatchLauncher {
 
   template <typename T, int VEC, int LX, bool RAG>
   static int launch(const PdLaunchArgs<T> &a) {
-    const bool two_rows = pd_auto_rows_per_lane<VEC, LX>(a.G, a.members) == 2;
-    switch (a.G.ndim) {
-      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
-      case 2:
-        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
-      default:
-        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
-    }
+    return pd_launch_forms<BatchLauncher<ISO>, T, VEC, LX, RAG>(
+        a, pd_auto_rows_per_lane<VEC, LX>(a.G, a.members));
   }
 };
 using BatchKernel = BatchLauncher<false>;
 using BatchIsoKernel = BatchLauncher<true>;
-
-// What the stacked kernels take -- the sweep's conditions (nsol_pds.hip): a geometry
-// the single-volume kernels take, at least one member, all members together within
-// 2^31 voxels, members within the grid's y extent.
-inline bool batch_takes(int members, int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  if (members < 1 || members > 65535) return false;
-  if (!geom_ok(ndim, nz, ny, nx)) return false;
-  const int64_t n = nz * ny * nx;
-  return n <= (int64_t(1) << 31) / members;
-}
 
 template <typename T>
 int batch_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p_in,
@@ -127,17 +105,14 @@ int batch_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p
                     double wx, double wy, double wz, const void *tab, int iteration,
                     int flags, void *stream) {
   if (flags & NSOL_PD_DATA_WEIGHTED) return -2;   // no weights pointer here: nsol_pdw.hip
-  if (!batch_takes(members, ndim, nz, ny, nx)) return -2;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   if (!xbar_in || !xbar_out || !x || !bt || !p_in || !p_out || !tab || iteration < 0 ||
       xbar_in == xbar_out || p_in == p_out)
     return NSOL_EINVAL;
   PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
                     make_geom<T>(ndim, nz, ny, nx, wx, wy, wz)};
   a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
-  a.members = members;
-  // as the sweep: automatic z chunks and rows per lane, the XCD map and the ragged
-  // form on
-  a.tune = PdLaunchTune{0, 0, 1, 1};
+  a.members = members;    // (the pd_* knobs do not reach the stack: kPdStackTune)
   a.st = as_stream(stream);
   if (flags & NSOL_PD_REG_ISOTROPIC) return pd_launch<BatchIsoKernel>(a);
   return pd_launch<BatchKernel>(a);
@@ -151,42 +126,19 @@ int batch_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int memb
                    int flags, void *tab_host, void *tab, int64_t tab_bytes,
                    int *final_slot, void *stream) {
   if (flags & NSOL_PD_DATA_WEIGHTED) return -2;   // no weights pointer here: nsol_pdw.hip
-  if (!batch_takes(members, ndim, nz, ny, nx)) return -2;
-  if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
-      tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)
-    return NSOL_EINVAL;
-  const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   // the table, [iteration][member], rounded as a single run's scalars are
-  PdScalars<T> *h = static_cast<PdScalars<T> *>(tab_host);
-  for (int n = 0; n < iterations; ++n)
-    for (int m = 0; m < members; ++m) {
-      const int64_t k = (int64_t)m * iterations + n;
-      const double tl = tau[k] * lmbda[m];
-      const PdScalars<T> S = pd_make_scalars<T>(
-          sig[k], huber ? 1.0 + sig[k] * gamma_huber : 1.0, tau[k], tl, theta[k], flags,
-          !(n == 0 && p_is_zero));
-      // the table is uploaded as bytes: no stale padding behind the last member
-      PdScalars<T> &row = h[(int64_t)n * members + m];
-      memset(&row, 0, sizeof(row));
-      memcpy(&row, &S, offsetof(PdScalars<T>, has_p) + sizeof(S.has_p));
-    }
-  if (iterations > 0) {
-    hipError_t e = hipMemcpyAsync(tab, tab_host,
-                                  sizeof(PdScalars<T>) * (size_t)members * iterations,
-                                  hipMemcpyHostToDevice, as_stream(stream));
-    if (e != hipSuccess) return (int)e;
-  }
+  const int rc = pd_table_fill_upload<T>(members, lmbda, sig, tau, theta, iterations,
+                                         p_is_zero, gamma_huber, flags, tab_host, tab,
+                                         tab_bytes, as_stream(stream));
+  if (rc) return rc;
   T *xb[2] = {xbar0, xbar1};
   T *pp[2] = {p0, p1};
-  int slot = 0;
-  for (int n = 0; n < iterations; ++n, slot ^= 1) {
-    const int rc = batch_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, pp[slot], pp[slot ^ 1],
-                                      members, ndim, nz, ny, nx, wx, wy, wz, tab, n,
-                                      flags, stream);
-    if (rc) return rc;     // (-2 can only come from the first launch: nothing ran)
-  }
-  if (final_slot) *final_slot = slot;
-  return 0;
+  return pd_ping_pong(iterations, final_slot, [&](int n, int slot) {
+    return batch_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, pp[slot], pp[slot ^ 1],
+                              members, ndim, nz, ny, nx, wx, wy, wz, tab, n, flags,
+                              stream);
+  });
 }
 
 // ---------------------------------------------------------------------------

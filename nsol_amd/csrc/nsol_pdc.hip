@@ -18,10 +18,10 @@
 // k_pd_change: the same four sums from (x_old, x_new) and (p_old, p_new) in memory,
 // for the loops of separate kernels.
 //
-// Reduction (the scheme of nsol_observe.hip): wave shuffle, one partial per workgroup
-// and sum in ws[sum * nparts + workgroup], then ONE closing workgroup that adds the
-// partials in a fixed order into row[0..3].  No floating-point atomics: the same
-// input gives the same bits on every run.
+// Reduction (nsol_pd_sums.hpp): wave shuffle, one partial per workgroup and sum in
+// ws[sum * nparts + workgroup], then ONE closing workgroup that adds the partials in
+// a fixed order into row[0..3].  No floating-point atomics: the same input gives the
+// same bits on every run.
 #include <stddef.h>
 
 #include "nsol_common.hpp"
@@ -29,59 +29,20 @@
 #include "nsol_pd_fused_body.hpp"
 #include "nsol_pd_iso_body.hpp"
 #include "nsol_pd_launch.hpp"
+#include "nsol_pd_sums.hpp"
 #include "nsol_pd_weighted.hpp"
 
 using namespace nsol;
 
 namespace {
 
-constexpr int kChkSums = 4;
-constexpr int kChkWaves = kBlock / kWave;
-
-__device__ __forceinline__ double chk_wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;
-}
-
-// the workgroup's partial of every sum into ws[k * nparts + blockIdx.x]; called by
-// all threads of the workgroup
-__device__ __forceinline__ void chk_block_store(const double (&a)[kChkSums],
-                                                double *__restrict__ ws, int nparts) {
-  __shared__ double s[kChkSums][kChkWaves];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < kChkSums; ++k) {
-    const double v = chk_wave_sum(a[k]);
-    if (lane == 0) s[k][wv] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kChkSums) {
-    const int k = threadIdx.x;
-    double t = s[k][0];
-    for (int w = 1; w < kChkWaves; ++w) t += s[k][w];
-    ws[(int64_t)k * nparts + blockIdx.x] = t;
-  }
-}
-
 // the partials of every sum in a fixed order into row[0..3]; one workgroup
 __global__ __launch_bounds__(kBlock) void k_pd_check_final(const double *__restrict__ ws,
                                                            int nparts,
                                                            double *__restrict__ row) {
-  __shared__ double s[kChkWaves];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  for (int k = 0; k < kChkSums; ++k) {
-    double v = 0.0;
-    for (int j = threadIdx.x; j < nparts; j += kBlock) v += ws[(int64_t)k * nparts + j];
-    v = chk_wave_sum(v);
-    if (lane == 0) s[wv] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int w = 0; w < kChkWaves; ++w) t += s[w];
-      row[k] = t;
-    }
-    __syncthreads();
+  for (int k = 0; k < kPdSums; ++k) {
+    const double t = pd_parts_sum(ws + (int64_t)k * nparts, nparts);
+    if (threadIdx.x == 0) row[k] = t;
   }
 }
 
@@ -93,13 +54,13 @@ __global__ __launch_bounds__(kBlock) void k_pd_check(
     const T *__restrict__ bt, const T *__restrict__ wt, const T *__restrict__ p_in,
     T *__restrict__ p_out, Geom<T> G, PdScalars<T> S, int ntx, int nty, int zchunk,
     int slab, double *__restrict__ ws) {
-  double a[kChkSums] = {0.0, 0.0, 0.0, 0.0};
+  double a[kPdSums] = {0.0, 0.0, 0.0, 0.0};
   int tx, ty, zc;
   if (pd_fused_block_tile(blockIdx.x, ntx, nty, slab, tx, ty, zc))
     pd_fused_tile<T, VEC, LX, RY, NDIM, RAG, WGT, true>(xbar_in, xbar_out, x, bt, p_in,
                                                         p_out, G, S, tx, ty, zc, zchunk,
                                                         wt, a);
-  chk_block_store(a, ws, (int)gridDim.x);
+  pd_block_store(a, ws, (int)gridDim.x, 0);
 }
 
 template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT>
@@ -108,13 +69,13 @@ __global__ __launch_bounds__(kBlock) void k_pd_check_iso(
     const T *__restrict__ bt, const T *__restrict__ wt, const T *__restrict__ p_in,
     T *__restrict__ p_out, Geom<T> G, PdScalars<T> S, int ntx, int nty, int zchunk,
     int slab, double *__restrict__ ws) {
-  double a[kChkSums] = {0.0, 0.0, 0.0, 0.0};
+  double a[kPdSums] = {0.0, 0.0, 0.0, 0.0};
   int tx, ty, zc;
   if (pd_fused_block_tile(blockIdx.x, ntx, nty, slab, tx, ty, zc))
     pd_fused_iso_tile<T, VEC, LX, RY, NDIM, RAG, WGT, true>(xbar_in, xbar_out, x, bt,
                                                             p_in, p_out, G, S, tx, ty, zc,
                                                             zchunk, wt, a);
-  chk_block_store(a, ws, (int)gridDim.x);
+  pd_block_store(a, ws, (int)gridDim.x, 0);
 }
 
 // rows per lane: the knob "pd_ry" as k_pd_fused reads it (4 has no form here and
@@ -133,7 +94,7 @@ struct CheckLauncher {
     const PdGridPlan g = pd_plan_grid<VEC, LX, RY>(a.G, 1, a.tune);
     if (g.blocks > kPdMaxBlocks) return -2;
     // one partial per workgroup and sum: the caller's workspace must hold them
-    if (g.blocks > a.chk_ws_doubles / kChkSums) return NSOL_EINVAL;
+    if (g.blocks > a.chk_ws_doubles / kPdSums) return NSOL_EINVAL;
     if constexpr (ISO)
       hipLaunchKernelGGL((k_pd_check_iso<T, VEC, LX, RY, NDIM, RAG, WGT>),
                          dim3((unsigned)g.blocks), dim3(kBlock), 0, a.st, a.xbar_in,
@@ -153,41 +114,10 @@ struct CheckLauncher {
 
   template <typename T, int VEC, int LX, bool RAG>
   static int launch(const PdLaunchArgs<T> &a) {
-    const bool two_rows = check_rows_per_lane<VEC, LX>(a.G, a.tune) == 2;
-    switch (a.G.ndim) {
-      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
-      case 2:
-        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
-      default:
-        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
-    }
+    return pd_launch_forms<CheckLauncher<ISO, WGT>, T, VEC, LX, RAG>(
+        a, check_rows_per_lane<VEC, LX>(a.G, a.tune));
   }
 };
-
-// what the kernels take: a geometry of the one-iteration kernels within 2^31 voxels
-inline bool check_takes(int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  if (!geom_ok(ndim, nz, ny, nx)) return false;
-  // (step by step: the product of three extents near 2^31 does not fit an int64)
-  const int64_t cap = int64_t(1) << 31;
-  return nx <= cap && ny <= cap / nx && nz <= cap / (nx * ny);
-}
-
-// The most workgroups any access form and rows-per-lane choice of pd_launch can ask
-// for on this geometry with the knobs as they stand.
-template <int VW>
-int64_t check_max_blocks(int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  const Geom<float> G = make_geom<float>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
-  const PdLaunchTune tune = pd_current_tune();
-  int64_t b = 0;
-  auto take = [&](const PdGridPlan &g) { if (g.blocks > b) b = g.blocks; };
-  take(pd_plan_grid<VW, 64, 1>(G, 1, tune)); take(pd_plan_grid<VW, 64, 2>(G, 1, tune));
-  take(pd_plan_grid<VW, 16, 1>(G, 1, tune)); take(pd_plan_grid<VW, 16, 2>(G, 1, tune));
-  take(pd_plan_grid<1, 64, 1>(G, 1, tune));  take(pd_plan_grid<1, 64, 2>(G, 1, tune));
-  take(pd_plan_grid<1, 16, 1>(G, 1, tune));  take(pd_plan_grid<1, 16, 2>(G, 1, tune));
-  return b;
-}
 
 template <typename T>
 int check_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *wt,
@@ -195,10 +125,10 @@ int check_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *w
                     double wx, double wy, double wz, double sigma, double hden, double tau,
                     double tl, double theta, int flags, double *ws, int64_t ws_doubles,
                     double *row, void *stream) {
-  if (!check_takes(ndim, nz, ny, nx)) return -2;
+  if (!pd_stack_takes(1, ndim, nz, ny, nx)) return -2;
   const bool weighted = (flags & NSOL_PD_DATA_WEIGHTED) != 0;
   if (!xbar_in || !xbar_out || !x || !bt || !p_out || xbar_in == xbar_out ||
-      p_in == p_out || !ws || !row || ws_doubles < kChkSums || weighted != (wt != nullptr))
+      p_in == p_out || !ws || !row || ws_doubles < kPdSums || weighted != (wt != nullptr))
     return NSOL_EINVAL;
   PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
                     make_geom<T>(ndim, nz, ny, nx, wx, wy, wz),
@@ -227,23 +157,23 @@ __global__ __launch_bounds__(kBlock) void k_pd_change(
     const T *__restrict__ x_old, const T *__restrict__ x_new, int64_t n,
     const T *__restrict__ p_old, const T *__restrict__ p_new, int64_t np,
     double *__restrict__ ws) {
-  double a[kChkSums] = {0.0, 0.0, 0.0, 0.0};
+  double a[kPdSums] = {0.0, 0.0, 0.0, 0.0};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   for (int64_t i = first; i < n; i += stride) chk_add(a[0], a[1], x_old[i], x_new[i]);
   for (int64_t i = first; i < np; i += stride)
     chk_add(a[2], a[3], p_old ? p_old[i] : T(0), p_new[i]);
-  chk_block_store(a, ws, (int)gridDim.x);
+  pd_block_store(a, ws, (int)gridDim.x, 0);
 }
 
 template <typename T>
 int change_impl(const T *x_old, const T *x_new, int64_t n, const T *p_old, const T *p_new,
                 int64_t np, double *ws, int64_t ws_doubles, double *row, void *stream) {
   if (!x_old || !x_new || !p_new || n < 1 || np < 1 || !ws || !row ||
-      ws_doubles < kChkSums)
+      ws_doubles < kPdSums)
     return NSOL_EINVAL;
   int64_t g = grid_for(n > np ? n : np);
-  if (g > ws_doubles / kChkSums) g = ws_doubles / kChkSums;
+  if (g > ws_doubles / kPdSums) g = ws_doubles / kPdSums;
   hipLaunchKernelGGL(k_pd_change<T>, dim3((unsigned)g), dim3(kBlock), 0,
                      as_stream(stream), x_old, x_new, n, p_old, p_new, np, ws);
   int rc = launch_status();
@@ -259,12 +189,15 @@ extern "C" {
 
 int64_t nsol_pd_check_ws_doubles(int elem_size, int ndim, int64_t nz, int64_t ny,
                                  int64_t nx) {
-  if ((elem_size != 4 && elem_size != 8) || !check_takes(ndim, nz, ny, nx)) return -1;
-  int64_t b = elem_size == 4 ? check_max_blocks<4>(ndim, nz, ny, nx)
-                             : check_max_blocks<2>(ndim, nz, ny, nx);
+  if ((elem_size != 4 && elem_size != 8) || !pd_stack_takes(1, ndim, nz, ny, nx))
+    return -1;
+  // the most workgroups a launch can ask for with the knobs as they stand
+  const Geom<float> G = make_geom<float>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
+  const PdLaunchTune tune = pd_current_tune();
+  int64_t b = elem_size == 4 ? pd_max_blocks<4>(G, tune) : pd_max_blocks<2>(G, tune);
   // (nsol_pd_change_* never needs more than the grid-stride cap)
   if (b < kMaxGridBlocksLimit) b = kMaxGridBlocksLimit;
-  return kChkSums * b;
+  return kPdSums * b;
 }
 
 #define NSOL_PDC_DEF(T, SUF)                                                           \

@@ -60,8 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_pd_lin_iso(
       lo, hi);
 }
 
-// The launcher struct of nsol_pd_launch.hpp: the (RY, NDIM) forms of k_pd_batch, one
-// volume.
+// The launcher struct of nsol_pd_launch.hpp, one volume.
 template <bool ISO>
 struct LinLauncher {
   template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
@@ -84,16 +83,8 @@ struct LinLauncher {
 
   template <typename T, int VEC, int LX, bool RAG>
   static int launch(const PdLaunchArgs<T> &a) {
-    const bool two_rows = pd_auto_rows_per_lane<VEC, LX>(a.G, 1) == 2;
-    switch (a.G.ndim) {
-      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
-      case 2:
-        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
-      default:
-        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
-    }
+    return pd_launch_forms<LinLauncher<ISO>, T, VEC, LX, RAG>(
+        a, pd_auto_rows_per_lane<VEC, LX>(a.G, 1));
   }
 };
 
@@ -118,10 +109,7 @@ int lin_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *g, const T *p_in
                   double wy, double wz, double sigma, double hden, double tau,
                   double theta, double lo, double hi, int flags, int has_p,
                   void *stream) {
-  if (!geom_ok(ndim, nz, ny, nx)) return -2;
-  // (nz * ny * nx without overflow: each factor is checked against what is left)
-  const int64_t cap = int64_t(1) << 31;
-  if (nx > cap || ny > cap / nx || nz > cap / (nx * ny)) return -2;
+  if (!pd_stack_takes(1, ndim, nz, ny, nx)) return -2;
   if (!xbar_in || !xbar_out || !x || !g || !p_in || !p_out || xbar_in == xbar_out ||
       p_in == p_out || !(lo <= hi) ||
       (flags & ~(NSOL_PD_REG_HUBER | NSOL_PD_REG_ISOTROPIC)))
@@ -129,9 +117,7 @@ int lin_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *g, const T *p_in
   PdLaunchArgs<T> a{xbar_in, xbar_out, x, g, p_in, p_out,
                     make_geom<T>(ndim, nz, ny, nx, wx, wy, wz),
                     pd_make_scalars<T>(sigma, hden, tau, 0.0, theta, flags, has_p != 0)};
-  // as the stacked kernels: automatic z chunks and rows per lane, the XCD map and the
-  // ragged form on
-  a.tune = PdLaunchTune{0, 0, 1, 1};
+  // (the pd_* knobs do not reach this kernel: kPdStackTune)
   a.st = as_stream(stream);
   box_in<T>(lo, hi, a.lo, a.hi);
   if (flags & NSOL_PD_REG_ISOTROPIC) return pd_launch<LinLauncher<true>>(a);

@@ -4,7 +4,7 @@
 // by one iteration in one launch, and a member that has stopped leaves the grid
 // without any array being re-laid.
 //
-// One kernel family, k_pd_stack / k_pd_stack_iso: everything is k_pd_w's (nsol_pdw.hip)
+// One kernel family, k_pd_stack / k_pd_stack_iso: the layout is k_pd_w's (nsol_pdw.hip)
 // -- the tile bodies pd_fused_tile / pd_fused_iso_tile on the member's own slice with
 // the member-local geometry, the scalars from the row PdScalars[iteration][member] of a
 // device table, bt and wt at a member stride of 0 or n -- except that the member is not
@@ -38,6 +38,7 @@
 #include "nsol_pd_fused_body.hpp"
 #include "nsol_pd_iso_body.hpp"
 #include "nsol_pd_launch.hpp"
+#include "nsol_pd_sums.hpp"
 #include "nsol_pd_weighted.hpp"
 
 using namespace nsol;
@@ -45,9 +46,6 @@ using namespace nsol;
 namespace {
 
 std::atomic<int> g_stack_launches{0};
-
-constexpr int kStkSums = 4;
-constexpr int kStkWaves = kBlock / kWave;
 
 // the checking kernel's last argument; nothing at all with CHK off
 template <bool CHK>
@@ -57,56 +55,17 @@ struct StackWs {
 template <>
 struct StackWs<false> {};
 
-__device__ __forceinline__ double stk_wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;
-}
-
-// chk_block_store of nsol_pdc.hip with the grid row in the address: the workgroup's
-// partial of every sum into ws[(blockIdx.y * 4 + k) * nparts + blockIdx.x]; called by
-// all threads of the workgroup
-__device__ __forceinline__ void stk_block_store(const double (&a)[kStkSums],
-                                                double *__restrict__ ws, int nparts) {
-  __shared__ double s[kStkSums][kStkWaves];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < kStkSums; ++k) {
-    const double v = stk_wave_sum(a[k]);
-    if (lane == 0) s[k][wv] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kStkSums) {
-    const int k = threadIdx.x;
-    double t = s[k][0];
-    for (int w = 1; w < kStkWaves; ++w) t += s[k][w];
-    ws[((int64_t)blockIdx.y * kStkSums + k) * nparts + blockIdx.x] = t;
-  }
-}
-
 // gridDim.x = active members: grid row r adds its nparts partials of every sum in a
 // fixed order into rows[map[r] * 4 + k]
 __global__ __launch_bounds__(kBlock) void k_pd_stack_final(
     const double *__restrict__ ws, int nparts, const int *__restrict__ map, int members,
     double *__restrict__ rows) {
-  __shared__ double s[kStkWaves];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const int64_t r = blockIdx.x;
   const int m = map[r];
   const bool mine = (unsigned)m < (unsigned)members;   // (uniform; see k_pd_stack)
-  for (int k = 0; k < kStkSums; ++k) {
-    const double *part = ws + (r * kStkSums + k) * nparts;
-    double v = 0.0;
-    for (int j = threadIdx.x; j < nparts; j += kBlock) v += part[j];
-    v = stk_wave_sum(v);
-    if (lane == 0) s[wv] = v;
-    __syncthreads();
-    if (threadIdx.x == 0 && mine) {
-      double t = 0.0;
-      for (int w = 0; w < kStkWaves; ++w) t += s[w];
-      rows[(int64_t)m * kStkSums + k] = t;
-    }
-    __syncthreads();
+  for (int k = 0; k < kPdSums; ++k) {
+    const double t = pd_parts_sum(ws + (r * kPdSums + k) * nparts, nparts);
+    if (threadIdx.x == 0 && mine) rows[(int64_t)m * kPdSums + k] = t;
   }
 }
 
@@ -120,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_pd_stack(
     T *__restrict__ p_out, Geom<T> G, const PdScalars<T> *__restrict__ tab,
     const int *__restrict__ map, int members, int64_t bt_stride, int64_t wt_stride,
     int ntx, int nty, int zchunk, int slab, StackWs<CHK> ws) {
-  double a[kStkSums] = {0.0, 0.0, 0.0, 0.0};
+  double a[kPdSums] = {0.0, 0.0, 0.0, 0.0};
   int tx, ty, zc;
   // the member of this grid row: uniform per workgroup, read once
   const int64_t m = map[blockIdx.y];
@@ -133,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void k_pd_stack(
         xbar_in + xo, xbar_out + xo, x + xo, bt + m * bt_stride, p_in + po, p_out + po,
         G, S, tx, ty, zc, zchunk, WGT ? wt + m * wt_stride : nullptr, a);
   }
-  if constexpr (CHK) stk_block_store(a, ws.p, (int)gridDim.x);
+  if constexpr (CHK) pd_block_store(a, ws.p, (int)gridDim.x, blockIdx.y);
 }
 
 template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG, bool WGT, bool CHK>
@@ -143,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_pd_stack_iso(
     T *__restrict__ p_out, Geom<T> G, const PdScalars<T> *__restrict__ tab,
     const int *__restrict__ map, int members, int64_t bt_stride, int64_t wt_stride,
     int ntx, int nty, int zchunk, int slab, StackWs<CHK> ws) {
-  double a[kStkSums] = {0.0, 0.0, 0.0, 0.0};
+  double a[kPdSums] = {0.0, 0.0, 0.0, 0.0};
   int tx, ty, zc;
   const int64_t m = map[blockIdx.y];
   if (pd_fused_block_tile(blockIdx.x, ntx, nty, slab, tx, ty, zc) &&
@@ -155,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void k_pd_stack_iso(
         xbar_in + xo, xbar_out + xo, x + xo, bt + m * bt_stride, p_in + po, p_out + po,
         G, S, tx, ty, zc, zchunk, WGT ? wt + m * wt_stride : nullptr, a);
   }
-  if constexpr (CHK) stk_block_store(a, ws.p, (int)gridDim.x);
+  if constexpr (CHK) pd_block_store(a, ws.p, (int)gridDim.x, blockIdx.y);
 }
 
 // what a launch needs beyond PdLaunchArgs (whose `members` is the ACTIVE count here:
@@ -167,8 +126,8 @@ struct StackArgs : PdLaunchArgs<T> {
   double *rows = nullptr;     // the board, 4 doubles per member of the group
 };
 
-// The launcher struct of nsol_pd_launch.hpp: BatchLauncher's (RY, NDIM) forms, the
-// active members counted as tiles in the grid and in the rows per lane.
+// The launcher struct of nsol_pd_launch.hpp: the active members count as tiles in the
+// grid and in the rows per lane.
 template <bool ISO, bool WGT, bool CHK>
 struct StackLauncher {
   template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
@@ -178,7 +137,7 @@ struct StackLauncher {
     StackWs<CHK> ws;
     if constexpr (CHK) {
       // one partial per workgroup, sum and active member
-      if (g.blocks > a.chk_ws_doubles / ((int64_t)kStkSums * a.members))
+      if (g.blocks > a.chk_ws_doubles / ((int64_t)kPdSums * a.members))
         return NSOL_EINVAL;
       ws.p = a.chk_ws;
     }
@@ -207,50 +166,10 @@ struct StackLauncher {
   template <typename T, int VEC, int LX, bool RAG>
   static int launch(const PdLaunchArgs<T> &base) {
     const StackArgs<T> &a = static_cast<const StackArgs<T> &>(base);
-    const bool two_rows = pd_auto_rows_per_lane<VEC, LX>(a.G, a.members) == 2;
-    switch (a.G.ndim) {
-      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
-      case 2:
-        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
-      default:
-        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
-    }
+    return pd_launch_forms<StackLauncher<ISO, WGT, CHK>, T, VEC, LX, RAG>(
+        a, pd_auto_rows_per_lane<VEC, LX>(a.G, a.members));
   }
 };
-
-// the tune of every stacked kernel: automatic z chunks and rows per lane, the XCD map
-// and the ragged form on
-constexpr PdLaunchTune kStackTune{0, 0, 1, 1};
-
-// What the kernels take -- the image stack's conditions (batch_takes, nsol_pdb.hip): a
-// geometry the single-volume kernels take, at least one member, all members together
-// within 2^31 voxels, members within the grid's y extent.
-inline bool stack_takes(int members, int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  if (members < 1 || members > 65535) return false;
-  if (!geom_ok(ndim, nz, ny, nx)) return false;
-  const int64_t n = nz * ny * nx;
-  return n <= (int64_t(1) << 31) / members;
-}
-
-// a member stride is 0 (one array for all members) or n (member-major rows)
-inline bool stride_ok(int64_t stride, int64_t n) { return stride == 0 || stride == n; }
-
-// The most workgroups along gridDim.x any access form and rows-per-lane choice of
-// pd_launch can ask for on this geometry: with ONE active member, as the z chunks only
-// grow with the tiles the members add (pd_plan_grid).
-template <int VW>
-int64_t stack_max_blocks(int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  const Geom<float> G = make_geom<float>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
-  int64_t b = 0;
-  auto take = [&](const PdGridPlan &g) { if (g.blocks > b) b = g.blocks; };
-  take(pd_plan_grid<VW, 64, 1>(G, 1, kStackTune)); take(pd_plan_grid<VW, 64, 2>(G, 1, kStackTune));
-  take(pd_plan_grid<VW, 16, 1>(G, 1, kStackTune)); take(pd_plan_grid<VW, 16, 2>(G, 1, kStackTune));
-  take(pd_plan_grid<1, 64, 1>(G, 1, kStackTune));  take(pd_plan_grid<1, 64, 2>(G, 1, kStackTune));
-  take(pd_plan_grid<1, 16, 1>(G, 1, kStackTune));  take(pd_plan_grid<1, 16, 2>(G, 1, kStackTune));
-  return b;
-}
 
 template <bool WGT, bool CHK, typename T>
 int stack_launch(const StackArgs<T> &a, bool iso) {
@@ -267,14 +186,14 @@ int stack_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, int64_t bt
                     int64_t nx, double wx, double wy, double wz, const void *tab,
                     int iteration, int flags, double *ws, int64_t ws_doubles,
                     double *rows, void *stream) {
-  if (!stack_takes(members, ndim, nz, ny, nx)) return -2;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   const int64_t n = nz * ny * nx;
   const bool weighted = (flags & NSOL_PD_DATA_WEIGHTED) != 0;
   if (!xbar_in || !xbar_out || !x || !bt || !p_in || !p_out || !tab || iteration < 0 ||
       xbar_in == xbar_out || p_in == p_out || weighted != (wt != nullptr) ||
-      !stride_ok(bt_stride, n) || (weighted && !stride_ok(wt_stride, n)) ||
+      !pd_stride_ok(bt_stride, n) || (weighted && !pd_stride_ok(wt_stride, n)) ||
       active < 0 || active > members || (active > 0 && !map) ||
-      (rows && (!ws || ws_doubles < (int64_t)kStkSums * active)))
+      (rows && (!ws || ws_doubles < (int64_t)kPdSums * active)))
     return NSOL_EINVAL;
   if (active == 0) return 0;
   // (with whole vectors n is a multiple of the vector, so every member's slice of
@@ -284,8 +203,7 @@ int stack_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, int64_t bt
       PdLaunchArgs<T>{xbar_in, xbar_out, x, bt, p_in, p_out,
                       make_geom<T>(ndim, nz, ny, nx, wx, wy, wz)};
   a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
-  a.members = active;
-  a.tune = kStackTune;
+  a.members = active;     // (the pd_* knobs do not reach the stack: kPdStackTune)
   a.st = as_stream(stream);
   a.wt = wt;
   a.bt_stride = bt_stride;
@@ -311,11 +229,12 @@ int nsol_pd_stack_launches(void) {
 
 int64_t nsol_pd_stack_ws_doubles(int elem_size, int ndim, int64_t nz, int64_t ny,
                                  int64_t nx, int members) {
-  if ((elem_size != 4 && elem_size != 8) || !stack_takes(members, ndim, nz, ny, nx))
+  if ((elem_size != 4 && elem_size != 8) || !pd_stack_takes(members, ndim, nz, ny, nx))
     return -1;
-  const int64_t b = elem_size == 4 ? stack_max_blocks<4>(ndim, nz, ny, nx)
-                                   : stack_max_blocks<2>(ndim, nz, ny, nx);
-  return kStkSums * b * members;
+  const Geom<float> G = make_geom<float>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
+  const int64_t b = elem_size == 4 ? pd_max_blocks<4>(G, kPdStackTune)
+                                   : pd_max_blocks<2>(G, kPdStackTune);
+  return kPdSums * b * members;
 }
 
 #define NSOL_PDM_DEF(T, SUF)                                                           \

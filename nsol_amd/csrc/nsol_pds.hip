@@ -12,10 +12,6 @@
 // offsets the base pointers (x[m n + i], p[m dim n + c n + i]; bt is shared) and
 // selects the row PdScalars[iteration][member] of a device table that
 // nsol_pd_sweep_run_* fills once per run.
-#include <stddef.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <atomic>
 
 #include "nsol_common.hpp"
@@ -66,35 +62,17 @@ struct SweepKernel {
 
   template <typename T, int VEC, int LX, bool RAG>
   static int launch(const PdLaunchArgs<T> &a) {
-    const bool two_rows = pd_auto_rows_per_lane<VEC, LX>(a.G, a.members) == 2;
-    switch (a.G.ndim) {
-      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
-      case 2:
-        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
-      default:
-        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
-    }
+    return pd_launch_forms<SweepKernel, T, VEC, LX, RAG>(
+        a, pd_auto_rows_per_lane<VEC, LX>(a.G, a.members));
   }
 };
-
-// What the stacked kernel takes: a geometry fused_iter_impl (nsol_pd.hip) takes,
-// at least one member, all members together within 2^31 voxels, members within
-// the grid's y extent.
-inline bool sweep_takes(int members, int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  if (members < 1 || members > 65535) return false;
-  if (!geom_ok(ndim, nz, ny, nx)) return false;
-  const int64_t n = nz * ny * nx;
-  return n <= (int64_t(1) << 31) / members;
-}
 
 template <typename T>
 int sweep_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p_in,
                     T *p_out, int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
                     double wx, double wy, double wz, const void *tab, int iteration,
                     void *stream) {
-  if (!sweep_takes(members, ndim, nz, ny, nx)) return -2;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   if (!xbar_in || !xbar_out || !x || !bt || !p_in || !p_out || !tab || iteration < 0 ||
       xbar_in == xbar_out || p_in == p_out)
     return NSOL_EINVAL;
@@ -103,10 +81,7 @@ int sweep_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, const T *p
   PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
                     make_geom<T>(ndim, nz, ny, nx, wx, wy, wz)};
   a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
-  a.members = members;
-  // the pd_* knobs do not reach the stack: automatic z chunks and rows per lane,
-  // the XCD map and the ragged form on
-  a.tune = PdLaunchTune{0, 0, 1, 1};
+  a.members = members;    // (the pd_* knobs do not reach the stack: kPdStackTune)
   a.st = as_stream(stream);
   return pd_launch<SweepKernel>(a);
 }
@@ -121,42 +96,18 @@ int sweep_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, T *p0, T *p1, int memb
   // the stacked kernel shares pd_fused_tile, the component-wise clamp: isotropic
   // sweeps run their members one after the other (nsol_pdi.hip)
   if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return -2;
-  if (!sweep_takes(members, ndim, nz, ny, nx)) return -2;
-  if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
-      tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)
-    return NSOL_EINVAL;
-  const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   // the table, [iteration][member], rounded as a single run's scalars are
-  PdScalars<T> *h = static_cast<PdScalars<T> *>(tab_host);
-  for (int n = 0; n < iterations; ++n)
-    for (int m = 0; m < members; ++m) {
-      const int64_t k = (int64_t)m * iterations + n;
-      const double tl = tau[k] * lmbda[m];
-      const PdScalars<T> S = pd_make_scalars<T>(
-          sig[k], huber ? 1.0 + sig[k] * gamma_huber : 1.0, tau[k], tl, theta[k], flags,
-          !(n == 0 && p_is_zero));
-      // the table is uploaded as bytes: no stale padding behind the last member
-      PdScalars<T> &row = h[(int64_t)n * members + m];
-      memset(&row, 0, sizeof(row));
-      memcpy(&row, &S, offsetof(PdScalars<T>, has_p) + sizeof(S.has_p));
-    }
-  if (iterations > 0) {
-    hipError_t e = hipMemcpyAsync(tab, tab_host,
-                                  sizeof(PdScalars<T>) * (size_t)members * iterations,
-                                  hipMemcpyHostToDevice, as_stream(stream));
-    if (e != hipSuccess) return (int)e;
-  }
+  const int rc = pd_table_fill_upload<T>(members, lmbda, sig, tau, theta, iterations,
+                                         p_is_zero, gamma_huber, flags, tab_host, tab,
+                                         tab_bytes, as_stream(stream));
+  if (rc) return rc;
   T *xb[2] = {xbar0, xbar1};
   T *pp[2] = {p0, p1};
-  int slot = 0;
-  for (int n = 0; n < iterations; ++n, slot ^= 1) {
-    const int rc = sweep_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, pp[slot], pp[slot ^ 1],
-                                      members, ndim, nz, ny, nx, wx, wy, wz, tab, n,
-                                      stream);
-    if (rc) return rc;     // (-2 can only come from the first launch: nothing ran)
-  }
-  if (final_slot) *final_slot = slot;
-  return 0;
+  return pd_ping_pong(iterations, final_slot, [&](int n, int slot) {
+    return sweep_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, pp[slot], pp[slot ^ 1],
+                              members, ndim, nz, ny, nx, wx, wy, wz, tab, n, stream);
+  });
 }
 
 }  // namespace

@@ -19,10 +19,6 @@
 // The stand-alone kernels k_prox_w (nsol_prox_ell2_weighted_* / _ell1_) are what the
 // generic device loop and NumPy callers run; they call the same prox_data_w, so the
 // fused run and the loop of separate kernels give the same bits.
-#include <stddef.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <atomic>
 
 #include "nsol_common.hpp"
@@ -73,8 +69,8 @@ __global__ __launch_bounds__(kBlock) void k_pd_w_iso(
       S, tx, ty, zc, zchunk, wt + m * wt_stride);
 }
 
-// The launcher struct of nsol_pd_launch.hpp: BatchLauncher's (RY, NDIM) forms, the
-// members counted as tiles in the grid and in the rows per lane.
+// The launcher struct of nsol_pd_launch.hpp: the members count as tiles in the grid
+// and in the rows per lane.
 template <bool ISO>
 struct WeightedLauncher {
   template <typename T, int VEC, int LX, int RY, int NDIM, bool RAG>
@@ -98,31 +94,10 @@ struct WeightedLauncher {
 
   template <typename T, int VEC, int LX, bool RAG>
   static int launch(const PdLaunchArgs<T> &a) {
-    const bool two_rows = pd_auto_rows_per_lane<VEC, LX>(a.G, a.members) == 2;
-    switch (a.G.ndim) {
-      case 1: return launch_t<T, VEC, LX, 1, 1, RAG>(a);
-      case 2:
-        return two_rows ? launch_t<T, VEC, LX, 2, 2, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 2, RAG>(a);
-      default:
-        return two_rows ? launch_t<T, VEC, LX, 2, 3, RAG>(a)
-                        : launch_t<T, VEC, LX, 1, 3, RAG>(a);
-    }
+    return pd_launch_forms<WeightedLauncher<ISO>, T, VEC, LX, RAG>(
+        a, pd_auto_rows_per_lane<VEC, LX>(a.G, a.members));
   }
 };
-
-// What the kernels take -- the image stack's conditions (nsol_pdb.hip): a geometry
-// the single-volume kernels take, at least one member, all members together within
-// 2^31 voxels, members within the grid's y extent.
-inline bool weighted_takes(int members, int ndim, int64_t nz, int64_t ny, int64_t nx) {
-  if (members < 1 || members > 65535) return false;
-  if (!geom_ok(ndim, nz, ny, nx)) return false;
-  const int64_t n = nz * ny * nx;
-  return n <= (int64_t(1) << 31) / members;
-}
-
-// a member stride is 0 (one array for all members) or n (member-major rows)
-inline bool stride_ok(int64_t stride, int64_t n) { return stride == 0 || stride == n; }
 
 template <typename T>
 int weighted_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, int64_t bt_stride,
@@ -130,22 +105,19 @@ int weighted_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *bt, int64_t
                        int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
                        double wx, double wy, double wz, const void *tab, int iteration,
                        int flags, void *stream) {
-  if (!weighted_takes(members, ndim, nz, ny, nx)) return -2;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   const int64_t n = nz * ny * nx;
   if (!xbar_in || !xbar_out || !x || !bt || !wt || !p_in || !p_out || !tab ||
       iteration < 0 || xbar_in == xbar_out || p_in == p_out ||
-      !(flags & NSOL_PD_DATA_WEIGHTED) || !stride_ok(bt_stride, n) ||
-      !stride_ok(wt_stride, n))
+      !(flags & NSOL_PD_DATA_WEIGHTED) || !pd_stride_ok(bt_stride, n) ||
+      !pd_stride_ok(wt_stride, n))
     return NSOL_EINVAL;
   // (with whole vectors n is a multiple of the vector, so every member's slice of
   // bt and wt starts a whole number of vectors behind its base, as x's does)
   PdLaunchArgs<T> a{xbar_in, xbar_out, x, bt, p_in, p_out,
                     make_geom<T>(ndim, nz, ny, nx, wx, wy, wz)};
   a.row = static_cast<const PdScalars<T> *>(tab) + (int64_t)iteration * members;
-  a.members = members;
-  // as the other stacked kernels: automatic z chunks and rows per lane, the XCD map
-  // and the ragged form on
-  a.tune = PdLaunchTune{0, 0, 1, 1};
+  a.members = members;    // (the pd_* knobs do not reach the stack: kPdStackTune)
   a.st = as_stream(stream);
   a.wt = wt;
   a.bt_stride = bt_stride;
@@ -161,31 +133,10 @@ int weighted_table_impl(int members, const double *lmbda, const double *sig,
                         const double *tau, const double *theta, int iterations,
                         int p_is_zero, double gamma_huber, int flags, void *tab_host,
                         void *tab, int64_t tab_bytes, void *stream) {
-  if (members < 1 || members > 65535) return -2;
-  if (iterations < 0 || !lmbda || !sig || !tau || !theta || !tab_host || !tab ||
-      tab_bytes < (int64_t)sizeof(PdScalars<T>) * members * iterations)
-    return NSOL_EINVAL;
-  const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
-  PdScalars<T> *h = static_cast<PdScalars<T> *>(tab_host);
-  for (int n = 0; n < iterations; ++n)
-    for (int m = 0; m < members; ++m) {
-      const int64_t k = (int64_t)m * iterations + n;
-      const double tl = tau[k] * lmbda[m];
-      const PdScalars<T> S = pd_make_scalars<T>(
-          sig[k], huber ? 1.0 + sig[k] * gamma_huber : 1.0, tau[k], tl, theta[k], flags,
-          !(n == 0 && p_is_zero));
-      // the table is uploaded as bytes: no stale padding behind the last member
-      PdScalars<T> &row = h[(int64_t)n * members + m];
-      memset(&row, 0, sizeof(row));
-      memcpy(&row, &S, offsetof(PdScalars<T>, has_p) + sizeof(S.has_p));
-    }
-  if (iterations > 0) {
-    hipError_t e = hipMemcpyAsync(tab, tab_host,
-                                  sizeof(PdScalars<T>) * (size_t)members * iterations,
-                                  hipMemcpyHostToDevice, as_stream(stream));
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  if (!pd_members_ok(members)) return -2;
+  return pd_table_fill_upload<T>(members, lmbda, sig, tau, theta, iterations, p_is_zero,
+                                 gamma_huber, flags, tab_host, tab, tab_bytes,
+                                 as_stream(stream));
 }
 
 template <typename T>
@@ -196,27 +147,24 @@ int weighted_run_impl(T *xbar0, T *xbar1, T *x, const T *bt, int64_t bt_stride,
                       const double *theta, int iterations, int p_is_zero,
                       double gamma_huber, int flags, void *tab_host, void *tab,
                       int64_t tab_bytes, int *final_slot, void *stream) {
-  if (!weighted_takes(members, ndim, nz, ny, nx)) return -2;
+  if (!pd_stack_takes(members, ndim, nz, ny, nx)) return -2;
   const int64_t n = nz * ny * nx;
   // everything the launches check, before the table is written or uploaded
   if (!xbar0 || !xbar1 || !x || !bt || !wt || !p0 || !p1 || xbar0 == xbar1 || p0 == p1 ||
-      !(flags & NSOL_PD_DATA_WEIGHTED) || !stride_ok(bt_stride, n) ||
-      !stride_ok(wt_stride, n))
+      !(flags & NSOL_PD_DATA_WEIGHTED) || !pd_stride_ok(bt_stride, n) ||
+      !pd_stride_ok(wt_stride, n))
     return NSOL_EINVAL;
-  int rc = weighted_table_impl<T>(members, lmbda, sig, tau, theta, iterations, p_is_zero,
-                                  gamma_huber, flags, tab_host, tab, tab_bytes, stream);
+  const int rc = weighted_table_impl<T>(members, lmbda, sig, tau, theta, iterations,
+                                        p_is_zero, gamma_huber, flags, tab_host, tab,
+                                        tab_bytes, stream);
   if (rc) return rc;
   T *xb[2] = {xbar0, xbar1};
   T *pp[2] = {p0, p1};
-  int slot = 0;
-  for (int it = 0; it < iterations; ++it, slot ^= 1) {
-    rc = weighted_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, bt_stride, wt, wt_stride,
-                               pp[slot], pp[slot ^ 1], members, ndim, nz, ny, nx, wx, wy,
-                               wz, tab, it, flags, stream);
-    if (rc) return rc;     // (-2 can only come from the first launch: nothing ran)
-  }
-  if (final_slot) *final_slot = slot;
-  return 0;
+  return pd_ping_pong(iterations, final_slot, [&](int it, int slot) {
+    return weighted_iter_impl<T>(xb[slot], xb[slot ^ 1], x, bt, bt_stride, wt, wt_stride,
+                                 pp[slot], pp[slot ^ 1], members, ndim, nz, ny, nx, wx, wy,
+                                 wz, tab, it, flags, stream);
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -1438,6 +1438,71 @@ def sweep_groups(members, group):
     return [(a, min(a + group, members)) for a in range(0, members, group)]
 
 
+def _schedules(members, lmbda, sigma, tau, theta, reshape=False):
+    """The schedules as contiguous float64 arrays, lmbda (members,), the others
+    (members, iterations); reshape: any layout of members * iterations counts (a 1-D
+    schedule for one member)."""
+    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
+    sigma, tau, theta = (np.ascontiguousarray(a, dtype=np.float64)
+                         for a in (sigma, tau, theta))
+    if reshape:
+        sigma, tau, theta = (a.reshape(members, -1) for a in (sigma, tau, theta))
+    if sigma.ndim != 2 or sigma.shape[0] != members or lmbda.size != members or \
+            tau.shape != sigma.shape or theta.shape != sigma.shape:
+        raise ValueError("schedules must be (members, iterations) arrays")
+    return lmbda, sigma, tau, theta
+
+
+def _table_entry_bytes(x):
+    return int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
+
+
+def _table_buffers(x, members, iters):
+    """(pinned host table, device table, bytes) for PdScalars[iters][members]."""
+    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
+    nbytes = max(16, _table_entry_bytes(x) * members * iters)
+    return (torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+            torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes)
+
+
+def _table_keep(tab_host):
+    # the upload is stream-ordered: its pinned source lives until the event has passed
+    ev = torch.cuda.Event()
+    ev.record()
+    _sweep_staging.append((ev, tab_host))
+
+
+def _table_has(tab, x, members, iteration):
+    if int(iteration) < 0 or \
+            tab.numel() < _table_entry_bytes(x) * members * (int(iteration) + 1):
+        raise ValueError("the table has no iteration %d for %d members" %
+                         (iteration, members))
+
+
+def _stacked_run(name, x, operands, members, schedules, p_is_zero, gamma_huber, flags,
+                 wrote):
+    """nsol_<name>_*(operands..., schedules, table buffers, slot, stream): the slot of
+    the final state, or None when the library declined."""
+    import ctypes
+    lmbda, sigma, tau, theta = schedules
+    iters = int(sigma.shape[1])
+    if _pending_runs:
+        settle_persist_runs()     # as pd_run: an earlier persistent run may feed this
+    tab_host, tab, nbytes = _table_buffers(x, members, iters)
+    slot = ctypes.c_int(0)
+    rc = _fn(name, x)(
+        *operands, lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
+        theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber), int(flags),
+        tab_host.data_ptr(), _p(tab), nbytes, ctypes.addressof(slot), stream_ptr())
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_" + name)
+    _wrote(*wrote)
+    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
+    _table_keep(tab_host)
+    return int(slot.value)
+
+
 def pd_sweep_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, tau,
                  theta, p_is_zero, gamma_huber, flags):
     """Enqueue sigma.shape[1] iterations of `members` stacked primal-dual runs that
@@ -1446,7 +1511,6 @@ def pd_sweep_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, t
     lmbda is (members,), sigma/tau/theta (members, iterations).  Returns the slot
     (0/1) of xbar/p that holds the final state, or None when the library declined
     (nothing was launched).  Does not synchronise."""
-    import ctypes
     ndim, nz, ny, nx = dims3(shape)
     members = int(members)
     n = nz * ny * nx
@@ -1458,39 +1522,11 @@ def pd_sweep_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, t
         raise ValueError("operand mismatch: %d members of %d voxels against x[%d], "
                          "bt[%d], p[%d]" % (members, n, x.numel(), bt.numel(),
                                             p0.numel()))
-    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
-    sigma = np.ascontiguousarray(sigma, dtype=np.float64)
-    tau = np.ascontiguousarray(tau, dtype=np.float64)
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    if sigma.ndim != 2 or sigma.shape[0] != members or lmbda.size != members or \
-            tau.shape != sigma.shape or theta.shape != sigma.shape:
-        raise ValueError("schedules must be (members, iterations) arrays")
-    iters = int(sigma.shape[1])
-    if _pending_runs:
-        settle_persist_runs()     # as pd_run: an earlier persistent run may feed this
-    # the upload of a run's table is stream-ordered: its pinned source lives until
-    # the event behind the run has passed
-    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
-    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
-    nbytes = max(16, entry * members * iters)
-    tab_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-    tab = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    slot = ctypes.c_int(0)
-    rc = _fn("pd_sweep_run", x)(
-        _p(xbar0), _p(xbar1), _p(x), _p(bt), _p(p0), _p(p1), members, ndim, nz, ny,
-        nx, w[0], w[1], w[2], lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
-        theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber),
-        int(flags), tab_host.data_ptr(), _p(tab), nbytes, ctypes.addressof(slot),
-        stream_ptr())
-    if rc == -2:
-        return None
-    _lib.check(rc, "nsol_pd_sweep_run")
-    _wrote(xbar0, xbar1, x, p0, p1)
-    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
-    ev = torch.cuda.Event()
-    ev.record()
-    _sweep_staging.append((ev, tab_host))
-    return int(slot.value)
+    return _stacked_run(
+        "pd_sweep_run", x,
+        (_p(xbar0), _p(xbar1), _p(x), _p(bt), _p(p0), _p(p1), members, ndim, nz, ny, nx,
+         w[0], w[1], w[2]), members, _schedules(members, lmbda, sigma, tau, theta),
+        p_is_zero, gamma_huber, flags, (xbar0, xbar1, x, p0, p1))
 
 
 # ----------------------------------------------------------- image stack ----
@@ -1556,7 +1592,6 @@ def pd_batch_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, t
     member-major, and flags may carry PD_REG_ISOTROPIC.  Returns the slot (0/1) of
     xbar/p that holds the final state, or None when the library declined (nothing
     was launched).  Does not synchronise."""
-    import ctypes
     ndim, nz, ny, nx = dims3(shape)
     members = int(members)
     n = nz * ny * nx
@@ -1566,37 +1601,11 @@ def pd_batch_run(xbar0, xbar1, x, bt, p0, p1, members, shape, w, lmbda, sigma, t
             p0.numel() != members * ndim * n:
         raise ValueError("operand mismatch: %d members of %d voxels against x[%d], "
                          "p[%d]" % (members, n, x.numel(), p0.numel()))
-    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
-    sigma = np.ascontiguousarray(sigma, dtype=np.float64)
-    tau = np.ascontiguousarray(tau, dtype=np.float64)
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    if sigma.ndim != 2 or sigma.shape[0] != members or lmbda.size != members or \
-            tau.shape != sigma.shape or theta.shape != sigma.shape:
-        raise ValueError("schedules must be (members, iterations) arrays")
-    iters = int(sigma.shape[1])
-    if _pending_runs:
-        settle_persist_runs()
-    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
-    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
-    nbytes = max(16, entry * members * iters)
-    tab_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-    tab = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    slot = ctypes.c_int(0)
-    rc = _fn("pd_batch_run", x)(
-        _p(xbar0), _p(xbar1), _p(x), _p(bt), _p(p0), _p(p1), members, ndim, nz, ny,
-        nx, w[0], w[1], w[2], lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
-        theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber),
-        int(flags), tab_host.data_ptr(), _p(tab), nbytes, ctypes.addressof(slot),
-        stream_ptr())
-    if rc == -2:
-        return None
-    _lib.check(rc, "nsol_pd_batch_run")
-    _wrote(xbar0, xbar1, x, p0, p1)
-    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
-    ev = torch.cuda.Event()
-    ev.record()
-    _sweep_staging.append((ev, tab_host))
-    return int(slot.value)
+    return _stacked_run(
+        "pd_batch_run", x,
+        (_p(xbar0), _p(xbar1), _p(x), _p(bt), _p(p0), _p(p1), members, ndim, nz, ny, nx,
+         w[0], w[1], w[2]), members, _schedules(members, lmbda, sigma, tau, theta),
+        p_is_zero, gamma_huber, flags, (xbar0, xbar1, x, p0, p1))
 
 
 # ------------------------------------------------- weighted data term ----
@@ -1635,32 +1644,6 @@ def _weighted_operands(x, xbar0, xbar1, bt, wt, p0, p1, members, shape):
             0 if wt.numel() == n else n)
 
 
-def _weighted_schedules(members, lmbda, sigma, tau, theta):
-    lmbda = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
-    sigma = np.ascontiguousarray(sigma, dtype=np.float64).reshape(members, -1)
-    tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(members, -1)
-    theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(members, -1)
-    if lmbda.size != members or tau.shape != sigma.shape or \
-            theta.shape != sigma.shape:
-        raise ValueError("schedules must be (members, iterations) arrays")
-    return lmbda, sigma, tau, theta
-
-
-def _weighted_table_buffers(x, members, iters):
-    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
-    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
-    nbytes = max(16, entry * members * iters)
-    return (torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
-            torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes)
-
-
-def _weighted_table_keep(tab_host):
-    # the upload is stream-ordered: its pinned source lives until the event has passed
-    ev = torch.cuda.Event()
-    ev.record()
-    _sweep_staging.append((ev, tab_host))
-
-
 def pd_weighted_run(xbar0, xbar1, x, bt, wt, p0, p1, members, shape, w, lmbda, sigma,
                     tau, theta, p_is_zero, gamma_huber, flags):
     """Enqueue the iterations of `members` stacked primal-dual runs with a weighted
@@ -1670,29 +1653,15 @@ def pd_weighted_run(xbar0, xbar1, x, bt, wt, p0, p1, members, shape, w, lmbda, s
     sigma/tau/theta (members, iterations) -- or 1-D for one member.  Returns the slot
     (0/1) of xbar/p that holds the final state, or None when the library declined
     (nothing was launched).  Does not synchronise."""
-    import ctypes
     members = int(members)
     ndim, nz, ny, nx, bts, wts = _weighted_operands(x, xbar0, xbar1, bt, wt, p0, p1,
                                                     members, shape)
-    lmbda, sigma, tau, theta = _weighted_schedules(members, lmbda, sigma, tau, theta)
-    iters = int(sigma.shape[1])
-    if _pending_runs:
-        settle_persist_runs()     # as pd_run: an earlier persistent run may feed this
-    tab_host, tab, nbytes = _weighted_table_buffers(x, members, iters)
-    slot = ctypes.c_int(0)
-    rc = _fn("pd_weighted_run", x)(
-        _p(xbar0), _p(xbar1), _p(x), _p(bt), bts, _p(wt), wts, _p(p0), _p(p1), members,
-        ndim, nz, ny, nx, w[0], w[1], w[2], lmbda.ctypes.data, sigma.ctypes.data,
-        tau.ctypes.data, theta.ctypes.data, iters, int(bool(p_is_zero)),
-        float(gamma_huber), int(flags), tab_host.data_ptr(), _p(tab), nbytes,
-        ctypes.addressof(slot), stream_ptr())
-    if rc == -2:
-        return None
-    _lib.check(rc, "nsol_pd_weighted_run")
-    _wrote(xbar0, xbar1, x, p0, p1)
-    tab.record_stream(torch.cuda.current_stream())     # freed once the run is done
-    _weighted_table_keep(tab_host)
-    return int(slot.value)
+    return _stacked_run(
+        "pd_weighted_run", x,
+        (_p(xbar0), _p(xbar1), _p(x), _p(bt), bts, _p(wt), wts, _p(p0), _p(p1), members,
+         ndim, nz, ny, nx, w[0], w[1], w[2]), members,
+        _schedules(members, lmbda, sigma, tau, theta, reshape=True), p_is_zero,
+        gamma_huber, flags, (xbar0, xbar1, x, p0, p1))
 
 
 def pd_weighted_table(like, members, lmbda, sigma, tau, theta, p_is_zero, gamma_huber,
@@ -1700,14 +1669,15 @@ def pd_weighted_table(like, members, lmbda, sigma, tau, theta, p_is_zero, gamma_
     """The device table of a weighted run's scalars ([iteration][member], the element
     type of `like`) for pd_weighted_iter; schedules as in pd_weighted_run."""
     members = int(members)
-    lmbda, sigma, tau, theta = _weighted_schedules(members, lmbda, sigma, tau, theta)
+    lmbda, sigma, tau, theta = _schedules(members, lmbda, sigma, tau, theta,
+                                          reshape=True)
     iters = int(sigma.shape[1])
-    tab_host, tab, nbytes = _weighted_table_buffers(like, members, iters)
+    tab_host, tab, nbytes = _table_buffers(like, members, iters)
     _lib.check(_fn("pd_weighted_table", like)(
         members, lmbda.ctypes.data, sigma.ctypes.data, tau.ctypes.data,
         theta.ctypes.data, iters, int(bool(p_is_zero)), float(gamma_huber), int(flags),
         tab_host.data_ptr(), _p(tab), nbytes, stream_ptr()), "nsol_pd_weighted_table")
-    _weighted_table_keep(tab_host)
+    _table_keep(tab_host)
     return tab
 
 
@@ -1719,10 +1689,7 @@ def pd_weighted_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, members, shape, 
     members = int(members)
     ndim, nz, ny, nx, bts, wts = _weighted_operands(x, xbar_in, xbar_out, bt, wt, p_in,
                                                     p_out, members, shape)
-    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
-    if int(iteration) < 0 or tab.numel() < entry * members * (int(iteration) + 1):
-        raise ValueError("the table has no iteration %d for %d members" %
-                         (iteration, members))
+    _table_has(tab, x, members, iteration)
     rc = _fn("pd_weighted_iter", x)(
         _p(xbar_in), _p(xbar_out), _p(x), _p(bt), bts, _p(wt), wts, _p(p_in), _p(p_out),
         members, ndim, nz, ny, nx, w[0], w[1], w[2], _p(tab), int(iteration), int(flags),
@@ -1927,10 +1894,7 @@ def pd_stack_iter(xbar_in, xbar_out, x, bt, wt, p_in, p_out, members, map, activ
                 rows.dtype != torch.float64 or rows.numel() < PD_CHECK_SUMS * members:
             raise ValueError("rows: a float64 device tensor of %d per member, with a "
                              "float64 workspace" % PD_CHECK_SUMS)
-    entry = int(_lib.load().nsol_pd_sweep_entry_bytes(int(x.element_size())))
-    if int(iteration) < 0 or tab.numel() < entry * members * (int(iteration) + 1):
-        raise ValueError("the table has no iteration %d for %d members" %
-                         (iteration, members))
+    _table_has(tab, x, members, iteration)
     bts = 0 if bt.numel() == n else n
     wts = 0 if wt is None or wt.numel() == n else n
     rc = _fn("pd_stack_iter", x)(
