@@ -148,12 +148,6 @@ class ADMMLinearSolver(LinearSolver):
             self._observe_iteration(i + 1, x)
         self._x = x
 
-    def _observe_iteration(self, it, x):
-        if self._observing_on_device():
-            self._observe_at(it, x)
-        elif self._observer is not None:
-            self._observer.add_x(self.get_x())
-
     _warm = None
     _inner_log = ()
 

@@ -1422,12 +1422,19 @@ def pd_sweep_launches():
     return int(_lib.load().nsol_pd_sweep_launches())
 
 
-def sweep_group_size(members, n, dim, elem_size):
-    """Members per stacked group: as many as keep a group's state under
-    PD_SWEEP_GROUP_BYTES and within the kernel's 2^31 voxels, at least one."""
-    per_member = (3 + 2 * int(dim)) * int(n) * int(elem_size)
-    g = min(PD_SWEEP_GROUP_BYTES // per_member, (1 << 31) // int(n))
+def _group_size(members, n, dim, elem_size, arrays, group_bytes, most=1 << 31):
+    """Members per stacked group: as many as keep a group's state (`arrays` + 2 dim
+    arrays of n elements per member) under group_bytes and within the kernel's 2^31
+    voxels and `most` members, at least one."""
+    per_member = (arrays + 2 * int(dim)) * int(n) * int(elem_size)
+    g = min(group_bytes // per_member, (1 << 31) // int(n), most)
     return int(max(1, min(int(members), g)))
+
+
+def sweep_group_size(members, n, dim, elem_size):
+    """Members per stacked group of a sweep (x, two xbar, two p: 3 + 2 dim arrays),
+    under PD_SWEEP_GROUP_BYTES."""
+    return _group_size(members, n, dim, elem_size, 3, PD_SWEEP_GROUP_BYTES)
 
 
 def sweep_groups(members, group):
@@ -1546,12 +1553,9 @@ def pd_batch_launches():
 
 
 def batch_group_size(members, n, dim, elem_size):
-    """Members per stacked group of independent images: as many as keep a group's
-    state, the per-member observation included, under PD_BATCH_GROUP_BYTES and within
-    the kernel's 2^31 voxels and 65535 members, at least one."""
-    per_member = (4 + 2 * int(dim)) * int(n) * int(elem_size)
-    g = min(PD_BATCH_GROUP_BYTES // per_member, (1 << 31) // int(n), 65535)
-    return int(max(1, min(int(members), g)))
+    """Members per stacked group of independent images: the per-member observation
+    counts (4 + 2 dim arrays), under PD_BATCH_GROUP_BYTES, at most 65535 members."""
+    return _group_size(members, n, dim, elem_size, 4, PD_BATCH_GROUP_BYTES, 65535)
 
 
 def scale_rows(x, s, members, divide=False, out=None, dtype=None):
@@ -1619,9 +1623,7 @@ def pd_weighted_launches():
 
 def weighted_batch_group_size(members, n, dim, elem_size):
     """batch_group_size with the member's own weights counted: 5 + 2 dim arrays."""
-    per_member = (5 + 2 * int(dim)) * int(n) * int(elem_size)
-    g = min(PD_BATCH_GROUP_BYTES // per_member, (1 << 31) // int(n), 65535)
-    return int(max(1, min(int(members), g)))
+    return _group_size(members, n, dim, elem_size, 5, PD_BATCH_GROUP_BYTES, 65535)
 
 
 def _weighted_operands(x, xbar0, xbar1, bt, wt, p0, p1, members, shape):

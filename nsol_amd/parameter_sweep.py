@@ -38,9 +38,9 @@ import numpy as np
 
 from . import ops
 from .observer import Observer
-from .primal_dual_solver import (PrimalDualSolver, checked_check_every,
-                                 checked_tolerance, step_schedule)
-from .stacked_stopping import run_group, stretch_bounds
+from .primal_dual_solver import PrimalDualSolver
+from .stacked_run import run_stack
+from .stopping import checked_check_every, checked_tolerance
 
 PARAMETER_KEYS = ("alpha", "alg_type", "L2")
 
@@ -176,38 +176,27 @@ class PrimalDualSweep(object):
             self._iterations_done.append(solver.get_iterations_done())
 
     def _run_stacked(self, template, plan):
-        """All members in one launch per iteration; False when the library
-        declined (nothing has run then)."""
+        """All members in one launch per iteration (stacked_run.run_stack, observation
+        and weights shared); False when the library declined (nothing has run then)."""
         import torch
         from .device import to_device
         from .proximal_operators import scaled_data_on_device, weights_on_device
-        members, iters = self._members, self._iterations
-        P = len(members)
+        iters = self._iterations
+        kws = [dict(self._defaults, **member) for member in self._members]
+        P = len(kws)
         x0 = template._x0_device()
-        n, dim = x0.numel(), plan["dim"]
-        lmbda = np.empty(P)
-        sig, ta, th = (np.empty((P, iters)) for _ in range(3))
-        for m, member in enumerate(members):
-            kw = dict(self._defaults)
-            kw.update(member)
-            lmbda[m] = 1. / float(kw["alpha"])
-            sig[m], ta[m], th[m] = step_schedule(kw["alg_type"], float(kw["L2"]),
-                                                 lmbda[m], iters)
+        n = x0.numel()
         bt = scaled_data_on_device(plan["data"], plan["data_scale"], x0)
         wt = weights_on_device(plan["weights"], x0) \
             if plan["flags"] & ops.PD_DATA_WEIGHTED else None
-        G = ops.sweep_group_size(P, n, dim, x0.element_size())
+        G = ops.sweep_group_size(P, n, plan["dim"], x0.element_size())
         x_all = torch.empty(P * n, dtype=x0.dtype, device=x0.device)
         x_all.view(P, n).copy_(x0)
-        xbar = [torch.empty(G * n, dtype=x0.dtype, device=x0.device)
-                for _ in range(2)]
-        p = [torch.empty(G * dim * n, dtype=x0.dtype, device=x0.device)
-             for _ in range(2)]
         # the observation of the start vector, as Solver._observe_at(0) makes it
         observers, bounds = [], [0, iters]
         if self._functions:
             refs = {}
-            for _ in members:
+            for _ in kws:
                 obs = self._observer()
                 bounds = obs._begin(n, iters, refs)
                 observers.append(obs)
@@ -219,61 +208,20 @@ class PrimalDualSweep(object):
                     start, scale = x0, self._x_scale
                 for obs in observers:
                     obs._observe(0, start, scale)
-        first_call = True
-        done = []
-        for a, b in ops.sweep_groups(P, G):
-            g = b - a
-            x = x_all[a * n:b * n]
-            xb = [t[:g * n] for t in xbar]
-            pp = [t[:g * dim * n] for t in p]
-            xb[0].view(g, n).copy_(x0)
-            k = 0
-            if self._tolerance is not None:
-                # every member stops at a check of its own (stacked_stopping)
-                res = run_group(
-                    x, xb, pp, bt, wt, g, plan["shape"], plan["w"],
-                    ops.pd_weighted_table(x, g, lmbda[a:b], sig[a:b], ta[a:b], th[a:b],
-                                          True, plan["gamma"], plan["flags"]),
-                    plan["flags"], [self._tolerance] * g, self._check_every, iters,
-                    stretch_bounds(iters, self._check_every,
-                                   bounds if observers else None),
-                    observe=(lambda m, it, a=a: observers[a + m]._observe(
-                        it, x_all[(a + m) * n:(a + m + 1) * n], self._x_scale))
-                    if observers else None)
-                if res is None:
-                    if first_call:
-                        return False
-                    raise RuntimeError("nsol_pd_stack_iter declined in mid-sweep")
-                first_call = False
-                done += res.iterations_done
-                continue
-            for i0, i1 in zip(bounds[:-1], bounds[1:]):
-                if wt is not None:
-                    # a weighted data term: observation and weights shared by
-                    # the members, both at member stride 0 (nsol_pd_weighted_run_*)
-                    slot = ops.pd_weighted_run(
-                        xb[k], xb[1 - k], x, bt, wt, pp[k], pp[1 - k], g,
-                        plan["shape"], plan["w"], lmbda[a:b], sig[a:b, i0:i1],
-                        ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0, plan["gamma"],
-                        plan["flags"])
-                else:
-                    slot = ops.pd_sweep_run(
-                        xb[k], xb[1 - k], x, bt, pp[k], pp[1 - k], g, plan["shape"],
-                        plan["w"], lmbda[a:b], sig[a:b, i0:i1], ta[a:b, i0:i1],
-                        th[a:b, i0:i1], i0 == 0, plan["gamma"], plan["flags"])
-                if slot is None:
-                    if first_call:
-                        return False
-                    raise RuntimeError("nsol_pd_sweep_run declined in mid-sweep")
-                first_call = False
-                k = k if slot == 0 else 1 - k
-                for m in range(a, b):
-                    if observers:
-                        observers[m]._observe(i1, x_all[m * n:(m + 1) * n],
-                                              self._x_scale)
+        stopping = self._tolerance is not None      # (stacked_stopping)
+        res = run_stack(
+            x_all, bt, wt, False, plan,
+            [(kw["alg_type"], float(kw["L2"]), kw["alpha"]) for kw in kws], iters, G,
+            ops.pd_sweep_run, bounds,
+            observe=(lambda m, it: observers[m]._observe(
+                it, x_all[m * n:(m + 1) * n], self._x_scale)) if observers else None,
+            tolerances=[self._tolerance] * P if stopping else None,
+            check_every=self._check_every, start=x0)
+        if res is None:
+            return False
         self._x_all, self._n, self._observers = x_all, n, observers
-        if self._tolerance is not None:
-            self._iterations_done = done
+        if stopping:
+            self._iterations_done = res.iterations_done
         self._group = G
         return True
 

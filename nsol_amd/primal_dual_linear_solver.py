@@ -44,11 +44,10 @@ from . import linear_operators, ops
 from .bridge import BridgedCallable
 from .device import is_device_tensor
 from .linear_operators import ConvolutionOperator, DeviceOperator
-from .primal_dual_solver import (_StopRule, checked_check_every, checked_tolerance,
-                                 criterion_met, relative_changes)
 from .proximal_operators import (check_weights, scaled_data_on_device,
                                  weights_on_device)
 from .solver import Solver
+from .stopping import Stopping, _StopRule, criterion_met, relative_changes
 from .symbolic import trace_operator
 from ._accessors import add_accessors
 
@@ -111,7 +110,7 @@ class _LinearStopRule(_StopRule):
         return criterion_met(r_x, r_d, self.tolerance)
 
 
-class PrimalDualLinearSolver(Solver):
+class PrimalDualLinearSolver(Stopping, Solver):
 
     def __init__(self, A, A_adj, b, x0, dimension, spacing=None, alpha=0.01,
                  iterations=10, reg_type="TV", huber_gamma=0.05, isotropic=False,
@@ -140,9 +139,8 @@ class PrimalDualLinearSolver(Solver):
         self._isotropic = bool(isotropic)
         self._data_loss = data_loss
         self._bounds = checked_bounds(bounds)
-        self._tolerance = checked_tolerance(tolerance)
-        self._check_every = checked_check_every(check_every)
-        self._iterations_done = self._stop_reason = self._rule = None
+        self.set_tolerance(tolerance)
+        self.set_check_every(check_every)
 
         n = int(x0.numel() if is_device_tensor(x0) else np.size(x0))
         m = int(b.numel() if is_device_tensor(b) else np.size(b))
@@ -211,25 +209,6 @@ class PrimalDualLinearSolver(Solver):
     def print_statistics(self, fmt="%.3e"):
         pass
 
-    def set_tolerance(self, tolerance):
-        self._tolerance = checked_tolerance(tolerance)
-
-    def set_check_every(self, check_every):
-        self._check_every = checked_check_every(check_every)
-
-    def get_iterations_done(self):
-        """Iterations the last run() did (None before one)."""
-        return self._iterations_done
-
-    def get_stop_reason(self):
-        """'tolerance' or 'iterations' after run() (None before)."""
-        return self._stop_reason
-
-    def get_changes(self):
-        """One row (k, r_x, r_dual) per check of the last run()."""
-        rows = self._rule.rows if self._rule is not None else []
-        return np.array(rows, dtype=np.float64).reshape(-1, 3)
-
     # ------------------------------------------------------------------
     def _flags(self):
         flags = ops.PD_REG_HUBER if self._reg_type == "huber" else ops.PD_REG_TV
@@ -240,10 +219,8 @@ class PrimalDualLinearSolver(Solver):
     def _run(self):
         import torch
         iters = max(int(self._iterations), 0)
-        self._points = self._observe_start(iters)
-        self._rule = rule = None if self._tolerance is None else _LinearStopRule(
-            self._tolerance, iters, self._check_every)
-        self._iterations_done, self._stop_reason = 0, "iterations"
+        self._observe_start(iters)
+        rule = self._start_rule(iters, _LinearStopRule)
 
         x = self._x0_device().clone()
         n, m = self._n, self._m
@@ -311,11 +288,8 @@ class PrimalDualLinearSolver(Solver):
                 ops.pd_change(q_old, q, q_old, q, rule.ws, row[ops.PD_CHECK_SUMS:])
             self._x = x
             self._observe_iteration(i + 1, x)
-            if rule is not None:
-                self._iterations_done = i + 1
-                if check and rule.decide(i + 1):
-                    self._stop_reason = "tolerance"
-                    break
+            if self._stops_after(i + 1):
+                break
         self._x = x
         if rule is None:
             self._iterations_done = iters
@@ -323,20 +297,10 @@ class PrimalDualLinearSolver(Solver):
             self._execution = "device" if (A.on_device in (True, None) and
                                            At.on_device in (True, None)) else "host"
 
-    _points = None
-
-    def _observe_iteration(self, it, x):
-        if self._observer is None:
-            return
-        if self._points is None:
-            self._observer.add_x(self.get_x())
-        else:
-            self._observe_at(it, x)
-
 
 add_accessors(PrimalDualLinearSolver,
               ["alpha", "iterations", "huber_gamma", "reg_type", "data_loss"])
 add_accessors(PrimalDualLinearSolver,
               ["A", "A_adj", "dimension", "spacing", "isotropic", "bounds", "A_norm2",
-               "L2", "tau", "sigma", "theta", "tolerance", "check_every", "shape"],
+               "L2", "tau", "sigma", "theta", "shape"],
               setters=False)

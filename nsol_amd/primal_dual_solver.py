@@ -25,13 +25,7 @@ nsol/primal_dual_solver.py:26-403).
           copied to the host for the callable only.
 
 With a `tolerance` the run stops before `iterations` once its iterates have stopped
-changing: after iteration k = check_every, 2 check_every, ... and the last,
-
-    r_x = sqrt(sum (x_k - x_{k-1})^2 / sum x_k^2),   r_p likewise for the dual p
-
-(p = 0 before the first iteration; a ratio whose numerator is exactly 0 counts as 0;
-sums that are not finite never meet the criterion) and the run stops if
-max(r_x, r_p) <= tolerance.  The fused forms run the check_every - 1 iterations
+changing (the rule: stopping.py).  The fused forms run the check_every - 1 iterations
 between two checks as before (multi-iteration and persistent kernels included) and
 the checked iteration through k_pd_check (nsol_pdc.hip), which forms the four sums
 from the values it holds in registers when it stores them; the other forms call
@@ -46,6 +40,9 @@ from .device import is_device_tensor
 from .proximal_operators import (check_weights, scaled_data_on_device,
                                  weights_on_device)
 from .solver import Solver
+from .stopping import (Stopping, _StopRule, check_points, checked_check_every,  # noqa: F401
+                       checked_tolerance, criterion_met, next_slot, relative_changes,
+                       stretch_bounds)
 from ._accessors import add_accessors
 from .symbolic import TauSym, trace_operator, trace_prox
 
@@ -97,100 +94,83 @@ def _init_alg3(L2, lmbda, huber_alpha=0.05):
     return mu / (2. * lmbda), mu / (2. * huber_alpha), 1. / (1. + mu)
 
 
-def checked_tolerance(tolerance):
-    """None, or the tolerance as a float >= 0 (ValueError for a negative one or NaN)."""
-    if tolerance is None:
-        return None
-    tolerance = float(tolerance)
-    if not tolerance >= 0.:
-        raise ValueError("tolerance must be None or a number >= 0")
-    return tolerance
+def _taken(took, entry, shape):
+    """What a launch returned, unless the library declined it (None / False)."""
+    if took is None or took is False:
+        raise ValueError("nsol_%s does not take a volume of shape %r" %
+                         (entry, tuple(shape)))
+    return took
 
 
-def checked_check_every(check_every):
-    """check_every as an int >= 1 (ValueError otherwise)."""
-    try:
-        k = int(check_every)
-        ok = k >= 1 and k == check_every
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError("check_every must be a positive integer")
-    return k
+class _PlainForm(object):
+    """How PrimalDualSolver._run_stretches advances a fused run: ops.pd_run over a
+    stretch (multi-iteration and persistent kernels included; pitch > 0: every array at
+    that row pitch), ops.pd_check_iter for a checked iteration.  single: the stretches
+    are single iterations of a run without a tolerance, launched through the
+    one-iteration entry.  A new fused form supplies an object like this one."""
+    wt = None
+
+    def __init__(self, plan, lmbda, sig, ta, th, x, bt, x_alt=None, pitch=0,
+                 single=False):
+        self.shape, self.w, self.flags = plan["shape"], plan["w"], plan["flags"]
+        self.gamma = plan["gamma"]
+        self.lmbda, self.sig, self.ta, self.th = lmbda, sig, ta, th
+        self.x, self.bt, self.x_alt, self.pitch, self.single = x, bt, x_alt, pitch, single
+        # what the observer reads x as
+        self.layout = (self.shape, pitch) if pitch else None
+
+    def _hden(self, i):
+        return 1. + self.sig[i] * self.gamma if self.flags & ops.PD_REG_HUBER else 1.
+
+    def advance(self, xbar_in, xbar_out, p_in, p_out, a, last):
+        """Iterations a ... last - 1 (p counts as zero before iteration 0); returns
+        the slot of ops.pd_run."""
+        sig, ta, th = self.sig, self.ta, self.th
+        if self.single:
+            ops.pd_fused_iter(xbar_in, xbar_out, self.x, self.bt,
+                              None if a == 0 else p_in, p_out, self.shape, self.w,
+                              sig[a], self._hden(a), ta[a], ta[a] * self.lmbda, th[a],
+                              self.flags)
+            return 1
+        return ops.pd_run(xbar_in, xbar_out, self.x, self.bt, p_in, p_out, self.shape,
+                          self.w, self.lmbda, sig[a:last], ta[a:last], th[a:last], a == 0,
+                          self.gamma, self.flags, x_alt=self.x_alt, swap_ok=True,
+                          pitch=self.pitch)
+
+    def check(self, xbar_in, xbar_out, p_in, p_out, i, ws, row):
+        """Iteration i through k_pd_check, its four sums into `row`."""
+        _taken(ops.pd_check_iter(xbar_in, xbar_out, self.x, self.bt, self.wt,
+                                 None if i == 0 else p_in, p_out, self.shape, self.w,
+                                 self.sig[i], self._hden(i), self.ta[i],
+                                 self.ta[i] * self.lmbda, self.th[i], self.flags, ws, row),
+               "pd_check_iter", self.shape)
 
 
-def check_points(iterations, check_every):
-    """Iterations after which the stopping rule is evaluated: check_every,
-    2 check_every, ... and always the last."""
-    iterations, check_every = int(iterations), int(check_every)
-    if iterations < 1:
-        return []
-    pts = list(range(check_every, iterations + 1, check_every))
-    if not pts or pts[-1] != iterations:
-        pts.append(iterations)
-    return pts
+class _WeightedForm(_PlainForm):
+    """The fused run with a weighted data term (k_pd_w, nsol_pdw.hip): one iteration
+    per launch, contiguous arrays -- no row pitch, no multi-iteration kernels and never
+    the persistent kernel, which have no weighted form.  stepwise: the stretches are
+    single iterations, launched from one table of the run's scalars."""
+
+    def __init__(self, plan, lmbda, sig, ta, th, x, bt, wt, stepwise):
+        _PlainForm.__init__(self, plan, lmbda, sig, ta, th, x, bt)
+        self.wt = wt
+        self.tab = ops.pd_weighted_table(x, 1, [lmbda], sig, ta, th, True, self.gamma,
+                                         self.flags) if stepwise else None
+
+    def advance(self, xbar_in, xbar_out, p_in, p_out, a, last):
+        if self.tab is not None:
+            _taken(ops.pd_weighted_iter(xbar_in, xbar_out, self.x, self.bt, self.wt, p_in,
+                                        p_out, 1, self.shape, self.w, self.tab, a,
+                                        self.flags), "pd_weighted_iter", self.shape)
+            return 1
+        return _taken(ops.pd_weighted_run(
+            xbar_in, xbar_out, self.x, self.bt, self.wt, p_in, p_out, 1, self.shape,
+            self.w, [self.lmbda], self.sig[a:last], self.ta[a:last], self.th[a:last],
+            a == 0, self.gamma, self.flags), "pd_weighted_run", self.shape)
 
 
-def relative_changes(sums):
-    """(r_x, r_p) from the four sums {sum dx^2, sum x^2, sum dp^2, sum p^2}: a ratio
-    whose numerator is exactly 0 is 0; NaN where a sum is not finite."""
-    out = []
-    for num, den in ((sums[0], sums[1]), (sums[2], sums[3])):
-        num, den = float(num), float(den)
-        if not (np.isfinite(num) and np.isfinite(den)):
-            out.append(float("nan"))
-        elif num == 0.:
-            out.append(0.)
-        elif den == 0.:
-            out.append(float("inf"))
-        else:
-            out.append(float(np.sqrt(num / den)))
-    return out[0], out[1]
-
-
-def criterion_met(r_x, r_p, tolerance):
-    """max(r_x, r_p) <= tolerance; never with a NaN among them."""
-    return bool(np.isfinite(r_x) and np.isfinite(r_p) and
-                max(r_x, r_p) <= tolerance)
-
-
-class _StopRule(object):
-    """The stopping rule of one run: its check points, the device workspace and
-    board (one row of four sums per check) and the rows (k, r_x, r_p) read so far."""
-
-    def __init__(self, tolerance, iterations, check_every):
-        self.tolerance = float(tolerance)
-        self.points = check_points(iterations, check_every)
-        self._index = {p: j for j, p in enumerate(self.points)}
-        self.ws = self.board = None
-        self.rows = []
-
-    def allocate(self, like, shape=None):
-        """shape: the volume of the fused kernels (None: nsol_pd_change_* only)."""
-        import torch
-        if shape is not None:
-            self.ws = ops.pd_check_workspace(like, shape)
-        else:
-            self.ws = torch.empty(ops.PD_CHECK_SUMS * 4096, dtype=torch.float64,
-                                  device=like.device)
-        self.board = torch.empty((max(len(self.points), 1), ops.PD_CHECK_SUMS),
-                                 dtype=torch.float64, device=like.device)
-
-    def is_point(self, it):
-        return it in self._index
-
-    def row(self, it):
-        return self.board[self._index[it]]
-
-    def decide(self, it):
-        """Reads the row of check `it` back (this waits for the device) and says
-        whether the run stops."""
-        r_x, r_p = relative_changes(self.row(it).cpu().numpy())
-        self.rows.append((float(it), r_x, r_p))
-        return criterion_met(r_x, r_p, self.tolerance)
-
-
-class PrimalDualSolver(Solver):
+class PrimalDualSolver(Stopping, Solver):
 
     def __init__(self, prox_f, prox_g_conj, B, B_conj, L2, x0, alpha=0.01,
                  iterations=10, x_scale=1., verbose=0, alg_type="ALG2",
@@ -199,9 +179,6 @@ class PrimalDualSolver(Solver):
                         dtype=dtype)
         self.set_tolerance(tolerance)
         self.set_check_every(check_every)
-        self._iterations_done = None
-        self._stop_reason = None
-        self._rule = None
         self._prox_f = prox_f
         self._prox_g_conj = prox_g_conj
         self._B = B
@@ -218,33 +195,6 @@ class PrimalDualSolver(Solver):
 
     def print_statistics(self, fmt="%.3e"):
         pass
-
-    # ---- the stopping rule -------------------------------------------
-    def set_tolerance(self, tolerance):
-        """None: run all `iterations`; else stop once max(r_x, r_p) <= tolerance."""
-        self._tolerance = checked_tolerance(tolerance)
-
-    def get_tolerance(self):
-        return self._tolerance
-
-    def set_check_every(self, check_every):
-        self._check_every = checked_check_every(check_every)
-
-    def get_check_every(self):
-        return self._check_every
-
-    def get_iterations_done(self):
-        """Iterations the last run() did (None before one)."""
-        return self._iterations_done
-
-    def get_stop_reason(self):
-        """'tolerance' or 'iterations' after run() (None before)."""
-        return self._stop_reason
-
-    def get_changes(self):
-        """One row (k, r_x, r_p) per check of the last run()."""
-        rows = self._rule.rows if self._rule is not None else []
-        return np.array(rows, dtype=np.float64).reshape(-1, 3)
 
     # ------------------------------------------------------------------
     def _native_dual(self):
@@ -314,9 +264,7 @@ class PrimalDualSolver(Solver):
         lmbda = 1. / self._alpha
         sig, ta, th = step_schedule(self._alg_type, self._L2, lmbda,
                                     self._iterations)
-        self._rule = None if self._tolerance is None else _StopRule(
-            self._tolerance, self._iterations, self._check_every)
-        self._iterations_done, self._stop_reason = 0, "iterations"
+        self._start_rule(self._iterations)
         plan = self.plan()
         if plan is not None:
             self._execution = "fused"
@@ -326,37 +274,22 @@ class PrimalDualSolver(Solver):
         if self._rule is None:
             self._iterations_done = max(int(self._iterations), 0)
 
-    def _stops_after(self, it):
-        """Bookkeeping after iteration `it` of a run with a tolerance; True when the
-        rule was evaluated there and the run stops."""
-        self._iterations_done = it
-        if self._rule.is_point(it) and self._rule.decide(it):
-            self._stop_reason = "tolerance"
-            return True
-        return False
-
     # ------------------------------------------------------------------
     def _run_fused(self, plan, lmbda, sig, ta, th):
+        """The fused run: a form object (plain, pitched or weighted) driven by
+        _run_stretches.  A run with a tolerance or weights gives up the row pitch."""
         import torch
         x = self._x0_device().clone()
-        xbar = [x.clone(), torch.empty_like(x)]
-        n = x.numel()
-        p = [torch.empty(plan["dim"] * n, dtype=x.dtype, device=x.device)
-             for _ in range(2)]
+        n, iters = x.numel(), int(self._iterations)
         bt = scaled_data_on_device(plan["data"], plan["data_scale"], x)
-        if self._rule is not None:
-            self._run_checked(plan, lmbda, sig, ta, th, x, xbar, p, bt)
-            return
-        if plan["flags"] & ops.PD_DATA_WEIGHTED:
-            self._run_weighted(plan, lmbda, sig, ta, th, x, xbar, p, bt)
-            return
-        # a device-mode observer (observer.py) keeps the multi-iteration kernels
-        # and the row pitch: the run is enqueued in chunks between its
-        # observation points, nsol_observe_* reads the pitched x as it is
-        unobserved = self._observer is None or self._points is not None
+        rule = self._rule
+        weighted = bool(plan["flags"] & ops.PD_DATA_WEIGHTED)
+        bounds, stepwise = self._stretch_bounds(iters)
+        if rule is not None:
+            rule.allocate(x, plan["shape"])
         pitch = ops.row_pitch(plan["shape"], x) if USE_ROW_PITCH and \
-            n >= PITCH_MIN_VOXELS and self._iterations > 1 and \
-            unobserved and not self._verbose else 0
+            n >= PITCH_MIN_VOXELS and iters > 1 and \
+            not (stepwise or weighted or rule is not None) else 0
         if pitch:
             # rows that are not whole 16-byte vectors (511^3, 181 x 217 x 181 ...): the
             # run's arrays hold them at a pitch of whole vectors -- aligned accesses
@@ -368,186 +301,83 @@ class PrimalDualSolver(Solver):
             xbq = [xq.clone(), torch.empty_like(xq)]
             pq = [torch.zeros(plan["dim"] * np_, dtype=x.dtype, device=x.device),
                   torch.empty(plan["dim"] * np_, dtype=x.dtype, device=x.device)]
-            btq = ops.to_pitched(bt, shape, pitch)
+            form = _PlainForm(plan, lmbda, sig, ta, th, xq,
+                              ops.to_pitched(bt, shape, pitch), torch.zeros_like(xq),
+                              pitch)
             try:
-                self._chunks(xbq, xq, btq, pq, plan, lmbda, sig, ta, th,
-                             torch.zeros_like(xq), pitch)
+                self._run_stretches(form, xbq, pq, bounds)
                 self._x = ops.from_pitched(xq, shape, pitch)
                 return
             except ValueError:
                 # the pitched entry declined (NSOL_EINVAL: the ragged-row form is
                 # switched off, knob pd_rag): the contiguous arrays are untouched
-                del xq, xbq, pq, btq
-        if unobserved and not self._verbose:
-            # scratch for the two-iterations-per-pass kernel (x ping-pong)
-            x_alt = torch.empty_like(x) if self._iterations > 1 else None
-            self._chunks(xbar, x, bt, p, plan, lmbda, sig, ta, th, x_alt, 0)
-            self._x = x
-            return
-        for i in range(self._iterations):      # observed / verbose: stepwise
-            if self._verbose:
-                print("Primal-Dual iteration %d/%d" % (i + 1,
-                                                       self._iterations))
-            k = i & 1
-            hden = 1. + sig[i] * plan["gamma"] \
-                if plan["flags"] & ops.PD_REG_HUBER else 1.
-            ops.pd_fused_iter(xbar[k], xbar[1 - k], x, bt,
-                              None if i == 0 else p[k], p[1 - k],
-                              plan["shape"], plan["w"], sig[i], hden, ta[i],
-                              ta[i] * lmbda, th[i], plan["flags"])
-            self._x = x
-            self._observe_iteration(i + 1, x)
-        self._x = x
-
-    def _run_weighted(self, plan, lmbda, sig, ta, th, x, xbar, p, bt):
-        """The fused run with a weighted data term (k_pd_w, nsol_pdw.hip): one
-        iteration per launch, contiguous arrays -- no row pitch, no multi-iteration
-        kernels and never the persistent kernel, which have no weighted form.  The
-        weights are converted to the working dtype once per run."""
-        wt = weights_on_device(plan["weights"], x)
-        shape, w, flags = plan["shape"], plan["w"], plan["flags"]
-        unobserved = self._observer is None or self._points is not None
-        if unobserved and not self._verbose:
-            # the whole run, or the stretches between a device-mode observer's points
-            pts = self._points
-            bounds = [0, self._iterations] if pts is None else pts
-            k = 0
-            for a, b in zip(bounds[:-1], bounds[1:]):
-                slot = ops.pd_weighted_run(
-                    xbar[k], xbar[1 - k], x, bt, wt, p[k], p[1 - k], 1, shape, w,
-                    [lmbda], sig[a:b], ta[a:b], th[a:b], a == 0, plan["gamma"], flags)
-                if slot is None:
-                    raise ValueError("nsol_pd_weighted_run does not take a volume "
-                                     "of shape %r" % (tuple(shape),))
-                k = k if slot == 0 else 1 - k
-                if pts is not None:
-                    self._observe_at(b, x, None)
-            self._x = x
-            return
-        tab = ops.pd_weighted_table(x, 1, [lmbda], sig, ta, th, True, plan["gamma"],
-                                    flags)
-        for i in range(self._iterations):      # observed / verbose: stepwise
-            if self._verbose:
-                print("Primal-Dual iteration %d/%d" % (i + 1,
-                                                       self._iterations))
-            k = i & 1
-            if not ops.pd_weighted_iter(xbar[k], xbar[1 - k], x, bt, wt, p[k],
-                                        p[1 - k], 1, shape, w, tab, i, flags):
-                raise ValueError("nsol_pd_weighted_iter does not take a volume of "
-                                 "shape %r" % (tuple(shape),))
-            self._x = x
-            self._observe_iteration(i + 1, x)
-        self._x = x
-
-    def _run_checked(self, plan, lmbda, sig, ta, th, x, xbar, p, bt):
-        """The fused run with a tolerance, weighted or not: contiguous arrays (no row
-        pitch).  The run is enqueued in stretches between the check points merged
-        with a device-mode observer's points; a stretch that ends in a check runs
-        all but its last iteration through ops.pd_run / ops.pd_weighted_run as an
-        unchecked run does, and the last through k_pd_check, whose sums are read
-        back for the decision.  With verbose or an observer that keeps iterates the
-        stretches are single iterations (a weighted run then launches them from one
-        table of scalars, as _run_weighted does)."""
-        import torch
-        rule = self._rule
-        shape, w, flags = plan["shape"], plan["w"], plan["flags"]
-        weighted = bool(flags & ops.PD_DATA_WEIGHTED)
-        wt = weights_on_device(plan["weights"], x) if weighted else None
-        rule.allocate(x, shape)
-        iters = int(self._iterations)
-        stepwise = bool(self._verbose) or not (
-            self._observer is None or self._points is not None)
-        if stepwise:
-            bounds = list(range(iters + 1))
+                del xq, xbq, pq, form
+        xbar = [x.clone(), torch.empty_like(x)]
+        p = [torch.empty(plan["dim"] * n, dtype=x.dtype, device=x.device)
+             for _ in range(2)]
+        if weighted:
+            # (the weights are converted to the working dtype once per run)
+            form = _WeightedForm(plan, lmbda, sig, ta, th, x, bt,
+                                 weights_on_device(plan["weights"], x), stepwise)
         else:
-            bounds = sorted(set([0]) | set(self._points or []) | set(rule.points))
-        x_alt = torch.empty_like(x) if not weighted and iters > 1 else None
-        huber = bool(flags & ops.PD_REG_HUBER)
-        # stepwise and weighted: one table for the whole run, as _run_weighted has
-        tab = ops.pd_weighted_table(x, 1, [lmbda], sig, ta, th, True, plan["gamma"],
-                                    flags) if stepwise and weighted else None
+            # x_alt: scratch for the multi-iteration kernels (x ping-pong); none for
+            # single iterations, checked or not: nsol_pd_run_* reads it only where two
+            # or more iterations are left, so the launches are the same without it
+            form = _PlainForm(
+                plan, lmbda, sig, ta, th, x, bt,
+                torch.empty_like(x) if iters > 1 and not stepwise else None,
+                single=stepwise and rule is None)
+        self._x = x
+        self._run_stretches(form, xbar, p, bounds)
+
+    _points = None
+
+    def _stretch_bounds(self, iters):
+        """(bounds of the stretches the run is enqueued in, stepwise).  Verbose, or an
+        observer that keeps iterates: stepwise, the stretches are single iterations.  A
+        device-mode observer (observer.py) keeps the multi-iteration kernels and the row
+        pitch: the stretches end at its points (nsol_observe_* reads the pitched x as
+        it is), merged with the rule's check points."""
+        if self._verbose or not (self._observer is None or self._points is not None):
+            return list(range(iters + 1)), True
+        if self._rule is not None:
+            return stretch_bounds(iters, self._check_every, self._points), False
+        return ([0, iters] if self._points is None else self._points), False
+
+    def _run_stretches(self, form, xbar, p, bounds):
+        """The loop of every fused run: the run is enqueued in the stretches between
+        `bounds` (check points, a device-mode observer's points, every iteration when
+        stepwise), each starting from the xbar / p half the one before ended in.  A
+        stretch that ends in a check runs all but its last iteration as an unchecked
+        run does and the last in the checking form, whose sums are read back for the
+        decision (the multi-iteration kernels are bit-identical to a launch per
+        iteration, so the stretches change no bit of x).  Pending persistent runs are
+        settled before every check and observation, whatever the form: only
+        ops.pd_run leaves one, but a foreign one (an outer solver's) is then settled
+        here too, before x is read.  form: _PlainForm's interface."""
+        rule, iters = self._rule, int(self._iterations)
+        observed = self._observer is not None
         k = 0
         for a, b in zip(bounds[:-1], bounds[1:]):
             if self._verbose:
                 print("Primal-Dual iteration %d/%d" % (b, iters))
-            check = rule.is_point(b)
+            check = rule is not None and rule.is_point(b)
             last = b - 1 if check else b
-            if last > a and tab is not None:
-                if not ops.pd_weighted_iter(xbar[k], xbar[1 - k], x, bt, wt, p[k],
-                                            p[1 - k], 1, shape, w, tab, a, flags):
-                    raise ValueError("nsol_pd_weighted_iter does not take a volume of "
-                                     "shape %r" % (tuple(shape),))
-                k = 1 - k
-            elif last > a and weighted:
-                slot = ops.pd_weighted_run(
-                    xbar[k], xbar[1 - k], x, bt, wt, p[k], p[1 - k], 1, shape, w,
-                    [lmbda], sig[a:last], ta[a:last], th[a:last], a == 0, plan["gamma"],
-                    flags)
-                if slot is None:
-                    raise ValueError("nsol_pd_weighted_run does not take a volume "
-                                     "of shape %r" % (tuple(shape),))
-                k = k if slot == 0 else 1 - k
-            elif last > a:
-                slot = ops.pd_run(xbar[k], xbar[1 - k], x, bt, p[k], p[1 - k], shape, w,
-                                  lmbda, sig[a:last], ta[a:last], th[a:last], a == 0,
-                                  plan["gamma"], flags, x_alt=x_alt, swap_ok=True)
-                k = k if slot == 0 else 1 - k
-            if ops._pending_runs:
+            if last > a:
+                k = next_slot(k, form.advance(xbar[k], xbar[1 - k], p[k], p[1 - k], a,
+                                              last))
+            if ops._pending_runs and (check or observed):
                 # (a persistent stretch that timed out is repeated here, before the
                 # checking kernel or the observer reads its x)
                 ops.settle_persist_runs()
             if check:
-                i = b - 1
-                hden = 1. + sig[i] * plan["gamma"] if huber else 1.
-                if not ops.pd_check_iter(xbar[k], xbar[1 - k], x, bt, wt,
-                                         None if i == 0 else p[k], p[1 - k], shape, w,
-                                         sig[i], hden, ta[i], ta[i] * lmbda, th[i],
-                                         flags, rule.ws, rule.row(b)):
-                    raise ValueError("nsol_pd_check_iter does not take a volume of "
-                                     "shape %r" % (tuple(shape),))
+                form.check(xbar[k], xbar[1 - k], p[k], p[1 - k], b - 1, rule.ws,
+                           rule.row(b))
                 k = 1 - k
-            self._x = x
-            if stepwise:
-                self._observe_iteration(b, x)
-            elif self._points is not None:
-                self._observe_at(b, x, None)
+            if observed:
+                self._observe_iteration(b, form.x, form.layout)
             if self._stops_after(b):
                 break
-        self._x = x
-
-    _points = None
-
-    def _chunks(self, xbar, x, bt, p, plan, lmbda, sig, ta, th, x_alt, pitch):
-        """ops.pd_run over the whole run, or, with a device-mode observer, over
-        the stretches between its observation points (the multi-iteration
-        kernels are bit-identical to a launch per iteration, so the chunks
-        change no bit of x): each chunk starts from the xbar / p slot the
-        previous one ended in, p counts as zero in the first chunk only."""
-        pts = self._points
-        bounds = [0, self._iterations] if pts is None else pts
-        layout = (plan["shape"], pitch) if pitch else None
-        k, first = 0, True
-        for a, b in zip(bounds[:-1], bounds[1:]):
-            slot = ops.pd_run(xbar[k], xbar[1 - k], x, bt, p[k], p[1 - k],
-                              plan["shape"], plan["w"], lmbda, sig[a:b], ta[a:b],
-                              th[a:b], first, plan["gamma"], plan["flags"],
-                              x_alt=x_alt, swap_ok=True, pitch=pitch)
-            k = k if slot == 0 else 1 - k
-            first = False
-            if pts is not None:
-                if ops._pending_runs:
-                    # (a persistent chunk that timed out is repeated here, before
-                    # its x is observed)
-                    ops.settle_persist_runs()
-                self._observe_at(b, x, layout)
-
-    def _observe_iteration(self, it, x):
-        if self._observer is None:
-            return
-        if self._points is None:
-            self._observer.add_x(self.get_x())
-        else:
-            self._observe_at(it, x)
 
     # ------------------------------------------------------------------
     def _run_generic(self, lmbda, sig, ta, th):
@@ -584,7 +414,7 @@ class PrimalDualSolver(Solver):
             x = x_new
             self._x = x
             self._observe_iteration(i + 1, x)
-            if rule is not None and self._stops_after(i + 1):
+            if self._stops_after(i + 1):
                 break
         self._x = x
         self._execution = "device" if all(
@@ -623,7 +453,7 @@ class PrimalDualSolver(Solver):
             x = x_new
             self._x = x
             self._observe_iteration(i + 1, x)
-            if rule is not None and self._stops_after(i + 1):
+            if self._stops_after(i + 1):
                 break
         self._x = x
         self._execution = "device" if pf.on_device else "host"

@@ -164,6 +164,15 @@ class Solver(object):
                 x = self._x if self._x is not None else self._x0_device()
         self._observer._observe(it, x, scale, layout)
 
+    def _observe_iteration(self, it, x, layout=None):
+        """What a loop calls after iteration `it` has left the unscaled iterate x
+        (self._x): the device observation where `it` is a point, a host copy for an
+        observer that keeps iterates, nothing without an observer."""
+        if self._observing_on_device():
+            self._observe_at(it, x, layout)
+        elif self._observer is not None:
+            self._observer.add_x(self.get_x())
+
     def _run(self):
         raise NotImplementedError
 

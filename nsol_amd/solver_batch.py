@@ -40,8 +40,9 @@ import numpy as np
 from . import ops
 from .device import is_device_tensor, torch_dtype
 from .observer import observation_points
-from .primal_dual_solver import PrimalDualSolver, step_schedule
-from .stacked_stopping import GroupResult, StoppedRule, run_group, stretch_bounds
+from .primal_dual_solver import PrimalDualSolver
+from .stacked_run import run_stack
+from .stacked_stopping import StoppedRule
 
 
 def _dev_index(v):
@@ -234,11 +235,6 @@ class PrimalDualBatch(object):
         n = int(np.prod(plan["shape"]))
         td = torch_dtype(solvers[0]._dtype)
         dev = device()
-        lmbda = np.empty(P)
-        sig, ta, th = (np.empty((P, iters)) for _ in range(3))
-        for m, s in enumerate(solvers):
-            lmbda[m] = 1. / s._alpha
-            sig[m], ta[m], th[m] = step_schedule(s._alg_type, s._L2, lmbda[m], iters)
         # ---- the scaled observations: float64 / x_scale, rounded once
         datas = [plans[i]["data"] for i in idx]
         if is_device_tensor(datas[0]):
@@ -275,81 +271,31 @@ class PrimalDualBatch(object):
             G = ops.weighted_batch_group_size(P, n, dim, x_all.element_size())
         else:
             G = ops.batch_group_size(P, n, dim, x_all.element_size())
-        xbar = [torch.empty(G * n, dtype=td, device=dev) for _ in range(2)]
-        p = [torch.empty(G * dim * n, dtype=td, device=dev) for _ in range(2)]
         # ---- device-mode observers share their points (member_key): the run is
         # enqueued in the stretches between them
         obs = solvers[0]._observer
         bounds = [0, iters] if obs is None else \
             observation_points(iters, obs.get_every())
-        first_call = True
+
+        def taken():
+            # the library has taken the stack: the observation of the start
+            # vectors, as Solver._observe_start makes it
+            for s in solvers:
+                s._x = None
+                s._observe_start(iters)
+
+        res = run_stack(
+            x_all, bt, wt, True, plan, [(s._alg_type, s._L2, s._alpha) for s in solvers],
+            iters, G, ops.pd_batch_run, bounds,
+            observe=None if obs is None else (lambda m, it: solvers[m]._observe_at(
+                it, x_all[m * n:(m + 1) * n])),
+            taken=None if obs is None else taken,
+            tolerances=[s._tolerance for s in solvers] if stopping else None,
+            check_every=solvers[0]._check_every)
+        if res is None:
+            return None
         if stopping:
-            bounds = stretch_bounds(iters, solvers[0]._check_every,
-                                    None if obs is None else bounds)
-            self._stopped = GroupResult(0)
-        for a, b in ops.sweep_groups(P, G):
-            g = b - a
-            x = x_all[a * n:b * n]
-            xb = [t[:g * n] for t in xbar]
-            pp = [t[:g * dim * n] for t in p]
-            xb[0].copy_(x)
-            k = 0
-            if stopping:
-                def observe(m, it, a=a):
-                    if not observe.started:
-                        # the library has taken the stack: the observation of the
-                        # start vectors, as Solver._observe_start makes it
-                        for s in solvers:
-                            s._x = None
-                            s._observe_start(iters)
-                        observe.started = True
-                    solvers[a + m]._observe_at(
-                        it, x_all[(a + m) * n:(a + m + 1) * n])
-                observe.started = not first_call
-                res = run_group(
-                    x, xb, pp, bt[a * n:b * n],
-                    None if wt is None else wt[a * n:b * n], g, plan["shape"],
-                    plan["w"], ops.pd_weighted_table(
-                        x, g, lmbda[a:b], sig[a:b], ta[a:b], th[a:b], True,
-                        plan["gamma"], plan["flags"]),
-                    plan["flags"], [s._tolerance for s in solvers[a:b]],
-                    solvers[0]._check_every, iters, bounds,
-                    observe=None if obs is None else observe)
-                if res is None:
-                    if first_call:
-                        return None
-                    raise RuntimeError("nsol_pd_stack_iter declined in mid-stack")
-                first_call = False
-                self._stopped.extend(res)
-                continue
-            for i0, i1 in zip(bounds[:-1], bounds[1:]):
-                if wt is not None:
-                    slot = ops.pd_weighted_run(
-                        xb[k], xb[1 - k], x, bt[a * n:b * n], wt[a * n:b * n], pp[k],
-                        pp[1 - k], g, plan["shape"], plan["w"], lmbda[a:b],
-                        sig[a:b, i0:i1], ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0,
-                        plan["gamma"], plan["flags"])
-                else:
-                    slot = ops.pd_batch_run(
-                        xb[k], xb[1 - k], x, bt[a * n:b * n], pp[k], pp[1 - k], g,
-                        plan["shape"], plan["w"], lmbda[a:b], sig[a:b, i0:i1],
-                        ta[a:b, i0:i1], th[a:b, i0:i1], i0 == 0, plan["gamma"],
-                        plan["flags"])
-                if slot is None:
-                    if first_call:
-                        return None
-                    raise RuntimeError("nsol_pd_batch_run declined in mid-stack")
-                if first_call and obs is not None:
-                    # the library has taken the stack: the observation of the
-                    # start vectors, as Solver._observe_start makes it
-                    for s in solvers:
-                        s._x = None
-                        s._observe_start(iters)
-                first_call = False
-                k = k if slot == 0 else 1 - k
-                if obs is not None:
-                    for m in range(a, b):
-                        solvers[m]._observe_at(i1, x_all[m * n:(m + 1) * n])
+            self._stopped = res
         self._group = max(self._group or 0, G)
         return x_all
 

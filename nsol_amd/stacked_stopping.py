@@ -1,14 +1,15 @@
-"""Stacked primal-dual runs whose members stop one by one: the group runner behind
-PrimalDualBatch(stacked_stopping=True) and PrimalDualSweep(stacked_stopping=True).
+"""Stacked primal-dual runs whose members stop one by one: what stacked_run.run_stack
+runs a group through for PrimalDualBatch(stacked_stopping=True) and
+PrimalDualSweep(stacked_stopping=True).
 
 A group of g members (stacked images with their own data, or the members of a sweep
 that share one observation) advances in ONE launch per iteration
 (ops.pd_stack_iter, nsol_pdm.hip) over a device map of the members still running.
-The iteration that ends in a check point (primal_dual_solver.check_points) runs in
+The iteration that ends in a check point (stopping.check_points) runs in
 the checking form and leaves the four sums of every active member in a device board;
 ONE read-back of that board per check is the only synchronisation.  The decision is
-PrimalDualSolver's own (relative_changes / criterion_met), taken per member with
-the member's tolerance; a member that has met it is dropped from the map (a small
+PrimalDualSolver's own (stopping.relative_changes / criterion_met), taken per member
+with the member's tolerance; a member that has met it is dropped from the map (a small
 int32 upload) and is never touched again -- x is updated in place, so its result
 stays where it is and no array is re-laid.  The run ends as soon as the map is empty.
 
@@ -16,14 +17,8 @@ The xbar / p slot alternates in lockstep for all active members; a retired membe
 needs only its x.
 """
 from . import ops
-from .primal_dual_solver import check_points, criterion_met, relative_changes
-
-
-def stretch_bounds(iterations, check_every, observer_points=None):
-    """The bounds of the stretches a run is enqueued in: the check points merged with
-    a device-mode observer's points, as PrimalDualSolver._run_checked merges them."""
-    return sorted(set([0]) | set(observer_points or []) |
-                  set(check_points(iterations, check_every)))
+from .stopping import (check_points, criterion_met, relative_changes,
+                       stretch_bounds)  # noqa: F401 (stretch_bounds: its former home)
 
 
 class StackDevice(object):
