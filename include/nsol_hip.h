@@ -932,6 +932,46 @@ int nsol_pdl_iter_f64(const double *xbar_in, double *xbar_out, double *x, const 
     double lo, double hi, int flags, int has_p, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * The same iteration for `members` stacked runs on volumes of one shape
+ * (nsol_pdls.hip): an alpha sweep on one observation, a stack of images, a set of
+ * small volumes.  All arrays are member-major with stride n = nz * ny * nx (p: n * ndim)
+ * unless said otherwise; member m is bit-identical to the single entries on its slices.
+ *
+ * nsol_pdl_stack_dual_data_*: nsol_pdl_dual_data_* on every member in one launch
+ * (grid y = member).  lmbda: DEVICE array of `members` values in the element type,
+ * each rounded as (T)lmbda is for a single run.  bt and wt (NULL: w = 1) at a member
+ * stride in elements of 0 (shared by the members) or n (member-major), each on its
+ * own; q, and t where given, at stride n.
+ * Returns -2, nothing launched, for members < 1, > 65535 or members * n over 2^31;
+ * NSOL_EINVAL for a missing q, bt or lmbda, t == q, sigma <= 0, n < 0 or a stride
+ * that is neither 0 nor n.
+ *
+ * nsol_pdl_stack_iter_*: nsol_pdl_iter_* on every member in one launch (k_pdl_stack /
+ * k_pdl_stack_iso, grid y = member).  The scalars, flags and the box are common to the
+ * stack: none of them depends on alpha.
+ * Returns -2, nothing launched, for members < 1, > 65535, members * n over 2^31 or a
+ * geometry nsol_pdl_iter_* declines; NSOL_EINVAL for a missing pointer (p_in
+ * included), xbar_in == xbar_out, p_in == p_out, lo > hi or a NaN among them, a data
+ * flag, sigma <= 0.
+ * nsol_pdl_stack_launches: launches of k_pdl_stack / k_pdl_stack_iso this process has
+ * made (nsol_pdl_launches does not count them). */
+int nsol_pdl_stack_launches(void);
+int nsol_pdl_stack_dual_data_f32(float *q, const float *t, const float *bt,
+    int64_t bt_stride, const float *wt, int64_t wt_stride, double sigma,
+    const float *lmbda, int l1, int members, int64_t n, void *stream);
+int nsol_pdl_stack_dual_data_f64(double *q, const double *t, const double *bt,
+    int64_t bt_stride, const double *wt, int64_t wt_stride, double sigma,
+    const double *lmbda, int l1, int members, int64_t n, void *stream);
+int nsol_pdl_stack_iter_f32(const float *xbar_in, float *xbar_out, float *x,
+    const float *g, const float *p_in, float *p_out, int members, int ndim, int64_t nz,
+    int64_t ny, int64_t nx, double wx, double wy, double wz, double sigma, double hden,
+    double tau, double theta, double lo, double hi, int flags, int has_p, void *stream);
+int nsol_pdl_stack_iter_f64(const double *xbar_in, double *xbar_out, double *x,
+    const double *g, const double *p_in, double *p_out, int members, int ndim, int64_t nz,
+    int64_t ny, int64_t nx, double wx, double wy, double wz, double sigma, double hden,
+    double tau, double theta, double lo, double hi, int flags, int has_p, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

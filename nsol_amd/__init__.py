@@ -21,4 +21,7 @@ def __getattr__(name):
     if name == "PrimalDualLinearSolver":
         from .primal_dual_linear_solver import PrimalDualLinearSolver
         return PrimalDualLinearSolver
+    if name in ("PrimalDualLinearBatch", "PrimalDualLinearSweep"):
+        from . import linear_stack
+        return getattr(linear_stack, name)
     raise AttributeError("module 'nsol_amd' has no attribute '%s'" % name)

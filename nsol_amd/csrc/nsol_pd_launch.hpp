@@ -1,7 +1,8 @@
 // Host-side launch path of the kernels that do ONE Chambolle-Pock iteration in one
 // pass: k_pd_fused (nsol_pd.hip), k_pd_fused_iso (nsol_pdi.hip), the member-stacked
 // k_pd_sweep (nsol_pds.hip), k_pd_batch (nsol_pdb.hip), k_pd_w (nsol_pdw.hip),
-// k_pd_stack (nsol_pdm.hip), k_pd_check (nsol_pdc.hip) and k_pd_lin (nsol_pdl.hip).
+// k_pd_stack (nsol_pdm.hip), k_pd_check (nsol_pdc.hip), k_pd_lin (nsol_pdl.hip) and
+// its member-stacked k_pdl_stack (nsol_pdls.hip).
 // They share the wave layout of nsol_pd_fused_body.hpp -- a wave owns
 // (LX*VEC) x (LY*RY) of an x-y tile and marches along z -- so everything that does
 // not depend on the kernel's arguments lives here, once: the rounding of the
@@ -23,6 +24,7 @@
 // forms is the order of the kernels in its code object, which stays as it is.)
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 #include <string.h>
 
@@ -43,6 +45,22 @@ PdScalars<T> pd_make_scalars(double sigma, double hden, double tau, double tl,
   S.l1 = (flags & NSOL_PD_DATA_L1) ? 1 : 0;
   S.has_p = has_p ? 1 : 0;
   return S;
+}
+
+// The box of the linear kernels (nsol_pdl.hip, nsol_pdls.hip) in the kernels' type,
+// rounded towards its inside: a float32 iterate inside [(float)lo, (float)hi] rounded
+// to nearest could lie outside the caller's [lo, hi].
+template <typename T> inline void box_in(double lo, double hi, T &l, T &h);
+template <> inline void box_in<double>(double lo, double hi, double &l, double &h) {
+  l = lo; h = hi;
+}
+template <> inline void box_in<float>(double lo, double hi, float &l, float &h) {
+  l = (float)lo; h = (float)hi;
+  if (lo == hi) return;
+  float li = l, hj = h;
+  if ((double)li < lo) li = nextafterf(li, INFINITY);
+  if ((double)hj > hi) hj = nextafterf(hj, -INFINITY);
+  if (li <= hj) { l = li; h = hj; }
 }
 
 // The tune of every kernel the pd_* knobs do not reach (the stacked and the linear

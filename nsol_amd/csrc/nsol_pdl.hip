@@ -18,7 +18,8 @@
 //     clip.  11 words per voxel in 3-D as k_pd_fused (read xbar, x, g, p[3]; write
 //     xbar, x, p[3]).
 // Single volumes, one iteration per launch, contiguous arrays: there is no
-// multi-iteration, persistent, stacked or pitched form.
+// multi-iteration, persistent or pitched form.  The member-stacked form of both
+// kernels (an alpha sweep, a stack of images) is nsol_pdls.hip.
 #include <math.h>
 #include <stddef.h>
 
@@ -87,21 +88,6 @@ struct LinLauncher {
         a, pd_auto_rows_per_lane<VEC, LX>(a.G, 1));
   }
 };
-
-// The box in the kernels' type, rounded towards its inside: a float32 iterate inside
-// [(float)lo, (float)hi] rounded to nearest could lie outside the caller's [lo, hi].
-template <typename T> inline void box_in(double lo, double hi, T &l, T &h);
-template <> inline void box_in<double>(double lo, double hi, double &l, double &h) {
-  l = lo; h = hi;
-}
-template <> inline void box_in<float>(double lo, double hi, float &l, float &h) {
-  l = (float)lo; h = (float)hi;
-  if (lo == hi) return;
-  float li = l, hj = h;
-  if ((double)li < lo) li = nextafterf(li, INFINITY);
-  if ((double)hj > hi) hj = nextafterf(hj, -INFINITY);
-  if (li <= hj) { l = li; h = hj; }
-}
 
 template <typename T>
 int lin_iter_impl(const T *xbar_in, T *xbar_out, T *x, const T *g, const T *p_in,

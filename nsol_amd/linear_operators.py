@@ -284,6 +284,100 @@ class ConvolutionOperator(DeviceOperator):
                               self.mode)
 
 
+    # ---- `members` volumes of one shape, member-major in one flat tensor
+    # (nsol_amd/linear_stack.py).  Every member's result has the bits _apply /
+    # apply_axpby give for it alone: the kernels pick their access form from the
+    # 16-byte alignment of their pointers, so a member whose slice does not start on
+    # one goes through an aligned copy, as a single run's own tensors are.
+    def _stack_batches_passes(self, in_shape):
+        """The 1-D passes of a separable 1-D / 2-D operator run over the whole stack
+        at once: no pass runs along the member axis."""
+        return self._passes is not None and self.dimension < 3 and \
+            len(in_shape) == self.dimension
+
+    def stacked_launches(self, in_shape, members):
+        """Launches _apply_stacked makes for `members` volumes of in_shape."""
+        if self._stack_batches_passes(in_shape):
+            return max(len(self._passes), 1)
+        return int(members) * max(self._launches(in_shape), 1)
+
+    def _launches(self, in_shape):
+        if self._passes is None:
+            return 1
+        if USE_FUSED_BLUR3 and self._fusable3():
+            return 1            # (three where nsol_corr3_wrap_* declines the shape)
+        return len(self._passes)
+
+    def _apply_stacked(self, x, in_shape, members, out=None):
+        """A applied to every one of the `members` volumes of in_shape that the flat
+        device tensor x holds; returns the flat stacked result (`out` when given).
+        A separable 1-D / 2-D operator: ONE ops.corr_axis launch per pass over the
+        padded shape (members, ny, nx) (1-D: (1, members, nx)).  Everything else --
+        3-D, dense taps -- member by member on its slice, with exactly the call
+        _apply makes."""
+        members = int(members)
+        n = int(np.prod(in_shape))
+        if len(in_shape) != self.dimension:
+            raise RuntimeError("%dD convolution applied to %d axes" %
+                               (self.dimension, len(in_shape)))
+        if x.numel() != members * n or (out is not None and
+                                        (out.numel() != x.numel() or
+                                         out.dtype != x.dtype)):
+            raise ValueError("operand mismatch: %d members of %d elements against "
+                             "x[%d]" % (members, n, x.numel()))
+        if self._stack_batches_passes(in_shape):
+            if not self._passes:
+                return x.clone() if out is None else out.copy_(x)
+            padded = (members,) + tuple(in_shape) if self.dimension == 2 else \
+                (1, members) + tuple(in_shape)
+            cur = x
+            for k, (axis3, taps, centre) in enumerate(self._passes):
+                last = k == len(self._passes) - 1
+                cur = ops.corr_axis(cur, padded, axis3, taps, centre, self.mode,
+                                    out=out if last else None)
+            return cur
+        if out is None:
+            out = ops.empty_like(x)
+        on_slices = (n * x.element_size()) % 16 == 0
+        for m in range(members):
+            xm = x[m * n:(m + 1) * n]
+            if on_slices and USE_FUSED_BLUR3 and self._passes and self._fusable3() and \
+                    ops.corr3_wrap(xm, in_shape, self._passes[0][1], self._passes[1][1],
+                                   self._passes[2][1],
+                                   out=out[m * n:(m + 1) * n]) is not None:
+                continue
+            out[m * n:(m + 1) * n].copy_(
+                self._apply(xm if on_slices else xm.clone(), in_shape))
+        return out
+
+    def apply_axpby_stacked(self, x, io, in_shape, members, ca, cb, results=None):
+        """apply_axpby on every one of the `members` volumes: io = ca A(x) + cb io in
+        place, member by member (the one-pass blur is a 3-D kernel); results: a
+        float64 device tensor with a slot per member for the sums.  None when the
+        kernel does not apply -- decided on the first member, with nothing run; the
+        choice depends on the shape alone, so a later member that declines is an
+        error."""
+        members = int(members)
+        n = int(np.prod(in_shape))
+        on_slices = (n * x.element_size()) % 16 == 0
+        for m in range(members):
+            xm, iom = x[m * n:(m + 1) * n], io[m * n:(m + 1) * n]
+            slot = None if results is None else results[m:m + 1]
+            if on_slices:
+                got = self.apply_axpby(xm, iom, in_shape, ca, cb, result=slot)
+            else:
+                tmp = iom.clone()
+                got = self.apply_axpby(xm.clone(), tmp, in_shape, ca, cb, result=slot)
+                if got is not None:
+                    iom.copy_(tmp)
+            if got is None:
+                if m == 0:
+                    return None
+                raise RuntimeError("the blur's epilogue declined member %d of a stack "
+                                   "it had taken" % m)
+        return results if results is not None else True
+
+
 class LinearOperators(object):
 
     def __init__(self, dimension, spacing):

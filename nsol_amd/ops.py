@@ -1753,6 +1753,106 @@ def pdl_iter(xbar_in, xbar_out, x, g, p_in, p_out, shape, w, sigma, hden, tau, t
     return True
 
 
+# ------------------------------ the same, member-stacked (nsol_pdls.hip) ----
+# An alpha sweep on one observation or a stack of images of one shape
+# (nsol_amd/linear_stack.py).  A member's state is x, two xbar, q, g = A^T q and two p
+# (5 + 2 dim arrays), plus its own scaled observation, its own weights and t = A xbar
+# where the caller counts them (a sweep shares the first two, the blur's epilogue
+# spares the third).  The constant decides speed only, as the other stacks' do.
+PDL_STACK_GROUP_BYTES = 256 << 20
+
+
+def pdl_stack_launches():
+    """Launches of k_pdl_stack / k_pdl_stack_iso so far (for tests and tools)."""
+    return int(_lib.load().nsol_pdl_stack_launches())
+
+
+def pdl_group_size(members, n, dim, elem_size, own_data=True, own_weights=False,
+                   with_t=True):
+    """Members per stacked group of PrimalDualLinearSolver runs: 5 + 2 dim arrays per
+    member and one more each for a member's own observation (own_data), its own
+    weights (own_weights) and t = A xbar (with_t), under PDL_STACK_GROUP_BYTES, at
+    most 65535 members."""
+    arrays = 5 + int(bool(own_data)) + int(bool(own_weights)) + int(bool(with_t))
+    return _group_size(members, n, dim, elem_size, arrays, PDL_STACK_GROUP_BYTES, 65535)
+
+
+def pdl_lambdas(lmbda, like):
+    """The members' lambdas as pdl_stack_dual_data takes them: a device array in the
+    element type of `like`, each rounded as pdl_dual_data rounds its own."""
+    lm = np.ascontiguousarray(lmbda, dtype=np.float64).reshape(-1)
+    if lm.size < 1 or not np.all(lm >= 0):
+        raise ValueError("lmbda: at least one value, all >= 0")
+    host = lm.astype(np.float32 if like.dtype == torch.float32 else np.float64)
+    return torch.from_numpy(host).to(like.device)
+
+
+def pdl_stack_dual_data(q, t, bt, wt, sigma, lmbda, members, l1=False):
+    """pdl_dual_data on `members` stacked runs in one launch: q (and t, where given)
+    hold members * n elements, member-major; bt and wt (None: all 1) hold n elements
+    (shared by the members) or members * n (member-major), each on its own; lmbda is
+    pdl_lambdas' device array.  Every member's q has the bits pdl_dual_data gives it
+    alone.  Returns False when the library declined (nothing was launched).  Does not
+    synchronise."""
+    members = int(members)
+    _chk(q)
+    _chk(bt)
+    _chk(lmbda)
+    if members < 1 or q.numel() % members:
+        raise ValueError("operand mismatch: q[%d] for %d members" % (q.numel(), members))
+    n = q.numel() // members
+    if t is not None:
+        _same(q, t)
+    if wt is not None:
+        _chk(wt)
+    if bt.dtype != q.dtype or lmbda.dtype != q.dtype or lmbda.numel() != members or \
+            bt.numel() not in (n, members * n) or \
+            (wt is not None and (wt.dtype != q.dtype or
+                                 wt.numel() not in (n, members * n))):
+        raise ValueError("operand mismatch: %d members of %d elements against bt[%d], "
+                         "wt[%s], lmbda[%d]" % (
+                             members, n, bt.numel(),
+                             "-" if wt is None else wt.numel(), lmbda.numel()))
+    bts = 0 if bt.numel() == n else n
+    wts = 0 if wt is None or wt.numel() == n else n
+    rc = _fn("pdl_stack_dual_data", q)(
+        _p(q), _p(t), _p(bt), bts, _p(wt), wts, float(sigma), _p(lmbda), int(bool(l1)),
+        members, n, stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pdl_stack_dual_data")
+    _wrote(q)
+    return True
+
+
+def pdl_stack_iter(xbar_in, xbar_out, x, g, p_in, p_out, members, shape, w, sigma, hden,
+                   tau, theta, lo, hi, flags, has_p=True):
+    """pdl_iter on `members` stacked runs in one launch: x, xbar_in/out and g hold
+    members * n elements, p_in/out members * dim * n, member-major; the scalars, the
+    flags and the box are common to the stack.  Every member has the bits pdl_iter
+    gives it alone.  Returns False when the library declined (nothing was launched).
+    Does not synchronise."""
+    ndim, nz, ny, nx = dims3(shape)
+    members = int(members)
+    n = nz * ny * nx
+    _same(x, xbar_in, xbar_out, g)
+    _same(p_out, p_in)
+    if p_out.dtype != x.dtype or members < 1 or x.numel() != members * n or \
+            p_out.numel() != members * ndim * n:
+        raise ValueError("operand mismatch: %d members of shape %r against x %s[%d], "
+                         "p %s[%d]" % (members, tuple(shape), str(x.dtype), x.numel(),
+                                       str(p_out.dtype), p_out.numel()))
+    rc = _fn("pdl_stack_iter", x)(
+        _p(xbar_in), _p(xbar_out), _p(x), _p(g), _p(p_in), _p(p_out), members, ndim, nz,
+        ny, nx, w[0], w[1], w[2], float(sigma), float(hden), float(tau), float(theta),
+        float(lo), float(hi), int(flags), int(bool(has_p)), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pdl_stack_iter")
+    _wrote(xbar_out, x, p_out)
+    return True
+
+
 # ------------------------------------------------------ stopping rule ----
 # (nsol_pdc.hip; the rule itself is primal_dual_solver.py's)
 PD_CHECK_SUMS = 4

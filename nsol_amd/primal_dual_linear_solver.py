@@ -23,7 +23,9 @@ indicator, so the accelerated schedules do not apply) is
 
 one application of A, one of A^T, one element-wise kernel (ops.pdl_dual_data) and one
 pass of the fused primal-dual tile (ops.pdl_iter, nsol_pdl.hip).  Weights, masks, the
-l1 data term and the box cost nothing extra.
+l1 data term and the box cost nothing extra.  A list of such solvers on volumes of one
+shape, or one observation under several alphas, runs in stacked launches through
+PrimalDualLinearBatch / PrimalDualLinearSweep (nsol_amd/linear_stack.py, nsol_pdls.hip).
 
 `run()` picks one of three execution forms for A and A^T; the regulariser side is
 nsol_pdl_iter_* in all of them:
