@@ -148,6 +148,38 @@ int nsol_corr_axis_f32(const float *x, float *out, int axis, int64_t nz,
 int nsol_corr_axis_f64(const double *x, double *out, int axis, int64_t nz,
                        int64_t ny, int64_t nx, const double *taps_host,
                        int ntaps, int centre, int mode, void *stream);
+/* Blur-and-sample along one ARRAY axis and its exact transpose (nsol_sample.hip): the
+ * per-axis halves of the acquisition model A = S G, "a point-spread function, then keep
+ * every factor-th sample from `offset` on".  With len the extent of (nz, ny, nx) along
+ * `axis`, f = factor, o = offset, c = centre and m = ceil((len - o) / f):
+ *   down:  out[j] = sum_t taps_host[t] * x[map(o + j f - c + t)]            j in [0, m)
+ *   up:    out[i] = sum_t taps_host[t] * q[(P - o) / f]  over the t with P >= o,
+ *          (P - o) % f == 0 and (P - o) / f < m, where P = (i + c - t) mod len (wrap),
+ *          or P = i + c - t where 0 <= P < len and no term otherwise (constant)
+ * `map` is nsol_corr_axis_*'s index mapping: periodic (wrap) or zero outside
+ * (constant).  `up` is the exact matrix transpose of `down`, and down equals
+ * nsol_corr_axis_* followed by [o::f].  (nz, ny, nx) is the FULL-RESOLUTION side in
+ * both calls -- the input of down, the output of up; the other side has extent m along
+ * `axis` and the same extents elsewhere.  taps_host are the FORWARD taps in both calls
+ * (HOST pointer, ntaps <= 129); up applies the transpose itself.  Gathers on both
+ * sides: no atomics, the same bits on every run; 64-bit indexing, accumulation in the
+ * element type over t upwards.  The operands must not alias.
+ * NSOL_EINVAL, nothing launched: a missing pointer, an extent < 1, axis outside 0..2,
+ * ntaps outside 1..129, centre outside the taps, a mode other than NSOL_MODE_WRAP /
+ * NSOL_MODE_CONSTANT (the transpose of the other modes is not a correlation),
+ * factor < 1, offset outside [0, min(factor, len)). */
+int nsol_corr_axis_down_f32(const float *x, float *out, int axis, int64_t nz,
+                            int64_t ny, int64_t nx, const double *taps_host, int ntaps,
+                            int centre, int mode, int factor, int offset, void *stream);
+int nsol_corr_axis_down_f64(const double *x, double *out, int axis, int64_t nz,
+                            int64_t ny, int64_t nx, const double *taps_host, int ntaps,
+                            int centre, int mode, int factor, int offset, void *stream);
+int nsol_corr_axis_up_f32(const float *q, float *out, int axis, int64_t nz, int64_t ny,
+                          int64_t nx, const double *taps_host, int ntaps, int centre,
+                          int mode, int factor, int offset, void *stream);
+int nsol_corr_axis_up_f64(const double *q, double *out, int axis, int64_t nz, int64_t ny,
+                          int64_t nx, const double *taps_host, int ntaps, int centre,
+                          int mode, int factor, int offset, void *stream);
 /* Separable periodic ("wrap") 3-D correlation in one pass over memory: the
  * Gaussian blur A = A^T of linear_operators.py:82-86 on a volume, 8 bytes per
  * voxel instead of 24 for three nsol_corr_axis_* passes.  taps_* are HOST arrays

@@ -33,6 +33,14 @@ data), run together through PrimalDualLinearBatch and reassembled; a single --al
 no --observe-every.  With --tolerance the members of either run one after the other
 (the tool says so).
 
+--solver PDL --upsample F [F ...] [--sample-offset O [O ...]]: super-resolution.  The
+observation is the COARSE data of the model "blur, then keep every F-th sample from O
+on" (SampledConvolutionOperator), one factor per ARRAY axis.  The result has shape
+obs.shape * F and the spacing obs spacing / F (a NIfTI result carries it); --blur is
+read on that fine grid; the start is sampled_start (A^T b / A^T 1).  --mask / --weights
+keep the observation's shape, --reference has the result's.  Not with --slice-wise or
+--result-dir, whose stacked forms need b and x on one grid.
+
 With --reference, the measures are evaluated through an Observer on the flat
 iterates against the flat reference (as run_denoising does and as the
 reference's tool does) and printed as first -> last value.
@@ -96,14 +104,79 @@ def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.
         verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every)
 
 
+def fine_grid(shape, spacing, factors):
+    """(fine shape, fine spacing) of an observation upsampled by `factors` (one per
+    ARRAY axis); spacing[0] belongs to the LAST array axis."""
+    factors = [int(f) for f in factors]
+    if len(factors) != len(shape) or min(factors) < 1:
+        raise ValueError("--upsample takes one factor >= 1 per axis of the "
+                         "observation (%d), not %r" % (len(shape), factors))
+    fine_shape = tuple(int(s) * f for s, f in zip(shape, factors))
+    fine_spacing = np.atleast_1d(spacing).astype(float) / np.array(factors[::-1], float)
+    return fine_shape, fine_spacing
+
+
+def sampled_pdl_wiring(observed_nda, spacing, blur, factors, offsets=None,
+                       reconstruction_type="TVL2", alpha=0.01, iterations=10, verbose=0,
+                       dtype=None, tolerance=None, check_every=10, weights=None,
+                       pdl_data_loss="ell2", nonnegative=False, isotropic=False):
+    """PrimalDualLinearSolver's keyword arguments for --upsample: the observation is
+    the coarse data of a SampledConvolutionOperator on the fine grid."""
+    dimension = observed_nda.ndim
+    coarse = observed_nda.shape
+    fine_shape, fine_spacing = fine_grid(coarse, spacing, factors)
+    sigma = np.atleast_1d(blur).astype(float)
+    cov = np.diag(np.ones(dimension)) * sigma ** 2
+    if dimension == 1:
+        cov = float(cov.reshape(-1)[0])
+    lo = getattr(LinearOperators, "LinearOperators%dD" % dimension)(
+        spacing=fine_spacing)
+    A, A_adj = lo.get_sampled_gaussian_blurring_operators(
+        cov, factors, offsets, fine_shape=fine_shape)
+    if A._out_shape(fine_shape) != tuple(coarse):
+        raise ValueError("the observation's shape %r is not what the factors and "
+                         "offsets keep of the fine grid %r" % (tuple(coarse), fine_shape))
+    b = observed_nda.flatten()
+    x_scale = np.max(observed_nda)
+    seen = np.array(observed_nda, dtype=np.float64)
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.shape != observed_nda.shape:
+            raise ValueError("the weights have shape %s, the observation %s" %
+                             (weights.shape, observed_nda.shape))
+        counted = weights > 0
+        x_scale = np.max(observed_nda[counted]) if counted.any() else 1.
+        seen[~counted & ~np.isfinite(seen)] = 0
+        weights = weights.flatten()
+    x0 = LinearOperators.sampled_start(A_adj, seen, fine_shape).flatten()
+    A_1D = lambda x: A(x.reshape(*fine_shape)).flatten()
+    A_adj_1D = lambda q: A_adj(q.reshape(*coarse)).flatten()
+    return dict(
+        A=A_1D, A_adj=A_adj_1D, b=b, x0=x0, dimension=dimension, spacing=fine_spacing,
+        alpha=alpha, iterations=iterations,
+        reg_type="TV" if reconstruction_type == "TVL2" else "huber",
+        isotropic=isotropic, data_loss=pdl_data_loss, weights=weights,
+        bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
+        verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every,
+        shape=fine_shape)
+
+
 def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  tv_solver="PD", alpha=0.01, iterations=10, iter_max=10,
                  rho=0.1, minimizer="lsmr", data_loss="linear",
                  data_loss_scale=1., L2=8, verbose=0, dtype=None,
                  tolerance=None, check_every=10, weights=None, pdl_data_loss="ell2",
-                 nonnegative=False, isotropic=False):
+                 nonnegative=False, upsample=None, sample_offset=None, isotropic=False):
     """weights, pdl_data_loss ("ell2" | "ell1") and nonnegative belong to
-    tv_solver="PDL" (PrimalDualLinearSolver)."""
+    tv_solver="PDL" (PrimalDualLinearSolver), and so do upsample / sample_offset (one
+    integer per array axis: the observation is the coarse data, sampled_pdl_wiring)."""
+    if upsample is not None:
+        if not (reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL"):
+            raise ValueError("upsample belongs to tv_solver='PDL'")
+        return pdl.PrimalDualLinearSolver(**sampled_pdl_wiring(
+            observed_nda, spacing, blur, upsample, sample_offset, reconstruction_type,
+            alpha, iterations, verbose, dtype, tolerance, check_every, weights,
+            pdl_data_loss, nonnegative, isotropic))
     if reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL":
         return pdl.PrimalDualLinearSolver(**pdl_wiring(
             observed_nda, spacing, blur, reconstruction_type, alpha, iterations,
@@ -314,6 +387,13 @@ def main(argv=None):
                          "independent 2-D images under the 2-D Gaussian of --blur, each "
                          "scaled by its own maximum, and run them stacked "
                          "(PrimalDualLinearBatch)")
+    ap.add_argument("--upsample", type=int, nargs="+", default=None, metavar="F",
+                    help="--solver PDL: super-resolution -- the observation is the "
+                         "blurred fine image with every F-th sample kept, one factor "
+                         "per ARRAY axis; the result has shape obs.shape * F")
+    ap.add_argument("--sample-offset", type=int, nargs="+", default=None, metavar="O",
+                    help="with --upsample: the first kept sample along every array "
+                         "axis, 0 <= O < F (default: zeros)")
     ap.add_argument("--tolerance", type=float, default=None, metavar="T",
                     help="--solver PD or PDL, TVL2 / HuberL2: stop once the relative change "
                          "of the primal and of the dual iterate in one iteration is "
@@ -358,17 +438,52 @@ def main(argv=None):
         ap.error("--slice-wise does not take --observe-every: the measures are "
                  "taken once, on the reassembled volume")
 
+    if args.sample_offset is not None and args.upsample is None:
+        ap.error("--sample-offset belongs to --upsample")
+    if args.upsample is not None:
+        if not linear:
+            ap.error("--upsample is an option of --solver PDL: the other solvers' "
+                     "native paths assume an observation on the result's own grid "
+                     "(b.size == x.size)")
+        if args.slice_wise:
+            ap.error("--upsample does not go with --slice-wise: the stacked batch "
+                     "holds b and x on one grid, and the sampled operator acts on "
+                     "the whole volume")
+        if args.result_dir is not None:
+            ap.error("--upsample does not go with --result-dir: the stacked sweep "
+                     "holds b and x on one grid; loop over --alpha without it")
+        if min(args.upsample) < 1:
+            ap.error("--upsample takes factors >= 1")
+        offs = args.sample_offset or [0] * len(args.upsample)
+        if len(offs) != len(args.upsample) or \
+                any(not 0 <= o < f for o, f in zip(offs, args.upsample)):
+            ap.error("--sample-offset takes one offset per --upsample factor with "
+                     "0 <= O < F")
+
     reader = dr.DataReader(args.observation)
     reader.read_data()
     observed_nda = reader.get_data()
     info = reader.get_image_sitk()
     spacing = np.ones(observed_nda.ndim) if info is None \
         else np.array(info.GetSpacing())
+    result_shape = observed_nda.shape
+    if args.upsample is not None:
+        if len(args.upsample) != observed_nda.ndim:
+            ap.error("--upsample takes one factor per axis of the observation (%d), "
+                     "not %d" % (observed_nda.ndim, len(args.upsample)))
+        result_shape, fine_spacing = fine_grid(observed_nda.shape, spacing,
+                                               args.upsample)
+        if info is not None:       # the result is written on the fine grid
+            info = dr.ImageInfo(fine_spacing, info.header)
     x_ref = None
     if args.reference is not None:
         ref_reader = dr.DataReader(args.reference)
         ref_reader.read_data()
-        x_ref = ref_reader.get_data().flatten()
+        x_ref = ref_reader.get_data()
+        if args.upsample is not None and x_ref.shape != tuple(result_shape):
+            ap.error("--reference has shape %s; with --upsample it has the result's, "
+                     "%s" % (x_ref.shape, tuple(result_shape)))
+        x_ref = x_ref.flatten()
     weights = None
     if linear:
         try:
@@ -382,6 +497,9 @@ def main(argv=None):
         return run_slice_wise(args, observed_nda, spacing, x_ref, info, weights)
     if args.result_dir is not None:
         return run_sweep(args, observed_nda, spacing, x_ref, info, weights)
+    # (without --upsample the call is what it was)
+    sampled = {} if args.upsample is None else dict(upsample=args.upsample,
+                                                    sample_offset=args.sample_offset)
     for alpha in args.alpha:
         solver = build_solver(
             observed_nda, spacing, args.blur, args.reconstruction_type,
@@ -390,7 +508,7 @@ def main(argv=None):
             args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic,
             tolerance=args.tolerance, check_every=args.check_every, weights=weights,
             pdl_data_loss="ell1" if args.data_loss == "ell1" else "ell2",
-            nonnegative=args.nonnegative)
+            nonnegative=args.nonnegative, **sampled)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \
@@ -401,7 +519,7 @@ def main(argv=None):
                 for m in args.measures})
             solver.set_observer(obs)
         solver.run()
-        recon = np.array(solver.get_x().reshape(*observed_nda.shape))
+        recon = np.array(solver.get_x().reshape(*result_shape))
         print("%s alpha=%g: %s" % (args.reconstruction_type, alpha,
                                    solver.get_computational_time()))
         if args.tolerance is not None:

@@ -378,6 +378,182 @@ class ConvolutionOperator(DeviceOperator):
         return results if results is not None else True
 
 
+def _per_axis_ints(values, dimension, what, default):
+    if values is None:
+        return [default] * dimension
+    try:
+        vals = [v for v in np.atleast_1d(np.asarray(values, dtype=object)).tolist()]
+        if len(vals) != dimension:
+            raise ValueError
+        out = [int(v) for v in vals]
+        if any(float(v) != o for v, o in zip(vals, out)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("%s must hold one integer per array axis (%d)" %
+                         (what, dimension))
+    return out
+
+
+class SampledConvolutionOperator(DeviceOperator):
+    """Acquisition on a coarser grid, A = S G:
+        x -> scipy.ndimage.convolve(x, kernel, mode)[o_0::f_0, o_1::f_1, ...]
+    on the GPU, computing only the samples it keeps (ops.corr_axis_down).
+
+    factors, offsets: one integer per ARRAY AXIS, in the order of `kernel`'s axes --
+    factors[0] belongs to the first (slowest) axis.  This is NOT the reversed order
+    of `spacing`, whose first entry belongs to the last array axis.  f >= 1 and
+    0 <= o < f; offsets=None: zeros.  mode: "wrap" or "constant" (the transpose of
+    the other boundary modes is not a correlation).  The kernel must be separable
+    (an outer product, as every Gaussian with a diagonal covariance) with at most
+    129 taps per axis.  Everything else raises ValueError.
+
+    The passes run the axes with f > 1 first, largest factor first (ties in axis
+    order), each on the grid the earlier ones have reduced; the axes with f = 1
+    follow on the reduced grid through ops.corr_axis.  adjoint() is the exact
+    transpose, the same list backwards."""
+    kind = "sampled_conv"
+
+    def __init__(self, dimension, kernel, factors, offsets=None, mode="wrap"):
+        kernel = np.asarray(kernel, dtype=np.float64)
+        dimension = int(dimension)
+        if dimension not in (1, 2, 3) or kernel.ndim != dimension:
+            raise ValueError("the kernel must have %d axes" % dimension)
+        if mode not in ops.SAMPLED_MODES:
+            raise ValueError("mode '%s': only 'wrap' and 'constant' have a transpose "
+                             "that is a correlation" % (mode,))
+        factors = _per_axis_ints(factors, dimension, "factors", 1)
+        offsets = _per_axis_ints(offsets, dimension, "offsets", 0)
+        if any(f < 1 for f in factors):
+            raise ValueError("factors must be >= 1")
+        if any(not 0 <= o < f for o, f in zip(offsets, factors)):
+            raise ValueError("offsets must satisfy 0 <= offset < factor")
+        flipped, centre = _ndimage_convolve_params(kernel)
+        facs = _rank1_factors(flipped)
+        if facs is None or max(f.size for f in facs) > 129:
+            raise ValueError("the kernel must be separable with at most 129 taps per "
+                             "axis (a dense form is not provided)")
+        self.dimension = dimension
+        self.kernel = kernel
+        self.mode = mode
+        self.factors, self.offsets = tuple(factors), tuple(offsets)
+        self._taps = [np.ascontiguousarray(f, dtype=np.float64) for f in facs]
+        self._centre = list(centre)
+        # the pass order: sampled axes by falling factor, then the others
+        self._down = sorted((a for a in range(dimension) if factors[a] > 1),
+                            key=lambda a: (-factors[a], a))
+        self._plain = [a for a in range(dimension) if factors[a] == 1 and
+                       not (self._taps[a].size == 1 and self._taps[a][0] == 1.0)]
+
+    def _check(self, shape):
+        if len(shape) != self.dimension:
+            raise RuntimeError("%dD operator applied to an array with %d axes" %
+                               (self.dimension, len(shape)))
+
+    def _out_shape(self, in_shape):
+        self._check(in_shape)
+        for s, o in zip(in_shape, self.offsets):
+            if not int(s) > o:
+                raise ValueError("offset %d is outside an axis of extent %d" % (o, s))
+        return tuple(ops.sampled_extent(s, f, o)
+                     for s, f, o in zip(in_shape, self.factors, self.offsets))
+
+    def _apply(self, x, in_shape):
+        self._out_shape(in_shape)
+        d = self.dimension
+        cur_shape = [int(s) for s in in_shape]
+        cur = x
+        for a in self._down:
+            cur = ops.corr_axis_down(cur, cur_shape, a + 3 - d, self._taps[a],
+                                     self._centre[a], self.mode, self.factors[a],
+                                     self.offsets[a])
+            cur_shape[a] = ops.sampled_extent(cur_shape[a], self.factors[a],
+                                              self.offsets[a])
+        for a in self._plain:
+            cur = ops.corr_axis(cur, cur_shape, a + 3 - d, self._taps[a],
+                                self._centre[a], self.mode)
+        return cur.clone() if cur is x else cur
+
+    def adjoint(self, fine_shape=None):
+        """The exact transpose, a SampledConvolutionAdjointOperator.  fine_shape: the
+        shape of the fine grid it maps to; None: factor * extent on every axis."""
+        return SampledConvolutionAdjointOperator(self, fine_shape)
+
+
+class SampledConvolutionAdjointOperator(DeviceOperator):
+    """The exact transpose of a SampledConvolutionOperator: the sampled data spread
+    back onto the fine grid and correlated with the transposed taps
+    (ops.corr_axis_up), the forward operator's passes backwards.
+
+    The coarse shape does not determine the fine one: an extent m belongs to every
+    fine extent from o + (m - 1) f + 1 to o + m f.  The operator is therefore BUILT
+    WITH the fine shape (fine_shape=); without one it maps to f * m on every axis,
+    the grid of an observation upsampled by whole factors."""
+    kind = "sampled_conv_adj"
+
+    def __init__(self, forward, fine_shape=None):
+        if not isinstance(forward, SampledConvolutionOperator):
+            raise ValueError("the adjoint is built from a SampledConvolutionOperator")
+        self.forward = forward
+        self.dimension = forward.dimension
+        if fine_shape is not None:
+            fine_shape = tuple(int(s) for s in fine_shape)
+            forward._out_shape(fine_shape)
+        self.fine_shape = fine_shape
+
+    def _out_shape(self, in_shape):
+        fw = self.forward
+        fw._check(in_shape)
+        in_shape = tuple(int(s) for s in in_shape)
+        fine = self.fine_shape
+        if fine is None:
+            fine = tuple(s * f for s, f in zip(in_shape, fw.factors))
+        if fw._out_shape(fine) != in_shape:
+            raise ValueError("a sampled array of shape %r does not belong to the fine "
+                             "grid %r (pass fine_shape=)" % (in_shape, fine))
+        return fine
+
+    def _apply(self, q, in_shape):
+        fw, d = self.forward, self.dimension
+        fine = self._out_shape(in_shape)
+        cur_shape = [int(s) for s in in_shape]
+        cur = q
+        for a in reversed(fw._plain):
+            taps = fw._taps[a]
+            cur = ops.corr_axis(cur, cur_shape, a + 3 - d, taps[::-1],
+                                taps.size - 1 - fw._centre[a], fw.mode)
+        for a in reversed(fw._down):
+            cur_shape[a] = fine[a]
+            cur = ops.corr_axis_up(cur, cur_shape, a + 3 - d, fw._taps[a],
+                                   fw._centre[a], fw.mode, fw.factors[a],
+                                   fw.offsets[a])
+        return cur.clone() if cur is q else cur
+
+
+def sampled_start(A_adj, b, fine_shape):
+    """The usual start on the fine grid for a sampled observation b: A^T b / A^T 1,
+    with 0 where A^T 1 == 0 (fine voxels no sample sees).  A_adj: the adjoint operator
+    (or a callable on arrays of the coarse shape); b: the coarse data, NumPy array or
+    device tensor; returns an array of fine_shape of b's kind."""
+    fine_shape = tuple(int(s) for s in fine_shape)
+    if isinstance(A_adj, SampledConvolutionAdjointOperator):
+        coarse = A_adj.forward._out_shape(fine_shape)
+        if A_adj._out_shape(coarse) != fine_shape:
+            raise ValueError("the adjoint maps to %r, not to fine_shape %r" %
+                             (A_adj._out_shape(coarse), fine_shape))
+        b = b.reshape(coarse)
+    if is_device_tensor(b):
+        import torch
+        num, den = A_adj(b), A_adj(torch.ones_like(b))
+        safe = torch.where(den != 0, den, torch.ones_like(den))
+        return torch.where(den != 0, num / safe, torch.zeros_like(num)).reshape(
+            fine_shape)
+    b = np.asarray(b)
+    num, den = np.asarray(A_adj(b)), np.asarray(A_adj(np.ones_like(b)))
+    out = np.zeros_like(num)
+    np.divide(num, den, out=out, where=den != 0)
+    return out.reshape(fine_shape)
+
+
 class LinearOperators(object):
 
     def __init__(self, dimension, spacing):
@@ -402,6 +578,23 @@ class LinearOperators(object):
     def get_gaussian_blurring_operators(self, cov, alpha_cut=3):
         kernel = self._kernels.get_gaussian(cov=cov, alpha_cut=alpha_cut)
         return self.get_convolution_and_adjoint_convolution_operators(kernel)
+
+    def get_sampled_convolution_operators(self, kernel, factors, offsets=None,
+                                          mode="wrap", fine_shape=None):
+        """(A, A_adj) of the acquisition model "blur, then keep every f-th sample":
+        SampledConvolutionOperator and its exact transpose.  factors / offsets: one
+        integer per ARRAY axis (not spacing's reversed order); fine_shape: the fine
+        grid the adjoint maps to (None: factor * extent on every axis)."""
+        A = SampledConvolutionOperator(self._dimension, kernel, factors, offsets, mode)
+        return A, A.adjoint(fine_shape)
+
+    def get_sampled_gaussian_blurring_operators(self, cov, factors, offsets=None,
+                                                alpha_cut=3, fine_shape=None):
+        """The same with the Gaussian of get_gaussian_blurring_operators, whose
+        spacing is the FINE grid's (periodic boundary)."""
+        kernel = self._kernels.get_gaussian(cov=cov, alpha_cut=alpha_cut)
+        return self.get_sampled_convolution_operators(kernel, factors, offsets,
+                                                      fine_shape=fine_shape)
 
     def _axis_operators(self, direction, mode):
         if direction >= self._dimension:

@@ -34,7 +34,9 @@ with equal taps, mode and dimension, and they agree in what member_key() lists; 
 b, x0, x_scale and the weights may differ.  Everything else runs `solver.run()`, one
 after the other ("sequential"): a tolerance (members do not stop one by one here), an
 observer that keeps iterates on the host, foreign callables, a verbose solver, a stack
-of one, a geometry the library declines on its first launch.
+of one, a geometry the library declines on its first launch, and every other operator
+of the package -- a SampledConvolutionOperator pair keeps b and q on the coarse grid
+and x on the fine one (m != n), which the stacked state does not hold.
 """
 import datetime
 import time

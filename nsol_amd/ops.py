@@ -164,6 +164,64 @@ def corr_axis(x, shape, axis3, taps, centre, mode, out=None):
     return _wrote(out)
 
 
+SAMPLED_MODES = ("wrap", "constant")
+
+
+def sampled_extent(length, factor, offset):
+    """Samples that [offset::factor] keeps of `length`: ceil((length - offset) / factor)."""
+    return -((int(offset) - int(length)) // int(factor))
+
+
+def _sampled_call(name, src, shape, axis3, taps, centre, mode, factor, offset, out, up):
+    _chk(src)
+    _, nz, ny, nx = dims3(shape)
+    if mode not in SAMPLED_MODES:
+        raise ValueError("%s: mode '%s' has no transpose that is a correlation "
+                         "(supported: wrap, constant)" % (name, mode))
+    factor, offset = int(factor), int(offset)
+    full = (nz, ny, nx)
+    if int(axis3) not in (0, 1, 2):
+        raise ValueError("%s: axis3 must be 0, 1 or 2" % name)
+    length = full[int(axis3)]
+    if factor < 1 or not 0 <= offset < min(factor, length):
+        raise ValueError("%s: factor %d, offset %d on an axis of extent %d" %
+                         (name, factor, offset, length))
+    coarse = list(full)
+    coarse[int(axis3)] = sampled_extent(length, factor, offset)
+    n_full, n_coarse = nz * ny * nx, coarse[0] * coarse[1] * coarse[2]
+    n_in, n_out = (n_coarse, n_full) if up else (n_full, n_coarse)
+    if src.numel() != n_in:
+        raise ValueError("operand mismatch: %d elements for the %d of shape %r" %
+                         (src.numel(), n_in, tuple(shape)))
+    taps = np.ascontiguousarray(taps, dtype=np.float64)
+    if out is None:
+        out = empty_like(src, n_out)
+    else:
+        _chk(out)
+        if out.dtype != src.dtype or out.numel() != n_out:
+            raise ValueError("operand mismatch: out %s[%d], expected %s[%d]" %
+                             (str(out.dtype), out.numel(), str(src.dtype), n_out))
+    _lib.check(_fn(name, src)(
+        _p(src), _p(out), int(axis3), nz, ny, nx, taps.ctypes.data, int(taps.size),
+        int(centre), MODES[mode], factor, offset, stream_ptr()), "nsol_" + name)
+    return _wrote(out)
+
+
+def corr_axis_down(x, shape, axis3, taps, centre, mode, factor, offset, out=None):
+    """corr_axis followed by [offset::factor] along axis3, computing only the samples
+    it keeps.  shape: the FULL-RESOLUTION volume x holds; the result has
+    sampled_extent(...) along axis3.  mode: "wrap" or "constant"."""
+    return _sampled_call("corr_axis_down", x, shape, axis3, taps, centre, mode, factor,
+                         offset, out, False)
+
+
+def corr_axis_up(q, shape, axis3, taps, centre, mode, factor, offset, out=None):
+    """The exact transpose of corr_axis_down with the same arguments (taps: the FORWARD
+    taps).  shape: the FULL-RESOLUTION volume of the result; q holds the sampled one."""
+    return _sampled_call("corr_axis_up", q, shape, axis3, taps, centre, mode, factor,
+                         offset, out, True)
+
+
 def corr3_wrap(x, shape, taps_z, taps_y, taps_x, out=None):
     """Separable periodic 3-D correlation in one pass (passes x, y, z); returns
     None when the fused kernel does not apply (nothing was launched)."""

@@ -32,7 +32,10 @@ nsol_pdl_iter_* in all of them:
   fused   A, A_adj are device operators of this package, recognised THROUGH
           caller-side lambdas (symbolic.trace_operator).  Where A is a
           ConvolutionOperator whose one-pass blur has the axpby epilogue, A xbar is
-          never stored: q <- sigma A xbar + q is the blur's epilogue;
+          never stored: q <- sigma A xbar + q is the blur's epilogue.  A
+          SampledConvolutionOperator with its adjoint (super-resolution: b, q and the
+          weights live on the m sampled values, x on the n of the fine grid, which
+          `shape` defaults to) runs here too, without that epilogue;
   device  callables on torch HIP tensors;
   host    NumPy-only callables: their argument is copied to the host for the call only.
 
@@ -45,7 +48,8 @@ import numpy as np
 from . import linear_operators, ops
 from .bridge import BridgedCallable
 from .device import is_device_tensor
-from .linear_operators import ConvolutionOperator, DeviceOperator
+from .linear_operators import (ConvolutionOperator, DeviceOperator,
+                               SampledConvolutionOperator)
 from .proximal_operators import (check_weights, scaled_data_on_device,
                                  weights_on_device)
 from .solver import Solver
@@ -159,10 +163,13 @@ class PrimalDualLinearSolver(Stopping, Solver):
             check_weights(weights, m)
 
         if A_norm2 is None:
-            if not isinstance(self._op, ConvolutionOperator):
+            if not isinstance(self._op, (ConvolutionOperator,
+                                         SampledConvolutionOperator)):
                 raise ValueError("A_norm2 (an upper bound of ||A||^2) is required "
-                                 "unless A is a ConvolutionOperator of this package")
-            # Young's bound, exact for non-negative taps
+                                 "unless A is a ConvolutionOperator or a "
+                                 "SampledConvolutionOperator of this package")
+            # Young's bound, exact for non-negative taps; sampling is a restriction
+            # (norm <= 1), so the bound holds for the sampled blur as well
             A_norm2 = float(np.sum(np.abs(self._op.kernel))) ** 2
         self._A_norm2 = float(A_norm2)
         if not (np.isfinite(self._A_norm2) and self._A_norm2 >= 0):
