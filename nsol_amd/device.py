@@ -47,6 +47,11 @@ def is_device_tensor(x):
     return isinstance(x, torch.Tensor) and x.is_cuda
 
 
+def device_index(x):
+    """The index of the device a device tensor lives on; None for anything else."""
+    return x.device.index if is_device_tensor(x) else None
+
+
 # Large device -> host copies go through two pinned staging buffers in chunks: the
 # cast into the caller's dtype out of the staging buffer of chunk k overlaps the
 # DMA of chunk k+1 (512^3 float32 -> float64 NumPy: 0.07-0.1 s instead of 0.19 s).

@@ -73,16 +73,23 @@ class PrimalDualSweep(object):
                  stacked_stopping=False):
         self._callables = dict(prox_f=prox_f, prox_g_conj=prox_g_conj, B=B,
                                B_conj=B_conj)
-        self._x0 = x0
         self._defaults = dict(alpha=alpha, alg_type=alg_type, L2=L2)
-        self._members = member_parameters(parameters)
-        self._iterations = int(iterations)
         # a tolerance (PrimalDualSolver's stopping rule): every member stops at an
         # iteration of its own, so the members run one after the other -- or, with
         # stacked_stopping, stacked over a map of the members still running
-        self._tolerance = checked_tolerance(tolerance)
+        self._init_state(x0, member_parameters(parameters), iterations,
+                         checked_tolerance(tolerance), checked_check_every(check_every),
+                         stacked_stopping, x_scale, dtype)
+
+    def _init_state(self, x0, members, iterations, tolerance, check_every,
+                    stacked_stopping, x_scale, dtype):
+        """What every kind of sweep keeps, whatever solver its members are."""
+        self._x0 = x0
+        self._members = members
+        self._iterations = int(iterations)
+        self._tolerance = tolerance
         self._stacked_stopping = bool(stacked_stopping)
-        self._check_every = checked_check_every(check_every)
+        self._check_every = check_every
         self._iterations_done = None
         self._x_scale = float(x_scale)
         self._dtype = dtype
@@ -141,17 +148,13 @@ class PrimalDualSweep(object):
             raise ValueError("Initial value x0 must be a 1D array")
         self._x_all = self._x_list = None
         self._observers = []
-        plan = template.plan()
-        stacked = False
         self._iterations_done = None
-        if plan is not None and self._iterations > 0 and \
-                (self._tolerance is None or self._stacked_stopping) and \
-                int(np.prod(plan["shape"])) <= ops.PD_SWEEP_MAX_VOXELS:
-            stacked = self._run_stacked(template, plan)
+        form = self._stack_form(template)
+        stacked = form is not None and self._run_stacked(template, form)
         if not stacked:
             self._run_sequential()
         torch.cuda.synchronize()
-        ops.settle_persist_runs(synchronize=False)
+        self._after_wait()
         for obs in self._observers:
             obs._finish()                 # every board, read after the one wait
         self._execution = "stacked" if stacked else "sequential"
@@ -175,30 +178,26 @@ class PrimalDualSweep(object):
             self._x_list.append(solver.get_x_device())
             self._iterations_done.append(solver.get_iterations_done())
 
-    def _run_stacked(self, template, plan):
-        """All members in one launch per iteration (stacked_run.run_stack, observation
-        and weights shared); False when the library declined (nothing has run then)."""
+    def _run_stacked(self, template, form):
+        """All members together, observation, weights and start shared; False when the
+        library declined (nothing has run then).  What differs from one kind of sweep
+        to the other is behind three methods: _stack_form (whether the template
+        stacks), _shared_operands and _advance."""
         import torch
         from .device import to_device
-        from .proximal_operators import scaled_data_on_device, weights_on_device
-        iters = self._iterations
-        kws = [dict(self._defaults, **member) for member in self._members]
-        P = len(kws)
+        iters, P = self._iterations, len(self._members)
         x0 = template._x0_device()
         n = x0.numel()
-        bt = scaled_data_on_device(plan["data"], plan["data_scale"], x0)
-        wt = weights_on_device(plan["weights"], x0) \
-            if plan["flags"] & ops.PD_DATA_WEIGHTED else None
-        G = ops.sweep_group_size(P, n, plan["dim"], x0.element_size())
+        bt, wt, G = self._shared_operands(template, form, x0)
         x_all = torch.empty(P * n, dtype=x0.dtype, device=x0.device)
         x_all.view(P, n).copy_(x0)
         # the observation of the start vector, as Solver._observe_at(0) makes it
-        observers, bounds = [], [0, iters]
+        observers, points = [], None
         if self._functions:
             refs = {}
-            for _ in kws:
+            for _ in range(P):
                 obs = self._observer()
-                bounds = obs._begin(n, iters, refs)
+                points = obs._begin(n, iters, refs)
                 observers.append(obs)
             if self._every is not None:
                 if template._x0_host is not None:
@@ -208,22 +207,57 @@ class PrimalDualSweep(object):
                     start, scale = x0, self._x_scale
                 for obs in observers:
                     obs._observe(0, start, scale)
-        stopping = self._tolerance is not None      # (stacked_stopping)
-        res = run_stack(
-            x_all, bt, wt, False, plan,
-            [(kw["alg_type"], float(kw["L2"]), kw["alpha"]) for kw in kws], iters, G,
-            ops.pd_sweep_run, bounds,
-            observe=(lambda m, it: observers[m]._observe(
-                it, x_all[m * n:(m + 1) * n], self._x_scale)) if observers else None,
-            tolerances=[self._tolerance] * P if stopping else None,
-            check_every=self._check_every, start=x0)
+        res = self._advance(
+            template, form, x_all, bt, wt, G, points,
+            (lambda m, it: observers[m]._observe(
+                it, x_all[m * n:(m + 1) * n], self._x_scale)) if observers else None, x0)
         if res is None:
             return False
         self._x_all, self._n, self._observers = x_all, n, observers
-        if stopping:
-            self._iterations_done = res.iterations_done
         self._group = G
         return True
+
+    # ---- what PrimalDualLinearSweep replaces
+    def _stack_form(self, template):
+        """What the stacked run of sweeps like `template` is built from -- here the
+        template's plan() -- or None where the members run one after the other."""
+        plan = template.plan()
+        if plan is not None and self._iterations > 0 and \
+                (self._tolerance is None or self._stacked_stopping) and \
+                int(np.prod(plan["shape"])) <= ops.PD_SWEEP_MAX_VOXELS:
+            return plan
+        return None
+
+    def _after_wait(self):
+        ops.settle_persist_runs(synchronize=False)
+
+    def _shared_operands(self, template, plan, x0):
+        """(bt, wt, members per group): the scaled observation and the weights (None:
+        unweighted) that the members share, n elements each like x0."""
+        from .proximal_operators import scaled_data_on_device, weights_on_device
+        bt = scaled_data_on_device(plan["data"], plan["data_scale"], x0)
+        wt = weights_on_device(plan["weights"], x0) \
+            if plan["flags"] & ops.PD_DATA_WEIGHTED else None
+        return bt, wt, ops.sweep_group_size(len(self._members), x0.numel(), plan["dim"],
+                                            x0.element_size())
+
+    def _advance(self, template, plan, x_all, bt, wt, group, points, observe, x0):
+        """One launch per iteration and group (stacked_run.run_stack: ops.pd_sweep_run,
+        with weights ops.pd_weighted_run, with a tolerance stacked_stopping.run_group).
+        Returns None when the library declined."""
+        iters = self._iterations
+        kws = [dict(self._defaults, **member) for member in self._members]
+        stopping = self._tolerance is not None      # (stacked_stopping)
+        res = run_stack(
+            x_all, bt, wt, False, plan,
+            [(kw["alg_type"], float(kw["L2"]), kw["alpha"]) for kw in kws], iters, group,
+            ops.pd_sweep_run, [0, iters] if points is None else points,
+            observe=observe,
+            tolerances=[self._tolerance] * len(kws) if stopping else None,
+            check_every=self._check_every, start=x0)
+        if res is not None and stopping:
+            self._iterations_done = res.iterations_done
+        return res
 
     _group = None
 

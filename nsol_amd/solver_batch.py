@@ -38,15 +38,29 @@ import time
 import numpy as np
 
 from . import ops
-from .device import is_device_tensor, torch_dtype
+from .device import device_index, is_device_tensor, torch_dtype
 from .observer import observation_points
 from .primal_dual_solver import PrimalDualSolver
 from .stacked_run import run_stack
 from .stacked_stopping import StoppedRule
 
 
-def _dev_index(v):
-    return v.device.index if is_device_tensor(v) else None
+def solver_key(solver):
+    """The solver's own part of a stack key, whatever kind of solver it is: (dtype,
+    iterations, a device-mode observer's points, ("x0", the device of x0)), or None for
+    a solver that runs on its own: no iterations, verbose, a tolerance (its own stopping
+    iteration: no stacked form), an observer that keeps iterates."""
+    iters = int(solver._iterations)
+    if iters < 1 or solver._verbose or solver._tolerance is not None:
+        return None
+    points = None
+    obs = solver._observer
+    if obs is not None:
+        if obs.get_keep_iterates():
+            return None
+        points = tuple(observation_points(iters, obs.get_every()))
+    x0_dev = None if solver._x0_host is not None else device_index(solver._x0_dev)
+    return np.dtype(solver._dtype).name, iters, points, ("x0", x0_dev)
 
 
 def member_key(solver, plan):
@@ -56,24 +70,14 @@ def member_key(solver, plan):
     ops.PD_DATA_WEIGHTED: a weighted and an unweighted solver never share a stack."""
     if plan is None:
         return None
-    iters = int(solver._iterations)
-    n = int(np.prod(plan["shape"]))
-    if iters < 1 or n > ops.PD_BATCH_MAX_VOXELS or solver._verbose:
+    own = solver_key(solver)
+    if own is None or int(np.prod(plan["shape"])) > ops.PD_BATCH_MAX_VOXELS:
         return None
-    if solver._tolerance is not None:
-        return None         # its own stopping iteration: no stacked form (DESIGN 8)
-    points = None
-    obs = solver._observer
-    if obs is not None:
-        if obs.get_keep_iterates():
-            return None
-        points = tuple(observation_points(iters, obs.get_every()))
-    x0_dev = None if solver._x0_host is not None else _dev_index(solver._x0_dev)
     return (tuple(int(s) for s in plan["shape"]),
             tuple(float(v) for v in plan["w"]), int(plan["dim"]),
-            int(plan["flags"]), float(plan["gamma"]), np.dtype(solver._dtype).name,
-            iters, points, ("data", _dev_index(plan["data"])), ("x0", x0_dev),
-            ("weights", _dev_index(plan.get("weights"))))
+            int(plan["flags"]), float(plan["gamma"])) + own[:3] + \
+        (("data", device_index(plan["data"])), own[3],
+         ("weights", device_index(plan.get("weights"))))
 
 
 class _WithoutTolerance(object):
@@ -111,16 +115,31 @@ def plan_stacks(keys):
 
 
 class PrimalDualBatch(object):
+    """The stacked front end of a list of solvers, and its form for PrimalDualSolver.
+    __init__, run() and the upload of a stack's operands are the same for every kind
+    of solver; a subclass (linear_stack.PrimalDualLinearBatch) replaces what is not:
+
+        _solver_type        the solvers the batch takes
+        _stops_members      whether stacked_stopping=True is on offer
+        _stacks_to_try()    [(member indices, stopping), ...]
+        _after_wait()       what follows the synchronisation behind a stack
+        _operands(idx)      where a stack's observations and weights come from
+        _advance(...)       the group size and the runner"""
+
+    _solver_type = PrimalDualSolver
+    _stops_members = True
 
     def __init__(self, solvers, stacked_stopping=False):
         solvers = list(solvers)
         if not solvers:
             raise ValueError("a batch needs at least one solver")
+        if stacked_stopping and not self._stops_members:
+            raise ValueError("%s has no stacked stopping" % type(self).__name__)
         seen = set()
         for s in solvers:
-            if not isinstance(s, PrimalDualSolver):
-                raise ValueError("a batch takes PrimalDualSolver objects, not %s" %
-                                 type(s).__name__)
+            if not isinstance(s, self._solver_type):
+                raise ValueError("a batch takes %s objects, not %s" %
+                                 (self._solver_type.__name__, type(s).__name__))
             if id(s) in seen:
                 raise ValueError("the same solver object is in the batch twice")
             seen.add(id(s))
@@ -158,23 +177,17 @@ class PrimalDualBatch(object):
         for s in solvers:
             if s._x0_ndim != 1:
                 raise ValueError("Initial value x0 must be a 1D array")
-        plans = [s.plan() for s in solvers]
-        keys = [member_key(s, p) for s, p in zip(solvers, plans)]
         execution = ["sequential"] * len(solvers)
         self._stacks, self._group = [], None
         self._staging = []
-        stacks = [(idx, False) for idx in plan_stacks(keys)]
-        if self._stacked_stopping:
-            stacks += [(idx, True) for idx in plan_stacks(
-                [stopping_member_key(s, p) for s, p in zip(solvers, plans)])]
-        for idx, stopping in stacks:
+        for idx, stopping in self._stacks_to_try():
             t1 = time.time()
-            x_all = self._run_stack(idx, plans, stopping)
-            if x_all is None:
+            ran = self._run_stack(idx, stopping)
+            if ran is None:
                 continue                       # declined: nothing was written
-            stopped = self._stopped
+            x_all, stopped = ran
             torch.cuda.synchronize()
-            ops.settle_persist_runs(synchronize=False)
+            self._after_wait()
             took = datetime.timedelta(seconds=time.time() - t1)
             n = x_all.numel() // len(idx)
             for m, i in enumerate(idx):
@@ -200,7 +213,21 @@ class PrimalDualBatch(object):
         self._execution = execution
         self._computational_time = datetime.timedelta(seconds=time.time() - t0)
 
-    _stopped = None     # GroupResult of the last stack that ran with stopping=True
+    def _stacks_to_try(self):
+        """[(member indices, stopping), ...] of this run: the solvers that agree in
+        member_key(), and with stacked_stopping those that agree in
+        stopping_member_key() and stop one by one."""
+        solvers = self._solvers
+        self._plans = plans = [s.plan() for s in solvers]
+        stacks = [(idx, False) for idx in plan_stacks(
+            [member_key(s, p) for s, p in zip(solvers, plans)])]
+        if self._stacked_stopping:
+            stacks += [(idx, True) for idx in plan_stacks(
+                [stopping_member_key(s, p) for s, p in zip(solvers, plans)])]
+        return stacks
+
+    def _after_wait(self):
+        ops.settle_persist_runs(synchronize=False)
 
     def _upload_rows(self, rows, dtype):
         """One page-locked (P, n) array of `dtype`, filled row by row (NumPy casts
@@ -220,62 +247,69 @@ class PrimalDualBatch(object):
         from .device import device
         return torch.from_numpy(np.asarray(values, dtype=np.float64)).to(device())
 
-    def _run_stack(self, idx, plans, stopping=False):
-        """The members `idx` in one launch per iteration and group.  Returns their
-        stacked iterate (P * n, solver units), or None when the library declined
-        on its first launch (nothing has been written to any solver then).
-        stopping: the members have tolerances and stop one by one
-        (stacked_stopping.run_group); self._stopped then holds what each did."""
+    def _upload_stack(self, solvers, data, weights, device_weights):
+        """(bt, x_all, wt) of the stack `solvers`: the scaled observations, the start
+        vectors and the weights (None: unweighted), P * n elements each, member-major,
+        in the working dtype.
+
+        data: (observation, its scale) per member; weights: every member's own, or
+        None; device_weights(w, like): a member's device-resident weights as the flat
+        tensor that is copied into its row, `like` having the working dtype.  Where
+        the first member's input lives decides the path (the members agree in it,
+        member_key): host arrays travel together, one page-locked (P, n) array each
+        (_upload_rows, kept in self._staging until run() has synchronised), and are
+        scaled by every member's own scale in one launch (ops.scale_rows);
+        device-resident inputs are converted and copied member by member."""
         import torch
         from .device import device
         from .proximal_operators import scaled_data_on_device
-        solvers = [self._solvers[i] for i in idx]
-        plan = plans[idx[0]]
-        P, iters, dim = len(idx), int(solvers[0]._iterations), plan["dim"]
-        n = int(np.prod(plan["shape"]))
-        td = torch_dtype(solvers[0]._dtype)
-        dev = device()
-        # ---- the scaled observations: float64 / x_scale, rounded once
-        datas = [plans[i]["data"] for i in idx]
-        if is_device_tensor(datas[0]):
-            bt = torch.empty(P * n, dtype=td, device=dev)
-            like = bt[:1]
-            for m, i in enumerate(idx):
-                bt[m * n:(m + 1) * n].copy_(scaled_data_on_device(
-                    datas[m], plans[i]["data_scale"], like))
+        s0 = solvers[0]
+        P, td, dev = len(solvers), torch_dtype(s0._dtype), device()
+        n = int(s0._x0_host.size if s0._x0_host is not None else s0._x0_dev.numel())
+
+        def member_by_member(parts):
+            out = torch.empty(P * n, dtype=td, device=dev)
+            for m, part in enumerate(parts(out[:1])):
+                out[m * n:(m + 1) * n].copy_(part)
+            return out
+
+        # ---- the scaled observations: float64 / scale, rounded once
+        if is_device_tensor(data[0][0]):
+            bt = member_by_member(lambda like: (scaled_data_on_device(d, scale, like)
+                                                for d, scale in data))
         else:
-            raw = self._upload_rows(datas, np.float64)
-            bt = ops.scale_rows(
-                raw, self._scales([plans[i]["data_scale"] for i in idx]), P,
-                divide=True, dtype=td).view(-1)
+            raw = self._upload_rows([d for d, _ in data], np.float64)
+            bt = ops.scale_rows(raw, self._scales([scale for _, scale in data]), P,
+                                divide=True, dtype=td).view(-1)
         # ---- the start vectors: rounded to the working dtype, then / x_scale
-        if solvers[0]._x0_host is None:
-            x_all = torch.empty(P * n, dtype=td, device=dev)
-            for m, s in enumerate(solvers):
-                x_all[m * n:(m + 1) * n].copy_(s._x0_device())
+        if s0._x0_host is None:
+            x_all = member_by_member(lambda like: (s._x0_device() for s in solvers))
         else:
-            raw = self._upload_rows([s._x0_host for s in solvers], solvers[0]._dtype)
+            raw = self._upload_rows([s._x0_host for s in solvers], s0._dtype)
             x_all = ops.scale_rows(raw, self._scales([s._x_scale for s in solvers]),
                                    P, divide=True).view(-1)
-        # ---- a weighted data term: every member's own weights, checked by plan(),
-        # converted to the working dtype and uploaded once like the observations
+        # ---- every member's own weights, converted to the working dtype
         wt = None
-        if plan["flags"] & ops.PD_DATA_WEIGHTED:
-            wts = [plans[i]["weights"] for i in idx]
-            if is_device_tensor(wts[0]):
-                wt = torch.empty(P * n, dtype=td, device=dev)
-                for m, v in enumerate(wts):
-                    wt[m * n:(m + 1) * n].copy_(v.reshape(-1))
+        if weights is not None:
+            if is_device_tensor(weights[0]):
+                wt = member_by_member(lambda like: (device_weights(w, like)
+                                                    for w in weights))
             else:
-                wt = self._upload_rows(wts, solvers[0]._dtype).view(-1)
-            G = ops.weighted_batch_group_size(P, n, dim, x_all.element_size())
-        else:
-            G = ops.batch_group_size(P, n, dim, x_all.element_size())
-        # ---- device-mode observers share their points (member_key): the run is
-        # enqueued in the stretches between them
+                wt = self._upload_rows(weights, s0._dtype).view(-1)
+        return bt, x_all, wt
+
+    def _run_stack(self, idx, stopping=False):
+        """The members `idx` together.  Returns (their stacked iterate (P * n, solver
+        units), the runner's result), or None when the library declined on its first
+        launch (nothing has been written to any solver then).  stopping: the members
+        have tolerances and stop one by one; the result then holds what each did."""
+        solvers = [self._solvers[i] for i in idx]
+        iters = int(solvers[0]._iterations)
+        bt, x_all, wt = self._upload_stack(solvers, *self._operands(idx))
+        n = x_all.numel() // len(idx)
+        # ---- device-mode observers share their points (member_key)
         obs = solvers[0]._observer
-        bounds = [0, iters] if obs is None else \
-            observation_points(iters, obs.get_every())
+        points = None if obs is None else observation_points(iters, obs.get_every())
 
         def taken():
             # the library has taken the stack: the observation of the start
@@ -284,20 +318,42 @@ class PrimalDualBatch(object):
                 s._x = None
                 s._observe_start(iters)
 
+        got = self._advance(
+            idx, x_all, bt, wt, points,
+            None if obs is None else (lambda m, it: solvers[m]._observe_at(
+                it, x_all[m * n:(m + 1) * n])),
+            None if obs is None else taken, stopping)
+        if got is None:
+            return None
+        self._group = max(self._group or 0, got[0])
+        return x_all, got[1]
+
+    def _operands(self, idx):
+        """(data, weights, device_weights) of the stack `idx` for _upload_stack: what
+        the members' plans hold.  plan() has checked the weights; a device-resident
+        member's are converted by the copy into its row."""
+        plans = [self._plans[i] for i in idx]
+        weighted = plans[0]["flags"] & ops.PD_DATA_WEIGHTED
+        return [(p["data"], p["data_scale"]) for p in plans], \
+            [p["weights"] for p in plans] if weighted else None, \
+            lambda w, like: w.reshape(-1)
+
+    def _advance(self, idx, x_all, bt, wt, points, observe, taken, stopping):
+        """Run the stack `idx` in one launch per iteration and group
+        (stacked_run.run_stack, in the stretches between the observers' points;
+        stopping: stacked_stopping.run_group).  Returns (members per group, the
+        runner's result), or None when the library declined."""
+        solvers, plan = [self._solvers[i] for i in idx], self._plans[idx[0]]
+        P, iters = len(solvers), int(solvers[0]._iterations)
+        size = ops.batch_group_size if wt is None else ops.weighted_batch_group_size
+        G = size(P, x_all.numel() // P, plan["dim"], x_all.element_size())
         res = run_stack(
             x_all, bt, wt, True, plan, [(s._alg_type, s._L2, s._alpha) for s in solvers],
-            iters, G, ops.pd_batch_run, bounds,
-            observe=None if obs is None else (lambda m, it: solvers[m]._observe_at(
-                it, x_all[m * n:(m + 1) * n])),
-            taken=None if obs is None else taken,
+            iters, G, ops.pd_batch_run, [0, iters] if points is None else points,
+            observe=observe, taken=taken,
             tolerances=[s._tolerance for s in solvers] if stopping else None,
             check_every=solvers[0]._check_every)
-        if res is None:
-            return None
-        if stopping:
-            self._stopped = res
-        self._group = max(self._group or 0, G)
-        return x_all
+        return None if res is None else (G, res)
 
     # ------------------------------------------------------------------
     def get_x_device(self, i):
