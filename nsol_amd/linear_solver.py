@@ -93,8 +93,17 @@ class LinearSolver(Solver):
         self._data_loss = data_loss
 
     # ---- costs at the current iterate (linear_solver.py:242-312)
+    _x_in_callers_units = False
+
     def _current(self):
-        return self._x if self._x is not None else self._x0_device()
+        """The iterate in the solver's own (scaled) units, which b and b_reg are in."""
+        if self._x is None:
+            return self._x0_device()
+        if self._x_in_callers_units:
+            # (a solution assembled as x * x_scale: divided for the one evaluation, not
+            # kept -- the solver holds no second copy of its iterate)
+            return ops.scale(self._x, self._x_scale, divide=True)
+        return self._x
 
     def get_total_cost(self):
         return self.get_cost_data_term() + \

@@ -683,7 +683,8 @@ def _operators_in_float64(A, A_adj, x_like):
 def lsmr_fused(A, A_adj, b_top, b_bot, bmode, shape, w, sa, x_like, maxiter,
                atol=0.0, btol=0.0, conlim=1e8, A_axpby=None, normb2=None, top_norm2=None,
                own_b=True, atb=None, x_bounds=None, b_bot_scale=1.0,
-               allow_normal=True, g0=None, b_bot_fill=None, out_scale=None):
+               allow_normal=True, g0=None, b_bot_fill=None, out_scale=None,
+               own_b_bot=True):
     """Same algorithm for the augmented system [A; sa*B] with B in {none, grad,
     identity}, on the fused kernels of nsol_lsmr.hip.  The Golub-Kahan vectors
     are held unnormalised (ut = su*u, vt = sv*v); b_top / b_bot are consumed.
@@ -703,7 +704,10 @@ def lsmr_fused(A, A_adj, b_top, b_bot, bmode, shape, w, sa, x_like, maxiter,
     cannot stay with the normal equations and needs the block itself.  out_scale =
     [s, False], s > 0: the caller wants s * x; where x is assembled from stored vectors the
     factor goes into their coefficients (and the bounds) and out_scale[1] becomes True --
-    otherwise x comes back as it is and the caller multiplies."""
+    otherwise x comes back as it is and the caller multiplies.  own_b_bot: as own_b for
+    the lower block -- False: b_bot is somebody's to keep (the caller's array, a solver's
+    b_reg), and the bidiagonalisation, whose u update overwrites the block on every step,
+    works in a copy (the scaled one where b_bot_scale != 1, a clone otherwise)."""
     import torch
     wide = None
     if bmode == ops.B_NONE and PROMOTE_WEAK_REGULARISERS and x_like.element_size() == 4 \
@@ -752,7 +756,9 @@ def lsmr_fused(A, A_adj, b_top, b_bot, bmode, shape, w, sa, x_like, maxiter,
     if not own_b:                 # (the caller's b: consumed below, so work in a copy)
         b_top = b_top.clone()
     if b_bot is not None and b_bot_scale != 1.0:
-        b_bot = ops.scale(b_bot, b_bot_scale)
+        b_bot = ops.scale(b_bot, b_bot_scale)           # (an array of its own)
+    elif b_bot is not None and not own_b_bot:
+        b_bot = b_bot.clone()
     ut, ub = b_top, b_bot
     if normb2 is not None:           # ||[b_top; b_bot]||^2 known to the caller
         normb = math.sqrt(normb2() if callable(normb2) else normb2)

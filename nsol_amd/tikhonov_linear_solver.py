@@ -272,6 +272,7 @@ class TikhonovLinearSolver(LinearSolver):
                                  top_norm2=lambda: _norm2_of_data(b_top),
                                  x_bounds=self._bounds,
                                  b_bot_scale=self._lower_scale,
+                                 own_b_bot=self._lower_owned,
                                  g0=None if start is None else (start["g"], start["gg"]),
                                  b_bot_fill=None if start is None else start["fill"])
             self._lsmr_stop = (istop, itn)     # (SciPy's istop, iterations taken)
@@ -324,6 +325,7 @@ class TikhonovLinearSolver(LinearSolver):
             return None
         flat_ok = ops.flat_geometry(n) is not None
         self._lower_scale = 1.0
+        self._lower_owned = True          # (no lower block yet)
         if not (self._alpha > EPS):
             if not flat_ok:
                 return None
@@ -353,9 +355,13 @@ class TikhonovLinearSolver(LinearSolver):
             return None
         sa = float(np.sqrt(self._alpha))
         self._lower_scale = 1.0
+        # (who owns the lower block handed over: only one that is given away may be
+        # overwritten by the bidiagonalisation, whatever its factor is)
+        self._lower_owned = False
         lazy = self._b_reg_lazy
         if self._prescaled_b_reg is None and lazy is not None and lazy[0].numel() == rows:
-            # (b_reg as the caller gave it; 1 / x_scale rides with sqrt(alpha))
+            # (b_reg as the caller gave it -- the caller's own array where dtype and
+            # layout fit; 1 / x_scale rides with sqrt(alpha))
             lower = lazy[0]
             self._lower_scale = sa / lazy[1]
         elif self._prescaled_b_reg is not None and \
@@ -363,11 +369,13 @@ class TikhonovLinearSolver(LinearSolver):
             # already sqrt(alpha) * b_reg; consumed by LSMR (it becomes u's lower
             # block), which is fine: the caller rewrites it before the next solve
             lower = self._dev(self._b_reg)
+            self._lower_owned = True
         elif is_device_tensor(self._b_reg) or np.ndim(self._b_reg) > 0:
             if self._prescaled_b_reg is not None:
                 return None
             # (handed over as it is with its factor: only the bidiagonalisation needs
-            # sqrt(alpha) * b_reg as an array of its own)
+            # sqrt(alpha) * b_reg as an array of its own -- this one stays the solver's,
+            # for get_b_reg(), the regularisation cost and the next run())
             lower = self._dev(self._b_reg)
             self._lower_scale = sa
             if lower.numel() != rows:
@@ -378,6 +386,7 @@ class TikhonovLinearSolver(LinearSolver):
             import torch
             lower = torch.full((rows,), sa * float(self._b_reg),
                                dtype=x0.dtype, device=x0.device)
+            self._lower_owned = True
         return (A, A_adj, b, lower, bmode, shape, w, sa)
 
     # ------------------------------------------------------------------
