@@ -525,6 +525,38 @@ int nsol_pd_fusedk_tail2(int elem_size, int64_t nz, int64_t ny, int64_t nx);
  * NSOL_EINVAL while the shape is unknown or still exploring. */
 int nsol_pd_fusedk_plan(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
                         int *waves, int *ntx, int64_t *zchunk);
+/* The SHIFTED depth-3 form (k_pd_shift3).  Once p^{n+1} exists nothing reads xbar^n, so
+ * a run cut after the dual step carries (x, p) only: a launch that runs P D P D P D reads
+ * x, bt, p[3] and writes x, p[3] -- 9 words per voxel for three iterations where
+ * k_pd_fusedk moves 11 -- with the same arithmetic per voxel in the same order.
+ * nsol_pd_run_* sends a long run of N iterations through
+ *     (N - 1) mod 3 leading iterations on the usual path,
+ *     one nsol_pd_dual_step_*, m = (N - 1) / 3 shifted launches, one nsol_pd_primal_step_*
+ * and returns the usual state, bit-identical.  The form takes 3-D volumes with contiguous
+ * rows of whole 16-byte vectors, component-wise TV / Huber, unweighted l2 / l1; everything
+ * else stays on the unshifted path.  Knobs (nsol_hip_set_param_pdk): "pdk_shift" -1 = runs
+ * of at least "pdk_shift_min_iters" iterations on volumes the online tuner handles
+ * (default), 0 = never (the unshifted path, unchanged), 1 = wherever the form applies,
+ * from 4 iterations on (tests, A/B runs).  Shifted launches count into
+ * nsol_pd_fusedk_launches(3); nsol_pd_shift_launches() counts them alone.  For depth 3 of
+ * a shape whose long runs take the block, nsol_pd_fusedk_tuned / _plan answer for the
+ * shifted form's plan once there is one (a process that has made short runs only gets the
+ * unshifted plan's answer).  The unshifted plan of such a shape -- its short runs take it
+ * -- explores a short candidate list on launches that long runs hand over to it once the
+ * shifted plan has issued its samples, and _tuned reports 1 when both have settled;
+ * nsol_pd_fusedk_plan_form reads either plan (form 0 unshifted, 1 shifted).
+ * nsol_pd_shift_min_iters: the shortest run of this problem that takes the block under
+ * the knobs as they stand, 0 if none does (flags, shape, pitch, a footprint that fits) --
+ * what nsol_pd_run_* itself asks, pointer alignment aside.
+ * nsol_pd_run_parts: how a run of `iterations` is cut for the threshold `min_iters`
+ * (0: no block): *lead leading iterations and *launches shifted launches -- the block is
+ * 3 * *launches + 1 iterations; returns 1 if the block is taken.  Pure host functions. */
+int nsol_pd_shift_launches(void);
+int nsol_pd_shift_min_iters(int elem_size, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                            int flags, int64_t pitch);
+int nsol_pd_fusedk_plan_form(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
+                             int form, int *waves, int *ntx, int64_t *zchunk);
+int nsol_pd_run_parts(int iterations, int min_iters, int *lead, int *launches);
 /* The whole loop of primal_dual_solver.py:232-261 in ONE launch for cache-
  * resident volumes (BASELINE configs 1-2; at most one tile of <= 1024 lanes x one
  * 16-byte vector per CU, i.e. up to ~1 Mi float voxels): every workgroup keeps its

@@ -235,14 +235,64 @@ int run_impl(T *xbar0, T *xbar1, T *x, T *x_alt, const T *bt, T *p0, T *p1,
   // the isotropic projection has the one-iteration forms only (the multi-iteration
   // entries decline it): one launch of k_pd_fused_iso per iteration
   const bool iso = (flags & NSOL_PD_REG_ISOTROPIC) != 0;
+  // A long run ends in a block of shifted launches (k_pd_shift3, nsol_pdk.hip): a
+  // stand-alone dual step, m launches of P D P D P D on (x, p) alone, a stand-alone
+  // primal step -- 3 m + 1 iterations; the (N - 1) mod 3 iterations before it take the
+  // usual rungs (at most two: no depth-3 launch, unless whole triples are handed to the
+  // unshifted plan's exploration below)
+  int lead = iterations, m_shift = 0;
+  if (!iso && xoth && !g_tune.force_two_pass)
+    nsol_pd_run_parts(iterations,
+                      pd_shift3_min_iters<T>(xcur, xoth, bt, p0, p1, ndim, nz, ny, nx, flags,
+                                             pitched ? pitch : 0, iterations),
+                      &lead, &m_shift);
+  bool ask = false;      // may the unshifted plan still want launches during this run
+  if (m_shift > 1) {
+    // while the shape's unshifted depth-3 plan is still owed samples (the plan its short
+    // runs take), that many leading launches of the block go to it: three iterations
+    // each, same bits
+    int d = pd_shift3_donation<T>(nz, ny, nx);
+    ask = d >= 0;
+    if (d < 0) d = 0;
+    if (d > m_shift - 1) d = m_shift - 1;
+    lead += 3 * d;
+    m_shift -= d;
+  }
   int n = 0;
   while (n < iterations) {
+    if (n == lead && m_shift > 0) {
+      const T *pin = (n == 0 && p_is_zero) ? nullptr : pp[slot];
+      int rc = dual_step_impl<T>(xb[slot], pin, pp[slot ^ 1], ndim, nz, ny, nx, wx, wy, wz,
+                                 sig[n], huber ? 1.0 + sig[n] * gamma_huber : 1.0, stream);
+      if (rc) return rc;
+      slot ^= 1;                       // p^{n+1} is in pp[slot]; xb[slot] is free
+      for (int i = 0; i < m_shift; ++i, n += 3) {
+        double h4[4], tl3[3];
+        for (int j = 0; j < 4; ++j) h4[j] = huber ? 1.0 + sig[n + j] * gamma_huber : 1.0;
+        for (int j = 0; j < 3; ++j) tl3[j] = tau[n + j] * lambda;
+        rc = pd_shift3_iter<T>(xcur, xoth, bt, pp[slot], pp[slot ^ 1], ndim, nz, ny, nx, wx,
+                               wy, wz, sig + n, h4, tau + n, tl3, theta + n, flags, stream);
+        if (rc) return rc == -2 ? NSOL_EINVAL : rc;   // (pd_shift3_min_iters said it applies)
+        slot ^= 1;
+        T *t = xcur; xcur = xoth; xoth = t;
+        // the shifted plan settled on this launch and the unshifted plan still explores:
+        // the block ends here, the rest of the run (whole triples) goes to that plan
+        if (ask && i + 2 < m_shift && pd_shift3_donation<T>(nz, ny, nx) > 0) m_shift = i + 1;
+      }
+      rc = primal_step_impl<T>(pp[slot], xcur, xb[slot], bt, ndim, nz, ny, nx, wx, wy, wz,
+                               tau[n], tau[n] * lambda, theta[n], flags, stream);
+      if (rc) return rc;
+      n += 1;
+      m_shift = 0;                     // one block per run: what is left takes the rungs
+      continue;
+    }
     const T *pin = (n == 0 && p_is_zero) ? nullptr : pp[slot];
-    if (!iso && xoth && n + 1 < iterations && !g_tune.force_two_pass) {
+    const int until = m_shift > 0 ? lead : iterations;   // end of this stretch of rungs
+    if (!iso && xoth && n + 1 < until && !g_tune.force_two_pass) {
       // deepest temporal blocking first: 3 iterations per pass (tiled
       // footprints), then 2 (tiled or full-row footprints), then 1
       double h3[3], tl3[3];
-      const int left = iterations - n < 3 ? iterations - n : 3;
+      const int left = until - n < 3 ? until - n : 3;
       for (int i = 0; i < left; ++i) {
         h3[i] = huber ? 1.0 + sig[n + i] * gamma_huber : 1.0;
         tl3[i] = tau[n + i] * lambda;

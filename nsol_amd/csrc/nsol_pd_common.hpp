@@ -169,6 +169,24 @@ int pd_fusedk_iter(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const
                    const double *hden, const double *tau, const double *tl,
                    const double *theta, int flags, void *stream, int64_t pitch);
 
+// The shifted depth-3 form (k_pd_shift3, nsol_pdk.hip): a launch runs P D P D P D on
+// (x, p) alone -- no xbar crosses it.  pd_shift3_min_iters: the shortest run of this
+// problem that takes a block of such launches (0: none does, or `iterations` is below the
+// threshold of any shape); pd_shift3_iter: one launch
+// (sigma, hden: iterations n .. n+3, the first unused; tau, tl, theta: n .. n+2).
+template <typename T>
+int pd_shift3_min_iters(const T *x, const T *x_alt, const T *bt, const T *p0, const T *p1,
+                        int ndim, int64_t nz, int64_t ny, int64_t nx, int flags,
+                        int64_t pitch, int iterations);
+// launches a long run of this shape gives up for the unshifted depth-3 plan's exploration
+template <typename T>
+int pd_shift3_donation(int64_t nz, int64_t ny, int64_t nx);
+template <typename T>
+int pd_shift3_iter(const T *x_in, T *x_out, const T *bt, const T *p_in, T *p_out, int ndim,
+                   int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+                   const double *sigma, const double *hden, const double *tau,
+                   const double *tl, const double *theta, int flags, void *stream);
+
 template <bool L1, typename T>
 __device__ __forceinline__ T prox_data_s(T u, T bt, T tl, T one_plus_tl) {
   if constexpr (L1) return prox_ell1(u, bt, tl);

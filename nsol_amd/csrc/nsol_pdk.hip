@@ -87,6 +87,8 @@ struct StageScalars {
 
 // launches of k_pd_fusedk so far, [0]: K = 2, [1]: K = 3 (tests ask which kernel ran)
 std::atomic<int> g_launches[2];
+// ... and those of them that were launches of the shifted form (k_pd_shift3)
+std::atomic<int> g_shift_launches;
 
 struct Tiling {
   int lxb;    // lanes per footprint row
@@ -896,6 +898,416 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_fusedk(
     step(std::false_type{}, s, LA, LA, CA, CA);
 }
 
+// ---------------------------------------------------------------------------
+// The SHIFTED depth-3 form: a run cut after the dual step instead of after the
+// primal step.  Once p^{n+1} exists nothing reads xbar^n any more (the primal update
+// reads x^n, bt and p^{n+1}; xbar^{n+1} is formed from x^{n+1} and x^n), so the state
+// that crosses such a cut is (x^n, p^{n+1}): four words instead of five.  A launch runs
+//   P_1 D_2 P_2 D_3 P_3 D_4
+// -- the same six half-steps as k_pd_fusedk's D P D P D P, the same arithmetic per
+// voxel in the same order -- reads x, bt, p[3] and writes x, p[3]: 9 words per voxel
+// instead of 11.  nsol_pd.hip's run loop puts a stand-alone dual step in front of a
+// block of such launches and a stand-alone primal step behind it.
+//
+// Pipeline at step s (one barrier per step, LDS arrays double buffered by step parity):
+//   stage 1   primal only, plane s: K^T of the LOADED p^(1) (own vectors, p_y of the row
+//             above and the one p_x left of a wave / row start from L1/L2, p_z of the
+//             plane before carried from the previous step's load);
+//   F_2, F_3  as in k_pd_fusedk, planes s-1, s-2 (stage 3 keeps its per-lane masks: its
+//             xbar IS read here, by stage 4); x^(3) is stored at plane s-2;
+//   IP_2      plane s: the recomputed p^(2) of the left / upper voxel starts from the
+//             same loaded p^(1) halo stage 1 used, so only p^(2) travels through the LDS;
+//   IP_3      plane s-1: p_x^(3), p_y^(3) are carried a step instead of being stored;
+//   IP_4      plane s-2: p_x^(4), p_y^(4) from xbar^(3) of the right neighbour and the
+//             row below (a third s_xb set), stored there;
+//   F_4       plane s-3: p_z^(4) from xbar^(3) of that plane (carried) and of plane s-2.
+// Dependency cone: the last dual step needs xbar^(3) one row further down, one voxel
+// further right and one plane further up than a launch of k_pd_fusedk does, so a
+// footprint keeps rows [2, rows-4] (2 above, 3 below: rows - 5 valid), the x halo is
+// HX >= K voxels wide (3 needed on the right) and a z-chunk runs one step longer.
+template <typename T>
+struct ShiftScalars {
+  T sigma[4], hden[4];                     // [k-1]: the dual step of stage k (k = 2..4)
+  T tau[3], tl[3], optl[3], theta[3];      // [k-1]: the primal step of stage k (k = 1..3)
+};
+
+template <typename T, int V>
+struct ShiftLoads {          // registers one prefetched plane lands in
+  T xv[V], btn[V], pxo[V], pyo[V], pzo[V], pyup[V];
+  T pxleft;
+};
+
+template <typename T, int VEC, int NW, int WPE, bool HUBER, bool L1, bool PF2, bool UNIT>
+__global__ __launch_bounds__(NW * 64, WPE) void k_pd_shift3(
+    const T *__restrict__ x_in, T *__restrict__ x_out, const T *__restrict__ bt,
+    const T *__restrict__ p_in, T *__restrict__ p_out, Geom<T> G, ShiftScalars<T> S,
+    Tiling Q, int zchunk, int slab) {
+  constexpr int K = 3;
+  constexpr int NT = NW * 64;
+  constexpr int HA = 2, HB = 3;                      // rows lost above / below
+  constexpr int HX = ((K + VEC - 1) / VEC) * VEC;
+  static_assert(HX >= K, "the x halo must hold the three voxels the right-hand cone needs");
+  constexpr int LN = LdsShape<NT, K>::N;
+  __shared__ __attribute__((aligned(16))) T s_xb[2][K][LN * VEC];   // xbar^(1..3)
+  __shared__ __attribute__((aligned(16))) T s_py[2][LN * VEC];      // p_y^(2)
+  __shared__ T s_px[2][LN];                                         // last p_x^(2) of a vector
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int ntiles = Q.ntx * Q.nty;
+  int tile, zc;
+  if (slab > 0) {
+    const int xcd = blockIdx.x & 7;
+    const int j = blockIdx.x >> 3;
+    tile = xcd * slab + j % slab;
+    zc = j / slab;
+    if (tile >= ntiles) return;
+  } else {
+    tile = blockIdx.x % ntiles;
+    zc = blockIdx.x / ntiles;
+  }
+  const int tx = tile % Q.ntx;
+  const int ty = tile / Q.ntx;
+
+  // ---- geometry of this lane (lane mappings as in k_pd_fusedk)
+  const int lxb = Q.lxb;
+  constexpr int HL = HX / VEC;
+  int row, lx;
+  bool lone = false;
+  if (Q.split) {
+    const int inner = lxb - 2 * HL;
+    const int main = Q.rows * inner;
+    if (tid < main) {
+      row = tid / inner;
+      lx = HL + (tid - row * inner);
+      lone = (lx == HL) || (lx == HL + inner - 1);
+    } else {
+      const int h = tid - main;
+      row = h / (2 * HL);
+      const int side = h - row * (2 * HL);
+      lx = side < HL ? side : inner + side;
+      lone = true;
+    }
+  } else {
+    row = tid / lxb;
+    lx = tid - row * lxb;
+  }
+  const bool active = row < Q.rows;
+  const bool single_x = (Q.xv == 0);
+  const int64_t xv_lo = single_x ? 0 : (int64_t)tx * Q.xv;
+  const int64_t xv_hi = single_x ? G.nx : xv_lo + Q.xv;
+  const int64_t x0 = (single_x ? 0 : xv_lo - HX) + (int64_t)lx * VEC;
+  const int64_t tyv = Q.rows - (HA + HB);
+  const int64_t yv_lo = (int64_t)ty * tyv;
+  const int64_t yv_hi = yv_lo + tyv;
+  const int64_t y = yv_lo - HA + row;
+  const bool rin = active && x0 >= 0 && x0 < G.nx && y >= 0 && y < G.ny;
+  const bool rvalid = rin && x0 >= xv_lo && x0 < xv_hi && y >= yv_lo && y < yv_hi;
+
+  // step sizes masked to zero outside the volume, for every stage whose xbar is read
+  // by a later one -- all three here
+  T sig_m[K], tau_m[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    sig_m[k] = rin ? S.sigma[k] : T(0);
+    tau_m[k] = rin ? S.tau[k] : T(0);
+  }
+
+  const int nzi = (int)G.nz;
+  const int zbeg = zc * zchunk;
+  int zend = zbeg + zchunk;
+  if (zend > nzi) zend = nzi;
+  const int s_first = zbeg > HA ? zbeg - HA : 0;
+  const int s_last = zend + K - 1;
+  const int s_hi = s_last < nzi - 1 ? s_last : nzi - 1;   // last step with a stage 1
+
+  // ---- buffer resources over the planes [pz0, pe) this workgroup touches
+  const int pz0 = s_first > 0 ? s_first - 1 : 0;
+  int pe = s_last + 1;
+  if (pe > nzi) pe = nzi;
+  const uint32_t szb = (uint32_t)(G.sz * (int64_t)sizeof(T));
+  const uint32_t syb = (uint32_t)(G.sy * (int64_t)sizeof(T));
+  const uint32_t span = (uint32_t)(pe - pz0) * szb;       // < 2^30 (host-checked)
+  const int64_t boff = (int64_t)pz0 * G.sz;
+  const rsrc_t r_x = make_rsrc(x_in + boff, span);
+  const rsrc_t r_bt = make_rsrc(bt + boff, span);
+  const rsrc_t r_px = make_rsrc(p_in + boff, span);
+  const rsrc_t r_py = make_rsrc(p_in + G.n + boff, span);
+  const rsrc_t r_pz = make_rsrc(p_in + 2 * G.n + boff, span);
+  const rsrc_t w_x = make_rsrc(x_out + boff, span);
+  const rsrc_t w_px = make_rsrc(p_out + boff, span);
+  const rsrc_t w_py = make_rsrc(p_out + G.n + boff, span);
+  const rsrc_t w_pz = make_rsrc(p_out + 2 * G.n + boff, span);
+
+  const bool row_beg = (lx == 0) || lane == 0 || lone;
+  const uint32_t o0 = (uint32_t)((y * G.sy + x0) * (int64_t)sizeof(T));
+  const uint32_t v_own = rin ? o0 : kInvalid;
+  const uint32_t v_up = (rin && y > 0) ? o0 - syb : kInvalid;
+  const uint32_t v_left = (rin && row_beg && x0 > 0) ? o0 - (uint32_t)sizeof(T) : kInvalid;
+  const uint32_t v_st = rvalid ? o0 : kInvalid;
+  const bool n_r = active && lx < lxb - 1;
+  const bool v_l = rin && lx > 0 && x0 > 0;      // the left / upper voxel is in the volume
+  const bool v_u = rin && row > 0 && y > 0;
+  const int slot = active ? (row + 1) * lxb + lx : tid + lxb;
+  const int li = slot * VEC;
+  T sig_u[K];
+#pragma unroll
+  for (int k = 1; k < K; ++k) sig_u[k] = v_u ? S.sigma[k] : T(0);
+  // Stage k (2, 3) is exact k-1 rows inside the footprint; stage 3 is used up to the first
+  // voxel of the right x halo (stage 4's right neighbour), stage 4 on the stored voxels.
+  bool wneed[K + 1];
+  wneed[0] = true;
+#pragma unroll
+  for (int k = 2; k <= K + 1; ++k) {
+    const bool in_x = single_x || k < K ||
+                      (lx >= HL && (k == K ? lx <= lxb - HL : lx < lxb - HL));
+    const int last = k <= K ? Q.rows - k : Q.rows - 1 - HB;
+    const bool mine = active && row >= (k <= K ? k - 1 : HA) && row <= last && in_x;
+    wneed[k - 1] = __ballot(mine) != 0ull;
+  }
+
+  // zero rows above and below the footprint, once
+  for (int i = tid; i < 2 * lxb * VEC; i += NT) {
+    const int e = i % (lxb * VEC);
+    const int at = i >= lxb * VEC ? (Q.rows + 1) * lxb * VEC + e : e;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+#pragma unroll
+      for (int kk = 0; kk < K; ++kk) s_xb[b][kk][at] = T(0);
+      s_py[b][at] = T(0);
+    }
+  }
+
+  struct Carry {
+    T pz[K][VEC];           // pz[k-1]: p^(k)_z on the plane stage k finished last
+    T c_xb[K + 1][VEC];     // [k-1], k = 2..4: xbar^(k-1) on plane s-(k-1)
+    T c_x[K][VEC];          //        k = 2..3:    x^(k-1) there
+    T c_bt[K][VEC];         //                     bt there
+    T c_kt[K][VEC];         //                     in-plane part of K^T p^(k) there
+    T c_px[K + 1][VEC];     // [k-1], k = 3..4: p_x^(k-1) on plane s-(k-2) (from IP_{k-1})
+    T c_py[K + 1][VEC];
+  };
+  Carry CA, CB;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    zero(CA.pz[k]); zero(CA.c_x[k]); zero(CA.c_bt[k]); zero(CA.c_kt[k]);
+  }
+#pragma unroll
+  for (int k = 0; k <= K; ++k) { zero(CA.c_xb[k]); zero(CA.c_px[k]); zero(CA.c_py[k]); }
+  uint32_t adv = (uint32_t)(s_first - pz0) * szb;   // scalar offset of plane s
+  // p_z^(1) of the plane below the first one (zero at the bottom of the volume)
+  bld<T, VEC>(r_pz, s_first > 0 ? v_own : kInvalid, s_first > 0 ? adv - szb : 0u, CA.pz[0]);
+
+  typedef ShiftLoads<T, VEC> Loads;
+  Loads LA, LB;
+  auto issue_loads = [&](Loads &L, uint32_t a) {
+    bld<T, VEC>(r_x, v_own, a, L.xv);
+    bld<T, VEC>(r_bt, v_own, a, L.btn);
+    bld<T, VEC>(r_px, v_own, a, L.pxo);
+    bld<T, VEC>(r_py, v_own, a, L.pyo);
+    bld<T, VEC>(r_pz, v_own, a, L.pzo);
+    bld<T, VEC>(r_py, v_up, a, L.pyup);
+    L.pxleft = bld1<T>(r_px, v_left, a);
+  };
+  issue_loads(LA, adv);
+
+  auto step = [&](auto have1_tag, int s, Loads &L, Loads &LN, const Carry &P,
+                  Carry &N) {
+    constexpr bool HAVE1 = decltype(have1_tag)::value;
+    // fr_*[k-1]: results of stage k produced in this step
+    T fr_xb[K][VEC], fr_x[K][VEC], fr_bt[K][VEC], pzn[K][VEC];
+    T f_px[VEC], f_py[VEC], h_pyup[VEC];
+    T pxl;                       // p_x^(1) of the voxel left of this lane's vector
+    if constexpr (HAVE1) {
+      const bool more = s + 1 <= s_hi;
+      if constexpr (PF2) issue_loads(LN, more ? adv + szb : adv);
+      // ================= stage 1: the primal half of iteration n+1 on plane s ==
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        f_px[j] = L.pxo[j];
+        f_py[j] = L.pyo[j];
+        pzn[0][j] = L.pzo[j];
+        h_pyup[j] = L.pyup[j];
+      }
+      pxl = __shfl_up(f_px[VEC - 1], 1, kWave);
+      if (row_beg) pxl = L.pxleft;
+      const T tm0 = tau_m[0];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const T pl = (j > 0) ? f_px[(j + VEC - 1) % VEC] : pxl;
+        T kt = adj_term<UNIT>(f_px[j], pl, G.wx);
+        kt += adj_term<UNIT>(f_py[j], h_pyup[j], G.wy);
+        kt += adj_term<UNIT>(pzn[0][j], P.pz[0][j], G.wz);
+        const T u = L.xv[j] - tm0 * kt;
+        const T xnew = prox_data_s<L1>(u, L.btn[j], S.tl[0], S.optl[0]);
+        fr_x[0][j] = xnew;
+        fr_xb[0][j] = xnew + S.theta[0] * (xnew - L.xv[j]);
+        fr_bt[0][j] = L.btn[j];
+      }
+      if constexpr (!PF2) issue_loads(L, more ? adv + szb : adv);
+    } else {
+      zero(fr_xb[0]); zero(fr_x[0]); zero(fr_bt[0]); zero(pzn[0]);
+      zero(f_px); zero(f_py); zero(h_pyup);
+      pxl = T(0);
+    }
+
+    // ================= F_k: finish iteration n+k on plane s-(k-1) ===========
+    const int a = s - (K - 1);                     // the plane x, p_x, p_y are stored at
+    const bool st_a = a >= zbeg && a < zend;       // uniform
+#pragma unroll
+    for (int k = 2; k <= K; ++k) {
+      const int f = s - (k - 1);
+      const bool inr = f >= 0 && f < nzi;
+      if (!wneed[k - 1]) {                         // wave-uniform
+        zero(fr_x[k - 1]); zero(fr_xb[k - 1]); zero(fr_bt[k - 1]); zero(pzn[k - 1]);
+        continue;
+      }
+      const T sk = inr ? sig_m[k - 1] : T(0);
+      const T tk = inr ? tau_m[k - 1] : T(0);
+      T pkz[VEC];
+      dual_vec<HUBER, UNIT>(pkz, P.pz[k - 2], fr_xb[k - 2], P.c_xb[k - 1], G.wz, sk,
+                            S.hden[k - 1]);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        T kt = P.c_kt[k - 1][j];
+        kt += adj_term<UNIT>(pkz[j], P.pz[k - 1][j], G.wz);
+        const T u = P.c_x[k - 1][j] - tk * kt;
+        const T xk = prox_data_s<L1>(u, P.c_bt[k - 1][j], S.tl[k - 1], S.optl[k - 1]);
+        fr_x[k - 1][j] = xk;
+        fr_xb[k - 1][j] = xk + S.theta[k - 1] * (xk - P.c_x[k - 1][j]);
+        fr_bt[k - 1][j] = P.c_bt[k - 1][j];
+        pzn[k - 1][j] = pkz[j];
+      }
+      if (k == K && st_a)
+        bst<T, VEC>(w_x, v_st + (adv - (uint32_t)(K - 1) * szb), fr_x[K - 1]);
+    }
+    // ================= F_4: the z component of the last dual step, plane s-K ===
+    if (wneed[K]) {
+      const int f = s - K;
+      if (f >= zbeg && f < zend) {                 // uniform
+        T pkz[VEC];
+        dual_vec<HUBER, UNIT>(pkz, P.pz[K - 1], fr_xb[K - 1], P.c_xb[K], G.wz, S.sigma[K],
+                              S.hden[K]);
+        bst<T, VEC>(w_pz, v_st + (adv - (uint32_t)K * szb), pkz);
+      }
+    }
+
+    // ================= IP_k: in-plane part of iteration n+k on plane s-(k-2) =
+    const int buf = (int)(s & 1);
+#pragma unroll
+    for (int k = 2; k <= K + 1; ++k) stv<T, VEC>(&s_xb[buf][k - 2][li], fr_xb[k - 2]);
+    stv<T, VEC>(&s_py[buf][li], P.c_py[K - 1]);
+    s_px[buf][slot] = P.c_px[K - 1][VEC - 1];
+    __syncthreads();
+    T n_kt[K][VEC], n_px[K][VEC], n_py[K][VEC];
+#pragma unroll
+    for (int k = 2; k <= K; ++k) {
+      if (!wneed[k - 1]) {                         // wave-uniform
+        zero(n_kt[k - 1]); zero(n_px[k - 1]); zero(n_py[k - 1]);
+        continue;
+      }
+      T below[VEC], above[VEC], above_py[VEC];
+      ldv<T, VEC>(&s_xb[buf][k - 2][li + lxb * VEC], below);
+      ldv<T, VEC>(&s_xb[buf][k - 2][li - lxb * VEC], above);
+      if (k == 2) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) above_py[j] = h_pyup[j];
+      } else {
+        ldv<T, VEC>(&s_py[buf][li - lxb * VEC], above_py);
+      }
+      T right = s_xb[buf][k - 2][li + VEC];
+      if (!n_r) right = T(0);
+      const T left_xb = s_xb[buf][k - 2][li - 1];
+      const T left_px = (k == 2) ? pxl : s_px[buf][slot - 1];
+      const T pl0 = v_l ? dual_update_u<HUBER, UNIT>(left_px, fr_xb[k - 2][0], left_xb, G.wx,
+                                               S.sigma[k - 1], S.hden[k - 1])
+                        : T(0);
+      T pkx[VEC], pky[VEC], puv[VEC];
+      const T sgk = sig_m[k - 1];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const T px_old = (k == 2) ? f_px[j] : P.c_px[k - 1][j];
+        const T hx = (j + 1 < VEC) ? fr_xb[k - 2][(j + 1) % VEC] : right;
+        pkx[j] = dual_update_u<HUBER, UNIT>(px_old, hx, fr_xb[k - 2][j], G.wx, sgk,
+                                      S.hden[k - 1]);
+      }
+      if (k == 2)
+        dual_vec<HUBER, UNIT>(pky, f_py, below, fr_xb[k - 2], G.wy, sgk, S.hden[k - 1]);
+      else
+        dual_vec<HUBER, UNIT>(pky, P.c_py[k - 1], below, fr_xb[k - 2], G.wy, sgk,
+                              S.hden[k - 1]);
+      dual_vec<HUBER, UNIT>(puv, above_py, fr_xb[k - 2], above, G.wy, sig_u[k - 1],
+                            S.hden[k - 1]);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const T pl = (j > 0) ? pkx[(j + VEC - 1) % VEC] : pl0;
+        T kt = adj_term<UNIT>(pkx[j], pl, G.wx);
+        kt += adj_term<UNIT>(pky[j], puv[j], G.wy);
+        n_kt[k - 1][j] = kt;
+        n_px[k - 1][j] = pkx[j];
+        n_py[k - 1][j] = pky[j];
+      }
+    }
+    // ================= IP_4: p_x, p_y of the last dual step on plane s-(K-1) ===
+    // (no K^T follows it: neither the left nor the upper voxel's dual is recomputed)
+    if (wneed[K] && st_a) {
+      T below[VEC], pkx[VEC], pky[VEC];
+      ldv<T, VEC>(&s_xb[buf][K - 1][li + lxb * VEC], below);
+      T right = s_xb[buf][K - 1][li + VEC];
+      if (!n_r) right = T(0);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const T hx = (j + 1 < VEC) ? fr_xb[K - 1][(j + 1) % VEC] : right;
+        pkx[j] = dual_update_u<HUBER, UNIT>(P.c_px[K][j], hx, fr_xb[K - 1][j], G.wx,
+                                      S.sigma[K], S.hden[K]);
+      }
+      dual_vec<HUBER, UNIT>(pky, P.c_py[K], below, fr_xb[K - 1], G.wy, S.sigma[K], S.hden[K]);
+      const uint32_t vo = v_st + (adv - (uint32_t)(K - 1) * szb);
+      bst<T, VEC>(w_px, vo, pkx);
+      bst<T, VEC>(w_py, vo, pky);
+    }
+
+    // ================= next state ==========================================
+#pragma unroll
+    for (int k = K + 1; k >= 2; --k) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        N.c_xb[k - 1][j] = fr_xb[k - 2][j];
+        if (k <= K) {
+          N.c_x[k - 1][j] = fr_x[k - 2][j];
+          N.c_bt[k - 1][j] = fr_bt[k - 2][j];
+          N.c_kt[k - 1][j] = n_kt[k - 1][j];
+          N.c_px[k][j] = n_px[k - 1][j];
+          N.c_py[k][j] = n_py[k - 1][j];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) N.pz[k][j] = pzn[k][j];
+    adv += szb;
+  };
+
+  __syncthreads();   // LDS padding rows are zero before anyone reads them
+  int s = s_first;
+  if constexpr (PF2) {
+    for (; s + 1 <= s_hi; s += 2) {
+      step(std::true_type{}, s, LA, LB, CA, CB);
+      step(std::true_type{}, s + 1, LB, LA, CB, CA);
+    }
+    if (s <= s_hi) {
+      step(std::true_type{}, s, LA, LB, CA, CB);
+      CA = CB;
+      ++s;
+    }
+  } else {
+    for (; s <= s_hi; ++s) step(std::true_type{}, s, LA, LA, CA, CA);
+  }
+  for (; s <= s_last; ++s)       // at most K drain steps
+    step(std::false_type{}, s, LA, LA, CA, CA);
+}
+
 struct Tuning {
   int enable = 1;
   int kmax = 3;
@@ -928,8 +1340,10 @@ struct Config {
 // Footprint of `nt` lanes cut into ntx columns of tiles.
 // xv_fixed > 0: that many valid voxels per tile (the last tile may be shorter)
 // instead of nx spread evenly over ntx tiles
+// lost: footprint rows that are overlap (2 h; the shifted form: 2 above + 3 below)
 inline bool make_tiling(int64_t nx, int64_t ny, int nt, int vec, int h, int hx,
-                        int lxm, int ntx, Tiling *out, int64_t xv_fixed = 0) {
+                        int lxm, int ntx, Tiling *out, int64_t xv_fixed = 0, int lost = -1) {
+  if (lost < 0) lost = 2 * h;
   Tiling q;
   if (ntx == 1) {
     q.xv = 0;
@@ -943,9 +1357,9 @@ inline bool make_tiling(int64_t nx, int64_t ny, int nt, int vec, int h, int hx,
   }
   if (q.lxb < 1 || q.lxb > lxm) return false;
   q.rows = nt / q.lxb;
-  if (q.rows - 2 * h < 1) return false;
+  if (q.rows - lost < 1) return false;
   q.ntx = ntx;
-  q.nty = (int)((ny + (q.rows - 2 * h) - 1) / (q.rows - 2 * h));
+  q.nty = (int)((ny + (q.rows - lost) - 1) / (q.rows - lost));
   // interior of a row = whole half-waves: give them to whole half-waves
   q.split = (ntx > 1 && (q.xv / vec) % 32 == 0 && g_split != 0) ? 1 : 0;
   *out = q;
@@ -977,9 +1391,10 @@ inline double pick_zchunk(int64_t nz, int64_t tiles, int extra, int64_t max_chun
 // Bytes one launch pulls through L2 if no overlap is shared between footprints:
 // whole 128-byte lines per footprint row (the x halo costs a line on each side,
 // which is what makes narrow tiles expensive), six input arrays, plus the five
-// output arrays once.
+// output arrays once.  (The shifted form: five input arrays, four output arrays, and
+// rows - 5 valid rows that start h = 2 rows inside the footprint.)
 inline double model_cost(const Tiling &q, int64_t nx, int64_t ny, int64_t nz,
-                         int vec, int esize, int h, int hx, double zeff) {
+                         int vec, int esize, int h, int hx, double zeff, bool shift = false) {
   double lines = 0.0;
   for (int tx = 0; tx < q.ntx; ++tx) {
     int64_t lo = q.xv ? (int64_t)tx * q.xv - hx : 0;
@@ -990,15 +1405,15 @@ inline double model_cost(const Tiling &q, int64_t nx, int64_t ny, int64_t nz,
     lines += (double)((hi * esize - 1) / 128 - (lo * esize) / 128 + 1);
   }
   double rows = 0.0;
-  const int64_t tyv = q.rows - 2 * h;
+  const int64_t tyv = q.rows - (shift ? 2 * h + 1 : 2 * h);
   for (int ty = 0; ty < q.nty; ++ty) {
     int64_t lo = (int64_t)ty * tyv - h, hi = lo + q.rows;
     if (lo < 0) lo = 0;
     if (hi > ny) hi = ny;
     if (hi > lo) rows += (double)(hi - lo);
   }
-  const double reads = lines * 128.0 * rows * (double)nz * 6.0;
-  const double writes = 5.0 * (double)nx * ny * nz * esize;
+  const double reads = lines * 128.0 * rows * (double)nz * (shift ? 5.0 : 6.0);
+  const double writes = (shift ? 4.0 : 5.0) * (double)nx * ny * nz * esize;
   return (reads + writes) / zeff;
 }
 
@@ -1082,11 +1497,14 @@ int launch_cfg(const Config &c, const T *xbar_in, T *xbar_out, const T *x_in,
 template <int NT, int K> constexpr int lxm_of() { return LdsShape<NT, K>::LXM; }
 
 // candidate configurations for a shape, cheapest (by model) first
-template <typename T, int K>
+// SHIFT: footprints of k_pd_shift3 (rows - 5 valid rows, an x halo of >= K voxels, one
+// more plane of overlap per z-chunk)
+template <typename T, int K, bool SHIFT = false>
 std::vector<Config> candidates(const Geom<T> &G) {
   constexpr int VW = 16 / sizeof(T);
   constexpr int H = K - 1;
-  constexpr int HX = ((H + VW - 1) / VW) * VW;
+  constexpr int HX = (((SHIFT ? K : H) + VW - 1) / VW) * VW;
+  constexpr int LOST = SHIFT ? 2 * H + 1 : 2 * H;   // rows, and planes per z-chunk
   std::vector<Config> out;
   const int64_t plane_bytes = G.sz * (int64_t)sizeof(T);
   // 32-bit buffer offsets: the planes one workgroup touches span < 2^30 bytes
@@ -1097,6 +1515,7 @@ std::vector<Config> candidates(const Geom<T> &G) {
     const int nw = Waves<K>::v[wi];
     if (g_tunek.nw > 0 && g_tunek.nw != nw) continue;
     if (G.nx % VW != 0 && nw != 12) continue;     // see launch_cfg
+    if (SHIFT && g_tunek.pf2 == 0 && nw == 8) continue;   // 8 waves: the two-set form only
     const int nt = nw * 64;
     const int lxm = nt / (2 * K);
     // tile counts 1..64 with nx spread evenly, plus tiles whose interior is exactly
@@ -1117,17 +1536,17 @@ std::vector<Config> candidates(const Geom<T> &G) {
       c.nw = nw;
       c.pf2 = (nw == 8) ? 1 : 0;
       if (g_tunek.pf2 == 0) c.pf2 = 0;
-      if (!make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &c.q, sp.xv)) continue;
+      if (!make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &c.q, sp.xv, LOST)) continue;
       const int64_t tiles = (int64_t)c.q.ntx * c.q.nty;
       double zeff;
       if (g_tunek.zchunk > 0) {
         c.zchunk = g_tunek.zchunk < max_chunk ? g_tunek.zchunk : max_chunk;
         if (c.zchunk > G.nz) c.zchunk = G.nz;
-        zeff = (double)c.zchunk / (double)(c.zchunk + 2 * H);
+        zeff = (double)c.zchunk / (double)(c.zchunk + LOST);
       } else {
-        zeff = pick_zchunk(G.nz, tiles, 2 * H, max_chunk, &c.zchunk);
+        zeff = pick_zchunk(G.nz, tiles, LOST, max_chunk, &c.zchunk);
       }
-      c.cost = model_cost(c.q, G.nx, G.ny, G.nz, VW, (int)sizeof(T), H, HX, zeff);
+      c.cost = model_cost(c.q, G.nx, G.ny, G.nz, VW, (int)sizeof(T), H, HX, zeff, SHIFT);
       // fewer waves hide less latency: mild penalty so that ties go to more waves
       c.cost *= 1.0 + 0.02 * (16 - nw) / 4.0;
       if (c.q.split) {
@@ -1157,9 +1576,10 @@ struct PlanKey {
   int device, esize, k;
   int64_t nz, ny, nx;
   int64_t pitch = 0;     // row pitch of a padded layout (0: contiguous rows)
+  int form = 0;          // 1: the shifted form (other tile counts and z-chunks)
   bool operator<(const PlanKey &o) const {
-    return std::tie(device, esize, k, nz, ny, nx, pitch) <
-           std::tie(o.device, o.esize, o.k, o.nz, o.ny, o.nx, o.pitch);
+    return std::tie(device, esize, k, nz, ny, nx, pitch, form) <
+           std::tie(o.device, o.esize, o.k, o.nz, o.ny, o.nx, o.pitch, o.form);
   }
 };
 inline int current_device() {
@@ -1263,6 +1683,19 @@ inline void plan_poll(Plan &P, int K) {
   }
 }
 
+template <typename T, int K, bool SHIFT, typename Go>
+int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go);
+
+// the unshifted depth-3 plan's candidates on a shape that has a shifted plan: per
+// workgroup size the model's best and the tilings with up to 4 tiles along x
+inline std::vector<Config> short_list(const std::vector<Config> &cand) {
+  std::vector<Config> out;
+  int per_nw[17] = {0};
+  for (const Config &c : cand)
+    if (per_nw[c.nw]++ < 1 || c.q.ntx <= 4) out.push_back(c);
+  return out;
+}
+
 template <typename T, int K>
 int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
              const T *p_in, T *p_out, const Geom<T> &G, const double *sigma,
@@ -1274,21 +1707,30 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
     S.tl[i] = (T)tl[i]; S.optl[i] = prox_den<T>(tl[i]); S.theta[i] = (T)theta[i];
   }
   S.has_p = p_in != nullptr ? 1 : 0;
-#define NSOL_GO(cfg)                                                              \
-  launch_cfg<T, K>(cfg, xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, S, flags, st)
+  return planned_launch<T, K, false>(G, S.has_p != 0, st, [&](const Config &cfg) {
+    return launch_cfg<T, K>(cfg, xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, S,
+                            flags, st);
+  });
+}
+
+// One launch under the shape's plan: `go(config)` launches; `sample`: this launch may be
+// timed as a sample of an exploring plan.
+template <typename T, int K, bool SHIFT, typename Go>
+int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go) {
+#define NSOL_GO(cfg) go(cfg)
   const bool forced = g_tunek.nw > 0 || g_tunek.ntx > 0 || g_tunek.zchunk > 0;
   if (forced) {                     // experiments and tests: no plan, no tuning
-    std::vector<Config> cand = candidates<T, K>(G);
+    std::vector<Config> cand = candidates<T, K, SHIFT>(G);
     if (cand.empty()) return -2;
     return NSOL_GO(cand[0]);
   }
   const PlanKey key{current_device(), (int)sizeof(T), K, G.nz, G.ny, G.nx,
-                    G.padded ? G.sy : 0};
+                    G.padded ? G.sy : 0, SHIFT ? 1 : 0};
   std::lock_guard<std::mutex> lock(g_plans_mutex);
   auto it = g_plans.find(key);
   if (it == g_plans.end()) {
     Plan P;
-    std::vector<Config> cand = candidates<T, K>(G);
+    std::vector<Config> cand = candidates<T, K, SHIFT>(G);
     if (cand.empty()) return -2;
     const bool big = G.n >= ((int64_t)g_tunek.tune_min_mvox << 20);
     // Depth 2 only ever runs the trailing pair of a run: ONE launch per run, far too
@@ -1298,9 +1740,12 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
     // a pair against 1.19 for k_pd_fused2 and for the depth-3 plan's own tiling,
     // tools/_probe/tail2_tuned.py), else the model's best tiling with the depth-3
     // plan's workgroup size and tile count along x.
+    // (the depth-3 plan of a shape whose long runs take the shifted block: that form's)
     int seeded = -1;
     if (K == 2 && g_tunek.autotune && big) {
       auto it3 = g_plans.find(PlanKey{key.device, key.esize, 3, G.nz, G.ny, G.nx, key.pitch});
+      if (it3 == g_plans.end() || it3->second.chosen < 0)
+        it3 = g_plans.find(PlanKey{key.device, key.esize, 3, G.nz, G.ny, G.nx, key.pitch, 1});
       if (it3 != g_plans.end() && it3->second.chosen >= 0) {
         const Config &c3 = it3->second.cand[it3->second.chosen];
         for (int i = 0; i < (int)cand.size() && seeded < 0; ++i)
@@ -1309,9 +1754,39 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
           if (cand[i].nw == c3.nw && cand[i].q.ntx == c3.q.ntx) seeded = i;
       }
     }
+    // The unshifted depth-3 form of a shape that has a shifted plan runs only what
+    // the block leaves over -- the short runs -- and explores on launches that long runs
+    // give up for it (shift_donation below).  Its list is short then: per workgroup size
+    // the tilings with up to 4 tiles along x and the model's best, no shorter z-chunks
+    // (the full list settles on one of them at 512^3 and at 256^3).
+    bool shortlist = false;
+    if (K == 3 && !SHIFT && g_tunek.autotune && big) {
+      auto its = g_plans.find(PlanKey{key.device, key.esize, 3, G.nz, G.ny, G.nx, key.pitch, 1});
+      shortlist = its != g_plans.end();
+    }
     if (seeded >= 0) {
       P.cand.push_back(cand[seeded]);
       P.chosen = 0;
+    } else if (shortlist && cand.size() > 1) {
+      P.cand = short_list(cand);
+    } else if (SHIFT && g_tunek.autotune && big && cand.size() > 1) {
+      // The shifted plan explores on the launches of the first long runs of a shape
+      // (bench.py's plan pass: 8 runs of 19 launches), so its list is shorter: per
+      // workgroup size the tilings with up to 4 tiles along x plus the model's best
+      // three, and a shorter z-chunk only for the model's two best -- at 512^3 about 14
+      // candidates, two launches each and four more for every finalist.
+      int per_nw[17] = {0};
+      for (const Config &c : cand) {
+        const int rank = per_nw[c.nw]++;
+        if (rank >= 3 && c.q.ntx > 4) continue;
+        P.cand.push_back(c);
+        const int64_t zc = c.zchunk > 96 ? 64 : 24;
+        if (rank < 2 && zc < c.zchunk && zc <= G.nz) {
+          Config d = c;
+          d.zchunk = zc;
+          P.cand.push_back(d);
+        }
+      }
     } else if (g_tunek.autotune && big && cand.size() > 1) {
       // per workgroup size: the tilings with up to 8 tiles along x plus the
       // model's best five, each also with a shorter z-chunk (more workgroups in
@@ -1353,7 +1828,7 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
   int pick = -1;
   {
     const float best_now = plan_best(P);
-    for (int r = 1; r <= kFinalRounds && pick < 0 && S.has_p; ++r)
+    for (int r = 1; r <= kFinalRounds && pick < 0 && sample; ++r)
       for (int i = 0; i < (int)P.cand.size() && pick < 0; ++i) {
         const int owed = plan_target(P, i, best_now);
         if (P.issued[i] < (r < owed ? r : owed)) pick = i;
@@ -1390,9 +1865,198 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
 #undef NSOL_GO
 }
 
+// ---- the shifted form: knobs, dispatch
+int g_shift = -1;             // -1: long runs of large volumes; 0: never; 1: wherever it applies
+// Shortest run that takes the shifted block when g_shift is -1: the block pays for a
+// stand-alone dual and a stand-alone primal pass (28 bytes per voxel each) with 8 bytes
+// per voxel saved per launch.  Measured at 512^3 and 256^3 (DESIGN.md section 5 has the
+// curves): even at 24 iterations, 4 - 5 % ahead at 30.
+int g_shift_min_iters = 30;
+
+inline int shift_threshold() {
+  if (g_shift > 0) return 4;            // one launch between the two stand-alone steps
+  return g_shift_min_iters > 4 ? g_shift_min_iters : 4;
+}
+
+template <typename T, int VEC, int NW, int WPE, bool PF2>
+int launch_shift(const Config &c, const T *x_in, T *x_out, const T *bt, const T *p_in,
+                 T *p_out, const Geom<T> &G, const ShiftScalars<T> &S, int flags,
+                 hipStream_t st) {
+  const Tiling &Q = c.q;
+  const int64_t tiles = (int64_t)Q.ntx * Q.nty;
+  const int64_t nzc = (G.nz + c.zchunk - 1) / c.zchunk;
+  int64_t blocks = tiles * nzc;
+  int64_t slab = 0;
+  if (g_tunek.xcd_map && tiles >= 16) {
+    slab = (tiles + 7) / 8;
+    blocks = 8 * slab * nzc;
+  }
+  if (blocks > 0x7fffffff) return NSOL_EINVAL;
+  if (g_tunek.verbose == 1)
+    fprintf(stderr, "k_pd_shift3 waves=%d pf2=%d split=%d: lxb=%d rows=%d xv=%d tiles=%dx%d "
+            "zchunk=%lld blocks=%lld slab=%lld model=%.3f GB\n", NW, (int)PF2, Q.split, Q.lxb,
+            Q.rows, Q.xv, Q.ntx, Q.nty, (long long)c.zchunk, (long long)blocks,
+            (long long)slab, c.cost * 1e-9);
+#define NSOL_S(HB, L, U)                                                             \
+  hipLaunchKernelGGL((k_pd_shift3<T, VEC, NW, WPE, HB, L, PF2, U>), dim3((unsigned)blocks), \
+                     dim3(NW * 64), 0, st, x_in, x_out, bt, p_in, p_out, G, S, Q,    \
+                     (int)c.zchunk, (int)slab)
+#define NSOL_SU(HB, L) do { if (unit) NSOL_S(HB, L, true); else NSOL_S(HB, L, false); } while (0)
+  const bool unit = G.wx == T(1) && G.wy == T(1) && G.wz == T(1);
+  const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
+  const bool l1 = (flags & NSOL_PD_DATA_L1) != 0;
+  if (huber) { if (l1) NSOL_SU(true, true); else NSOL_SU(true, false); }
+  else { if (l1) NSOL_SU(false, true); else NSOL_SU(false, false); }
+#undef NSOL_SU
+#undef NSOL_S
+  g_launches[1].fetch_add(1, std::memory_order_relaxed);
+  g_shift_launches.fetch_add(1, std::memory_order_relaxed);
+  return launch_status();
+}
+
+// Launches a long run gives up for the unshifted depth-3 plan of its shape (they run
+// ahead of the block or behind it, three iterations each, bit-identical either way): 0
+// until the shifted plan has issued its samples, then exactly the samples the unshifted
+// plan is still owed (plan_target), -1 once there is nothing left to ask for -- the run
+// loop then stops asking.  Without them the unshifted form -- the short runs -- would
+// explore on the very runs that are too short to gain from the block, or never.
+template <typename T>
+int shift_donation(const Geom<T> &G) {
+  if (!g_tunek.autotune || G.n < ((int64_t)g_tunek.tune_min_mvox << 20) || g_tunek.nw > 0 ||
+      g_tunek.ntx > 0 || g_tunek.zchunk > 0)
+    return -1;
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
+  const int dev = current_device();
+  auto its = g_plans.find(PlanKey{dev, (int)sizeof(T), 3, G.nz, G.ny, G.nx, 0, 1});
+  if (its == g_plans.end()) return 0;
+  plan_poll(its->second, 3);
+  if (its->second.chosen < 0) {
+    // (the host runs ahead of the device: a long run has issued every sample of the
+    // shifted plan long before the first one is read back -- that is when it hands over)
+    const Plan &S = its->second;
+    const float sbest = plan_best(S);
+    for (int i = 0; i < (int)S.cand.size(); ++i)
+      if (S.issued[i] < plan_target(S, i, sbest)) return 0;
+  }
+  auto it = g_plans.find(PlanKey{dev, (int)sizeof(T), 3, G.nz, G.ny, G.nx, 0, 0});
+  if (it == g_plans.end()) {        // not made yet: every candidate is owed kFinalRounds
+    const std::vector<Config> cand = candidates<T, 3, false>(G);
+    if (cand.size() < 2) return -1;
+    return (int)short_list(cand).size() * kFinalRounds + 1;
+  }
+  Plan &P = it->second;
+  plan_poll(P, 3);
+  if (P.chosen >= 0) return -1;
+  const float best = plan_best(P);
+  int want = 0;
+  for (int i = 0; i < (int)P.cand.size(); ++i) {
+    const int owed = plan_target(P, i, best) - P.issued[i];
+    if (owed > 0) want += owed;
+  }
+  return want + 1;      // (+ 1: a run's first launch may read no dual variable: no sample)
+}
+
+// does the shifted form apply to this shape under the knobs as they stand
+template <typename T>
+bool shift_shape_ok(int ndim, int64_t nz, int64_t ny, int64_t nx, int64_t pitch) {
+  constexpr int VW = 16 / sizeof(T);
+  if (!g_shift || !g_tunek.enable || g_tunek.kmax < 3 || ndim != 3 || pitch > nx) return false;
+  const int64_t n = nz * ny * nx;
+  if (n < ((int64_t)g_tunek.min_kvox << 10) || nx % VW != 0 || nx / VW < 8 || ny < 8 ||
+      nz < 8 || nz >= ((int64_t)1 << 30))
+    return false;
+  // by itself only on the volumes the online tuner handles (measured there)
+  return g_shift > 0 || n >= ((int64_t)g_tunek.tune_min_mvox << 20);
+}
+inline bool shift_shape_ok(int elem_size, int64_t nz, int64_t ny, int64_t nx) {
+  return elem_size == 4 ? shift_shape_ok<float>(3, nz, ny, nx, 0)
+                        : shift_shape_ok<double>(3, nz, ny, nx, 0);
+}
+
+// the shortest run of this shape that takes the shifted block (0: none): the form
+// applies under the knobs as they stand and a footprint fits
+template <typename T>
+int shift_min_iters_t(int ndim, int64_t nz, int64_t ny, int64_t nx, int64_t pitch) {
+  if (!shift_shape_ok<T>(ndim, nz, ny, nx, pitch)) return 0;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
+  const bool forced = g_tunek.nw > 0 || g_tunek.ntx > 0 || g_tunek.zchunk > 0;
+  if (forced || g_plans.find(PlanKey{current_device(), (int)sizeof(T), 3, nz, ny, nx, 0,
+                                     1}) == g_plans.end())
+    if (candidates<T, 3, true>(G).empty()) return 0;
+  return shift_threshold();
+}
+
 }  // namespace nsol_pdk
 
 namespace nsol {
+
+// The shortest run of this problem that nsol_pd_run_* sends through the shifted block,
+// 0 if none does: the form applies to the flags and the shape, and a footprint fits.
+template <typename T>
+int pd_shift3_min_iters(const T *x, const T *x_alt, const T *bt, const T *p0, const T *p1,
+                        int ndim, int64_t nz, int64_t ny, int64_t nx, int flags,
+                        int64_t pitch, int iterations) {
+  // (a run too short for the block under any shape asks nothing else: the short runs'
+  // path gains no host work -- the plan lookup and, without a plan, the candidate list
+  // cost tens of microseconds in front of a run's first launch)
+  if (!nsol_pdk::g_shift || iterations < nsol_pdk::shift_threshold()) return 0;
+  if (!x || !x_alt || !bt || !p0 || !p1 || !aligned16(x) || !aligned16(x_alt) ||
+      !aligned16(bt) || !aligned16(p0) || !aligned16(p1))
+    return 0;
+  return nsol_pd_shift_min_iters((int)sizeof(T), ndim, nz, ny, nx, flags, pitch);
+}
+
+template <typename T>
+int pd_shift3_donation(int64_t nz, int64_t ny, int64_t nx) {
+  return nsol_pdk::shift_donation<T>(make_geom<T>(3, nz, ny, nx, 1.0, 1.0, 1.0));
+}
+
+// One launch of k_pd_shift3: iterations n .. n+2's primal steps and n+1 .. n+3's dual
+// steps.  sigma, hden: 4 values (iterations n .. n+3, the first unused); tau, tl, theta: 3.
+// -2: the form does not apply, nothing was launched.
+template <typename T>
+int pd_shift3_iter(const T *x_in, T *x_out, const T *bt, const T *p_in, T *p_out, int ndim,
+                   int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+                   const double *sigma, const double *hden, const double *tau,
+                   const double *tl, const double *theta, int flags, void *stream) {
+  using namespace nsol_pdk;
+  if (!x_in || !x_out || !bt || !p_in || !p_out || !sigma || !hden || !tau || !tl ||
+      !theta || x_in == x_out || p_in == p_out)
+    return NSOL_EINVAL;
+  if (!pd_shift3_min_iters<T>(x_in, x_out, bt, p_in, p_out, ndim, nz, ny, nx, flags, 0,
+                              1 << 30))
+    return -2;
+  constexpr int VW = 16 / sizeof(T);
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  ShiftScalars<T> S;
+  for (int i = 0; i < 4; ++i) { S.sigma[i] = (T)sigma[i]; S.hden[i] = huber_den<T>(hden[i]); }
+  for (int i = 0; i < 3; ++i) {
+    S.tau[i] = (T)tau[i]; S.tl[i] = (T)tl[i]; S.optl[i] = prox_den<T>(tl[i]);
+    S.theta[i] = (T)theta[i];
+  }
+  hipStream_t st = as_stream(stream);
+  return planned_launch<T, 3, true>(G, true, st, [&](const Config &c) {
+    if (c.nw == 12)
+      return launch_shift<T, VW, 12, 3, false>(c, x_in, x_out, bt, p_in, p_out, G, S, flags, st);
+    if (c.nw == 8)
+      return launch_shift<T, VW, 8, 2, true>(c, x_in, x_out, bt, p_in, p_out, G, S, flags, st);
+    return (int)NSOL_EINVAL;
+  });
+}
+
+#define NSOL_PDS_INST(T)                                                                 \
+  template int pd_shift3_donation<T>(int64_t, int64_t, int64_t);                         \
+  template int pd_shift3_min_iters<T>(const T *, const T *, const T *, const T *,        \
+                                      const T *, int, int64_t, int64_t, int64_t, int,    \
+                                      int64_t, int);                                          \
+  template int pd_shift3_iter<T>(const T *, T *, const T *, const T *, T *, int, int64_t, \
+                                 int64_t, int64_t, double, double, double, const double *, \
+                                 const double *, const double *, const double *,         \
+                                 const double *, int, void *);
+NSOL_PDS_INST(float)
+NSOL_PDS_INST(double)
+#undef NSOL_PDS_INST
 
 // returns -2 if the kernel does not apply to this problem
 template <typename T>
@@ -1461,6 +2125,8 @@ int nsol_hip_set_param_pdk(const char *name, int value) {
   else if (!strcmp(name, "pdk_min_kvox")) nsol_pdk::g_tunek.min_kvox = value;
   else if (!strcmp(name, "pdk_tail2")) nsol_pdk::g_tunek.tail2 = value;
   else if (!strcmp(name, "pdk_tune_min_mvox")) nsol_pdk::g_tunek.tune_min_mvox = value;
+  else if (!strcmp(name, "pdk_shift")) nsol_pdk::g_shift = value < 0 ? -1 : (value ? 1 : 0);
+  else if (!strcmp(name, "pdk_shift_min_iters")) nsol_pdk::g_shift_min_iters = value;
   else if (!strcmp(name, "pdk_forget")) {
     std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
     for (auto &kv : nsol_pdk::g_plans)
@@ -1476,10 +2142,28 @@ int nsol_hip_set_param_pdk(const char *name, int value) {
 
 int nsol_pd_fusedk_tuned(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx) {
   std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
+  // (depth 3 of a shape whose long runs take the shifted block: that form's plan)
+  int form = (k == 3 && nsol_pdk::shift_shape_ok(elem_size, nz, ny, nx)) ? 1 : 0;
   auto it = nsol_pdk::g_plans.find(
-      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx});
+      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, form});
+  if (form && it == nsol_pdk::g_plans.end()) {
+    /* a process that has made short runs only: the unshifted plan is all there is */
+    form = 0;
+    it = nsol_pdk::g_plans.find(
+        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, 0});
+  }
   if (it == nsol_pdk::g_plans.end()) return -1;
   nsol_pdk::plan_poll(it->second, k);
+  if (form && it->second.chosen >= 0 && nsol_pdk::g_tunek.autotune &&
+      nz * ny * nx >= ((int64_t)nsol_pdk::g_tunek.tune_min_mvox << 20)) {
+    /* ... and the unshifted plan, which explores on launches the long runs give up for
+     * it once the shifted plan has settled: the shape's short runs take that one */
+    auto iu = nsol_pdk::g_plans.find(
+        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, 0});
+    if (iu == nsol_pdk::g_plans.end()) return 0;
+    nsol_pdk::plan_poll(iu->second, k);
+    return iu->second.chosen >= 0 ? 1 : 0;
+  }
   return it->second.chosen >= 0 ? 1 : 0;
 }
 
@@ -1496,10 +2180,13 @@ extern "C" int nsol_pd_fusedk_tail2_pitched(int elem_size, int64_t nz, int64_t n
       nz * ny * nx < ((int64_t)nsol_pdk::g_tunek.tune_min_mvox << 20))
     return 0;                       /* (measured on volumes the online tuner handles) */
   std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
-  auto it = nsol_pdk::g_plans.find(
-      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, 3, nz, ny, nx,
-                        pitch > nx ? pitch : 0});
-  return it != nsol_pdk::g_plans.end() && it->second.chosen >= 0 ? 1 : 0;
+  for (int form = 0; form < 2; ++form) {      /* either form's depth-3 plan */
+    auto it = nsol_pdk::g_plans.find(
+        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, 3, nz, ny, nx,
+                          pitch > nx ? pitch : 0, form});
+    if (it != nsol_pdk::g_plans.end() && it->second.chosen >= 0) return 1;
+  }
+  return 0;
 }
 
 int nsol_pd_fusedk_launches(int k) {
@@ -1507,11 +2194,54 @@ int nsol_pd_fusedk_launches(int k) {
   return nsol_pdk::g_launches[k - 2].load(std::memory_order_relaxed);
 }
 
+int nsol_pd_shift_launches(void) {
+  return nsol_pdk::g_shift_launches.load(std::memory_order_relaxed);
+}
+
+int nsol_pd_run_parts(int iterations, int min_iters, int *lead, int *launches) {
+  int l = iterations > 0 ? iterations : 0, m = 0;
+  if (min_iters > 0 && iterations >= min_iters && iterations >= 4) {
+    l = (iterations - 1) % 3;
+    m = (iterations - 1) / 3;
+  }
+  if (lead) *lead = l;
+  if (launches) *launches = m;
+  return m > 0 ? 1 : 0;
+}
+
+int nsol_pd_shift_min_iters(int elem_size, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                            int flags, int64_t pitch) {
+  if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return 0;
+  if (ndim != 3 || nz < 1 || ny < 1 || nx < 1) return 0;
+  if (elem_size == 4) return nsol_pdk::shift_min_iters_t<float>(ndim, nz, ny, nx, pitch);
+  if (elem_size == 8) return nsol_pdk::shift_min_iters_t<double>(ndim, nz, ny, nx, pitch);
+  return 0;
+}
+
+int nsol_pd_fusedk_plan_form(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
+                             int form, int *waves, int *ntx, int64_t *zchunk) {
+  std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
+  auto it = nsol_pdk::g_plans.find(nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k,
+                                                     nz, ny, nx, 0, form ? 1 : 0});
+  if (it == nsol_pdk::g_plans.end()) return NSOL_EINVAL;
+  nsol_pdk::plan_poll(it->second, k);
+  if (it->second.chosen < 0) return NSOL_EINVAL;
+  const nsol_pdk::Config &c = it->second.cand[it->second.chosen];
+  if (waves) *waves = c.nw;
+  if (ntx) *ntx = c.q.ntx;
+  if (zchunk) *zchunk = c.zchunk;
+  return 0;
+}
+
 int nsol_pd_fusedk_plan(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
                         int *waves, int *ntx, int64_t *zchunk) {
   std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
+  const int form = (k == 3 && nsol_pdk::shift_shape_ok(elem_size, nz, ny, nx)) ? 1 : 0;
   auto it = nsol_pdk::g_plans.find(
-      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx});
+      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, form});
+  if (form && it == nsol_pdk::g_plans.end())      /* short runs only so far: see _tuned */
+    it = nsol_pdk::g_plans.find(
+        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, 0});
   if (it == nsol_pdk::g_plans.end() || it->second.chosen < 0) return NSOL_EINVAL;
   const nsol_pdk::Config &c = it->second.cand[it->second.chosen];
   if (waves) *waves = c.nw;

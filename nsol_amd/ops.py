@@ -1156,6 +1156,34 @@ def pd_fusedk_launches(k=3):
     return int(_lib.load().nsol_pd_fusedk_launches(int(k)))
 
 
+def pd_fusedk_plan_form(x, shape, form, k=3):
+    """The settled plan of one form of the depth-k kernel (0: k_pd_fusedk, 1: the
+    shifted k_pd_shift3), or None."""
+    import ctypes
+    ndim, nz, ny, nx = dims3(shape)
+    wv, nt, zc = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    rc = _lib.load().nsol_pd_fusedk_plan_form(
+        int(x.element_size()), int(k), nz, ny, nx, int(form), ctypes.byref(wv),
+        ctypes.byref(nt), ctypes.byref(zc))
+    return None if rc else (int(wv.value), int(nt.value), int(zc.value))
+
+
+def pd_shift_launches():
+    """Launches of the shifted depth-3 form (k_pd_shift3) by this process so far;
+    they count into pd_fusedk_launches(3) as well."""
+    return int(_lib.load().nsol_pd_shift_launches())
+
+
+def pd_run_parts(iterations, min_iters):
+    """(taken, lead, launches): how nsol_pd_run_* cuts a run of `iterations` when the
+    shifted block starts at `min_iters` iterations (0: never)."""
+    import ctypes
+    lead, m = ctypes.c_int(0), ctypes.c_int(0)
+    taken = _lib.load().nsol_pd_run_parts(int(iterations), int(min_iters),
+                                          ctypes.byref(lead), ctypes.byref(m))
+    return bool(taken), int(lead.value), int(m.value)
+
+
 def pd_fusedk_plan(x, shape, k=3):
     """(waves, tiles along x, z-chunk) the online tuner settled on, or None."""
     import ctypes
