@@ -1036,6 +1036,48 @@ int nsol_pdl_stack_iter_f64(const double *xbar_in, double *xbar_out, double *x,
     double tau, double theta, double lo, double hi, int flags, int has_p, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * Second-order total generalised variation, TGV^2 (nsol_tgv.hip; the arithmetic is
+ * restated in nsol_amd/tgv_numpy.py):
+ *   min over x (n values), w (ndim * n)
+ *       lambda D(x, bt) + |grad x - w|_1 + beta |E w|_1
+ * grad: the zero-padded forward difference of nsol_grad_*, component 0 along x;
+ * (E w)_aa = D_a w_a, (E w)_ab = (D_a w_b + D_b w_a) / 2, M = ndim (ndim + 1) / 2 stored
+ * components, diagonals first (3-D: xx yy zz xy xz yz; 2-D: xx yy xy; 1-D: xx), the
+ * off-diagonals counted twice in every norm.  All stacks have component stride n.
+ *
+ * nsol_tgv_dual_*: p (ndim * n) and q (M * n) IN PLACE,
+ *   p_a  <- P_1   (p_a  + sigma (D_a xbar - wbar_a))
+ *   q_ab <- P_beta(q_ab + sigma (E wbar)_ab)
+ *   anisotropic: P_c clamps every component to [-c, c]; NSOL_PD_REG_ISOTROPIC: p /
+ *   max(1, |p|_2) and q / max(1, |q|_F / beta) per voxel.
+ * nsol_tgv_primal_*: x, w, xbar, wbar IN PLACE,
+ *   x+   = prox_{tl D}(x - tau sum_a D_a^T p_a)       (tl = tau * lambda, 0 allowed;
+ *                                                      NSOL_PD_DATA_L1: the l1 prox)
+ *   w_a+ = w_a - tau (-p_a + D_a^T q_aa + sum_{b != a} D_b^T q_ab)
+ *   xbar = x+ + theta (x+ - x),  wbar = w+ + theta (w+ - w)
+ * flags: NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_L1; any other bit is NSOL_EINVAL.
+ * Return -2, nothing launched, for a geometry the stencil grid does not take or more
+ * than 2^31 voxels; NSOL_EINVAL for a missing pointer, two arguments of one call that
+ * overlap, sigma, tau or beta that is not positive and finite, tl < 0; 0 at once when
+ * an extent is 0.
+ * nsol_tgv_launches: successful launches of the two kernels by this process. */
+int nsol_tgv_launches(void);
+int nsol_tgv_dual_f32(const float *xbar, const float *wbar, float *p, float *q,
+    int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+    double sigma, double beta, int flags, void *stream);
+int nsol_tgv_dual_f64(const double *xbar, const double *wbar, double *p, double *q,
+    int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+    double sigma, double beta, int flags, void *stream);
+int nsol_tgv_primal_f32(const float *p, const float *q, float *x, float *xbar,
+    float *w, float *wbar, const float *bt, int ndim, int64_t nz, int64_t ny,
+    int64_t nx, double wx, double wy, double wz, double tau, double tl, double theta,
+    int flags, void *stream);
+int nsol_tgv_primal_f64(const double *p, const double *q, double *x, double *xbar,
+    double *w, double *wbar, const double *bt, int ndim, int64_t nz, int64_t ny,
+    int64_t nx, double wx, double wy, double wz, double tau, double tl, double theta,
+    int flags, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
 /* t = grad(x) + w - c;  n = sqrt(sum_a t_a^2);  v_a = n > thr ?

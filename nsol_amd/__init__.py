@@ -21,6 +21,9 @@ def __getattr__(name):
     if name == "PrimalDualLinearSolver":
         from .primal_dual_linear_solver import PrimalDualLinearSolver
         return PrimalDualLinearSolver
+    if name == "TGVPrimalDualSolver":
+        from .tgv_solver import TGVPrimalDualSolver
+        return TGVPrimalDualSolver
     if name in ("PrimalDualLinearBatch", "PrimalDualLinearSweep"):
         from . import linear_stack
         return getattr(linear_stack, name)

@@ -32,6 +32,13 @@ The image must have the observation's shape.  Both compose with --isotropic, sev
 --alpha and --slice-wise (the weights are sliced with the data; a slice whose
 weights are all zero is copied through).
 
+--reconstruction-type TGVL2 | TGVL1 [--beta B]: second-order total generalised
+variation (TGVPrimalDualSolver, nsol_amd/tgv_solver.py), which keeps the smooth ramps
+that TV turns into terraces; B (default 2) weighs the second-order term.  Composes
+with --isotropic, --tolerance / --check-every, --dtype, --reference / --measures and
+--observe-every; several --alpha, --slice-wise, --mask / --weights and --alg-type are
+refused.  --L2 defaults to the bound of the operator's norm for these types.
+
 --slice-wise: a 3-D observation is shape[0] independent 2-D images, each with its
 own x_scale = max(slice), run together through PrimalDualBatch
 (nsol_amd/solver_batch.py) -- one launch per iteration for all slices -- and
@@ -50,6 +57,9 @@ from .. import data_writer as dw
 from .. import observer as Observer
 from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
+
+
+DEFAULT_ALG_TYPE = "ALG2"
 
 
 def wiring(observed_nda, reconstruction_type, isotropic=False, weights=None):
@@ -265,23 +275,46 @@ def run_slice_wise(args, observed_nda, x_ref, reader, weights=None):
     return 0
 
 
-def main(argv=None):
+TGV_TYPES = ("TGVL2", "TGVL1")
+
+
+def build_tgv_solver(observed_nda, reconstruction_type, alpha, beta, iterations, L2=None,
+                     verbose=0, dtype=None, tolerance=None, check_every=10,
+                     isotropic=False):
+    """The TGVPrimalDualSolver of a TGVL2 / TGVL1 run: start, data and scale as
+    wiring() takes them (x0 = b = the observation, x_scale its maximum)."""
+    from ..tgv_solver import TGVPrimalDualSolver
+    b = observed_nda.flatten()
+    return TGVPrimalDualSolver(
+        b, b.copy(), observed_nda.ndim, alpha=alpha, beta=beta, iterations=iterations,
+        data_loss="ell1" if reconstruction_type == "TGVL1" else "ell2",
+        isotropic=isotropic, L2=L2, x_scale=np.max(observed_nda), verbose=verbose,
+        dtype=dtype, tolerance=tolerance, check_every=check_every,
+        shape=observed_nda.shape)
+
+
+def build_parser():
     ap = argparse.ArgumentParser(
-        description="Run TVL1/TVL2/HuberL1/HuberL2 denoising on an MI355X")
+        description="Run TVL1/TVL2/HuberL1/HuberL2/TGVL1/TGVL2 denoising on an MI355X")
     ap.add_argument("--observation", required=True)
     ap.add_argument("--result", required=False)
     ap.add_argument("--reference", required=False)
     ap.add_argument("--reconstruction-type", default="TVL2",
-                    choices=["TVL1", "TVL2", "HuberL1", "HuberL2"])
+                    choices=["TVL1", "TVL2", "HuberL1", "HuberL2", "TGVL2", "TGVL1"])
+    ap.add_argument("--beta", type=float, default=None, metavar="B",
+                    help="TGVL2 / TGVL1: the weight of the second-order term "
+                         "|E w|_1 against |grad x - w|_1 (default 2)")
     ap.add_argument("--measures", nargs="+",
                     default=["PSNR", "RMSE", "NCC"])
     ap.add_argument("--iterations", type=int, default=50)
     ap.add_argument("--solver", default="PD", choices=["PD"])
     ap.add_argument("--alpha", type=float, nargs="+", default=[0.03])
-    ap.add_argument("--L2", type=float, default=8,
-                    help="the reference hard-codes 8 (run_denoising.py:147); "
-                         "3-D data needs >= 12 for a convergent step size")
-    ap.add_argument("--alg-type", default="ALG2")
+    ap.add_argument("--L2", type=float, default=None,
+                    help="default 8, which the reference hard-codes "
+                         "(run_denoising.py:147); 3-D data needs >= 12 for a "
+                         "convergent step size.  TGVL2 / TGVL1: default the bound "
+                         "of |K|^2 for the data's dimension")
+    ap.add_argument("--alg-type", default=DEFAULT_ALG_TYPE)
     ap.add_argument("--dtype", default="float32",
                     choices=["float32", "float64"])
     ap.add_argument("--verbose", type=int, default=0)
@@ -316,7 +349,36 @@ def main(argv=None):
     ap.add_argument("--check-every", type=int, default=10, metavar="K",
                     help="with --tolerance: evaluate the change every K iterations "
                          "and at the last")
+    return ap
+
+
+def parse_args(argv=None, ap=None):
+    """The checked arguments; a combination that is not taken is a parser error."""
+    ap = ap or build_parser()
     args = ap.parse_args(argv)
+    if args.reconstruction_type in TGV_TYPES:
+        if len(args.alpha) > 1:
+            ap.error("--reconstruction-type %s takes a single --alpha" %
+                     args.reconstruction_type)
+        if args.slice_wise:
+            ap.error("--reconstruction-type %s does not take --slice-wise" %
+                     args.reconstruction_type)
+        if args.mask is not None or args.weights is not None:
+            ap.error("--reconstruction-type %s does not take %s" % (
+                args.reconstruction_type,
+                "--mask" if args.mask is not None else "--weights"))
+        if args.alg_type != DEFAULT_ALG_TYPE:
+            ap.error("--reconstruction-type %s does not take --alg-type: its "
+                     "iteration has constant steps" % args.reconstruction_type)
+        if args.beta is None:
+            args.beta = 2.0
+        if not (np.isfinite(args.beta) and args.beta > 0):
+            ap.error("--beta must be positive")
+    else:
+        if args.beta is not None:
+            ap.error("--beta goes with --reconstruction-type TGVL2 / TGVL1")
+        if args.L2 is None:
+            args.L2 = 8
     if args.tolerance is not None and not args.tolerance >= 0:
         ap.error("--tolerance must be >= 0")
     if args.check_every < 1:
@@ -326,6 +388,12 @@ def main(argv=None):
     if args.slice_wise and args.observe_every is not None:
         ap.error("--slice-wise does not take --observe-every: the measures are "
                  "taken once, on the reassembled volume")
+    return args
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = parse_args(argv, ap)
 
     if len(args.alpha) == 1 and args.result is None:
         raise IOError("'--result' must be specified")
@@ -354,14 +422,24 @@ def main(argv=None):
         return run_sweep(args, observed_nda, x_ref, reader, weights)
 
     for alpha in args.alpha:
-        solver = build_solver(observed_nda, args.reconstruction_type, alpha,
-                              args.iterations, L2=args.L2,
-                              verbose=args.verbose,
-                              dtype=np.dtype(args.dtype).type,
-                              alg_type=args.alg_type,
-                              isotropic=args.isotropic, weights=weights,
-                              tolerance=args.tolerance,
-                              check_every=args.check_every)
+        if args.reconstruction_type in TGV_TYPES:
+            try:
+                solver = build_tgv_solver(
+                    observed_nda, args.reconstruction_type, alpha, args.beta,
+                    args.iterations, L2=args.L2, verbose=args.verbose,
+                    dtype=np.dtype(args.dtype).type, tolerance=args.tolerance,
+                    check_every=args.check_every, isotropic=args.isotropic)
+            except ValueError as e:
+                ap.error(str(e))
+        else:
+            solver = build_solver(observed_nda, args.reconstruction_type, alpha,
+                                  args.iterations, L2=args.L2,
+                                  verbose=args.verbose,
+                                  dtype=np.dtype(args.dtype).type,
+                                  alg_type=args.alg_type,
+                                  isotropic=args.isotropic, weights=weights,
+                                  tolerance=args.tolerance,
+                                  check_every=args.check_every)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \

@@ -1,0 +1,384 @@
+// Second-order total generalised variation (TGV^2, Bredies / Kunisch / Pock) for gfx950
+// (MI355X): the two kernels of one Chambolle-Pock iteration on
+//
+//   min over x (n values), w (d n values)   lambda D(x, b~) + |grad x - w|_1 + beta |E w|_1
+//
+// with grad the zero-padded forward difference of k_grad (component a = 0 is the x axis),
+// D_a^T its exact transpose (grad_adj_vec) and E w the symmetrised gradient of w,
+// (E w)_aa = D_a w_a, (E w)_ab = 1/2 (D_a w_b + D_b w_a), stored diagonals first (3-D: xx,
+// yy, zz, xy, xz, yz; 2-D: xx, yy, xy; 1-D: xx).  Off-diagonals count twice in every norm.
+//
+//   k_tgv_dual    p_a  <- P_1   (p_a  + sigma (D_a xbar - wbar_a))
+//                 q_ab <- P_beta(q_ab + sigma (E wbar)_ab)
+//                 reads xbar, wbar and their forward neighbours, p and q at their own
+//                 index; writes p and q in place.
+//   k_tgv_primal  x+   = prox_{tau lambda D}(x - tau sum_a D_a^T p_a)
+//                 w_a+ = w_a - tau (-p_a + D_a^T q_aa + sum_{b != a} D_b^T q_ab)
+//                 xbar = x+ + theta (x+ - x), wbar likewise
+//                 reads p, q and their backward neighbours, x, w, b~ at their own index;
+//                 writes x, w, xbar, wbar in place.
+//
+// No array is read at a neighbour and written in the same launch: no ping-pong buffers,
+// no dependency between workgroups.  The thread mapping is nsol_stencil.hpp's (k_grad /
+// k_grad_adj); 3-D traffic is 22 + 22 words per voxel and iteration, 2-D 13 + 15.
+//
+// w, p and q are d or M components stacked at stride n.  Voxel::wide is computed against
+// ONE n-element array (c.i + forward offset + VEC <= n), so a whole-vector read that it
+// allows at component k ends at k n + n at the latest: inside the stack for every
+// component, the last one included.
+#include <math.h>
+
+#include <atomic>
+#include <type_traits>
+
+#include "nsol_common.hpp"
+#include "nsol_pd_iso_body.hpp"
+#include "nsol_stencil.hpp"
+
+using namespace nsol;
+
+namespace {
+
+std::atomic<int> g_tgv_launches{0};
+
+// stored component of the off-diagonal (a, b), a < b
+template <int NDIM>
+__device__ __forceinline__ constexpr int sym_off(int a, int b) {
+  return NDIM == 2 ? 2 : (a == 0 ? 2 + b : 5);
+}
+
+// D_a u at the lane's voxels; `own` holds u there (u: one component's base)
+template <bool RAG, typename T, int VEC>
+__device__ __forceinline__ void fwd_dir(int a, const T *__restrict__ u, const T (&own)[VEC],
+                                        const Geom<T> &G, const Voxel &c, T (&g)[VEC]) {
+  if (a == 0) {
+    const T right = (c.ix + VEC < G.nx) ? u[c.i + VEC] : T(0);
+    fwd_diff_x<T, VEC>(own, right, G.wx, g);
+  } else {
+    T hi[VEC];
+    vzero(hi);
+    if (a == 1) {
+      if (c.iy + 1 < G.ny) vlc<RAG, T, VEC>(c, u + c.i + G.sy, hi);
+    } else {
+      if (c.iz + 1 < G.nz) vlc<RAG, T, VEC>(c, u + c.i + G.sz, hi);
+    }
+    fwd_diff<T, VEC>(own, hi, a == 1 ? G.wy : G.wz, g);
+  }
+}
+
+// D_a^T u at the lane's voxels, u[i] * (-w_a) + u[i - e_a] * w_a as grad_adj_vec forms
+// it; `own` receives u there
+template <bool RAG, typename T, int VEC>
+__device__ __forceinline__ void adj_dir(int a, const T *__restrict__ u, const Geom<T> &G,
+                                        const Voxel &c, T (&own)[VEC], T (&out)[VEC]) {
+  vlc<RAG, T, VEC>(c, u + c.i, own);
+  if (a == 0) {
+    const T left = (c.ix > 0) ? u[c.i - 1] : T(0);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const T l = (k > 0) ? own[(k + VEC - 1) % VEC] : left;
+      out[k] = own[k] * (-G.wx) + l * G.wx;
+    }
+  } else {
+    T lo[VEC];
+    vzero(lo);
+    if (a == 1) {
+      if (c.iy > 0) vlc<RAG, T, VEC>(c, u + c.i - G.sy, lo);
+    } else {
+      if (c.iz > 0) vlc<RAG, T, VEC>(c, u + c.i - G.sz, lo);
+    }
+    const T w = a == 1 ? G.wy : G.wz;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) out[k] = own[k] * (-w) + lo[k] * w;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ T clamp_beta(T v, T beta) {
+  v = v < -beta ? -beta : v;
+  return v > beta ? beta : v;
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO>
+__global__ __launch_bounds__(kBlock) void k_tgv_dual(const T *__restrict__ xbar,
+                                                      const T *__restrict__ wbar, T *p,
+                                                      T *q, Geom<T> G, T sigma, T beta) {
+  constexpr int M = NDIM * (NDIM + 1) / 2;
+  const int64_t nrg = row_groups<T, VEC, ROWS>(G);
+  for (int64_t rg = blockIdx.y; rg < nrg; rg += gridDim.y) {
+    const Voxel c = voxel_at<T, VEC, ROWS>(G, rg);
+    if (!c.ok) continue;
+    T xb[VEC], wb[NDIM][VEC], pn[NDIM][VEC], e[M][VEC], g[VEC];
+    vlc<RAG, T, VEC>(c, xbar + c.i, xb);
+#pragma unroll
+    for (int b = 0; b < NDIM; ++b) vlc<RAG, T, VEC>(c, wbar + b * G.n + c.i, wb[b]);
+    // one direction a at a time: D_a xbar into p_a, the d shifted vectors of wbar into
+    // q_aa and the q_ab they feed
+#pragma unroll
+    for (int a = 0; a < NDIM; ++a) {
+      fwd_dir<RAG, T, VEC>(a, xbar, xb, G, c, g);
+      vlc<RAG, T, VEC>(c, p + a * G.n + c.i, pn[a]);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) pn[a][k] = pn[a][k] + sigma * (g[k] - wb[a][k]);
+#pragma unroll
+      for (int b = 0; b < NDIM; ++b) {
+        fwd_dir<RAG, T, VEC>(a, wbar + b * G.n, wb[b], G, c, g);
+        if (b == a) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) e[a][k] = g[k];
+        } else if (a < b) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) e[sym_off<NDIM>(a, b)][k] = g[k];   // D_a w_b
+        } else {
+          const int m = sym_off<NDIM>(b, a);
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) e[m][k] = T(0.5) * (e[m][k] + g[k]);  // + D_a w_b
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      if constexpr (ISO) {
+        T q0 = pn[0][k], q1 = T(0), q2 = T(0);
+        if constexpr (NDIM >= 2) q1 = pn[1][k];
+        if constexpr (NDIM >= 3) q2 = pn[2][k];
+        dual_project<NDIM>(q0, q1, q2, false, T(1));
+        pn[0][k] = q0;
+        if constexpr (NDIM >= 2) pn[1][k] = q1;
+        if constexpr (NDIM >= 3) pn[2][k] = q2;
+      } else {
+#pragma unroll
+        for (int a = 0; a < NDIM; ++a) pn[a][k] = dual_clamp<T>(pn[a][k]);
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < NDIM; ++a) vs<RAG, T, VEC>(c.nval, p + a * G.n + c.i, pn[a]);
+
+    // q <- P_beta(q + sigma E wbar), into e
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      vlc<RAG, T, VEC>(c, q + m * G.n + c.i, g);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) e[m][k] = g[k] + sigma * e[m][k];
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      if constexpr (ISO) {
+        // Frobenius norm with the off-diagonals doubled; q / max(1, |q|_F / beta)
+        T s = e[0][k] * e[0][k];
+#pragma unroll
+        for (int m = 1; m < NDIM; ++m) s = s + e[m][k] * e[m][k];
+#pragma unroll
+        for (int m = NDIM; m < M; ++m) s = s + T(2) * (e[m][k] * e[m][k]);
+        const T den = t_max(T(1), t_sqrt(s) / beta);
+#pragma unroll
+        for (int m = 0; m < M; ++m) e[m][k] = e[m][k] / den;
+      } else {
+#pragma unroll
+        for (int m = 0; m < M; ++m) e[m][k] = clamp_beta<T>(e[m][k], beta);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) vs<RAG, T, VEC>(c.nval, q + m * G.n + c.i, e[m]);
+  }
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO, bool L1>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ bt, Geom<T> G, T tau, T tl, T den, T theta) {
+  // (ISO does not change the primal step; it is a template parameter so that both
+  // kernels of one iteration are named by the same list)
+  const int64_t nrg = row_groups<T, VEC, ROWS>(G);
+  for (int64_t rg = blockIdx.y; rg < nrg; rg += gridDim.y) {
+    const Voxel c = voxel_at<T, VEC, ROWS>(G, rg);
+    if (!c.ok) continue;
+    T pw[NDIM][VEC], acc[VEC], t[VEC], own[VEC], v[VEC], o[VEC];
+    // x+ = prox(x - tau sum_a D_a^T p_a); the own p_a are kept for w
+    adj_dir<RAG, T, VEC>(0, p, G, c, pw[0], acc);
+#pragma unroll
+    for (int a = 1; a < NDIM; ++a) {
+      adj_dir<RAG, T, VEC>(a, p + a * G.n, G, c, pw[a], t);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] += t[k];
+    }
+    vlc<RAG, T, VEC>(c, x + c.i, v);
+    vlc<RAG, T, VEC>(c, bt + c.i, t);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const T xn = prox_data<T>(v[k] - tau * acc[k], t[k], tl, den, L1);
+      o[k] = xn + theta * (xn - v[k]);
+      v[k] = xn;
+    }
+    vs<RAG, T, VEC>(c.nval, x + c.i, v);
+    vs<RAG, T, VEC>(c.nval, xbar + c.i, o);
+    // w_a+ = w_a - tau (-p_a + D_a^T q_aa + sum_{b != a} D_b^T q_ab)
+#pragma unroll
+    for (int a = 0; a < NDIM; ++a) {
+      adj_dir<RAG, T, VEC>(a, q + a * G.n, G, c, own, t);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] = -pw[a][k] + t[k];
+#pragma unroll
+      for (int b = 0; b < NDIM; ++b) {
+        if (b == a) continue;
+        const int m = a < b ? sym_off<NDIM>(a, b) : sym_off<NDIM>(b, a);
+        adj_dir<RAG, T, VEC>(b, q + m * G.n, G, c, own, t);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] += t[k];
+      }
+      vlc<RAG, T, VEC>(c, w + a * G.n + c.i, v);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const T wn = v[k] - tau * acc[k];
+        o[k] = wn + theta * (wn - v[k]);
+        v[k] = wn;
+      }
+      vs<RAG, T, VEC>(c.nval, w + a * G.n + c.i, v);
+      vs<RAG, T, VEC>(c.nval, wbar + a * G.n + c.i, o);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+constexpr int kTgvFlags = NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_L1;
+
+struct Span {
+  const void *ptr;
+  int64_t bytes;
+};
+
+// a missing pointer, or two of the arrays overlap
+template <size_t N>
+bool spans_bad(const Span (&s)[N]) {
+  for (size_t i = 0; i < N; ++i) {
+    if (!s[i].ptr) return true;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(s[i].ptr), a1 = a0 + s[i].bytes;
+    for (size_t j = 0; j < i; ++j) {
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(s[j].ptr), b1 = b0 + s[j].bytes;
+      if (a0 < b1 && b0 < a1) return true;
+    }
+  }
+  return false;
+}
+
+inline bool positive(double v) { return isfinite(v) && v > 0.0; }
+
+// 0: go on; else the value to return (1 stands for "n = 0: return 0")
+inline int tgv_geometry(int ndim, int64_t nz, int64_t ny, int64_t nx, int flags) {
+  if (ndim < 1 || ndim > 3 || nz < 0 || ny < 0 || nx < 0 || (flags & ~kTgvFlags))
+    return NSOL_EINVAL;
+  if (nz == 0 || ny == 0 || nx == 0) return 1;
+  if (!geom_ok(ndim, nz, ny, nx)) return NSOL_EINVAL;
+  // more than 2^31 voxels (by division: the product itself may not fit 64 bits)
+  constexpr int64_t most = (int64_t)1 << 31;
+  if (nx > most || ny > most / nx || nz > most / (ny * nx)) return -2;
+  if (!stencil_grid_ok(nz, ny, nx)) return -2;
+  return 0;
+}
+
+template <typename T, typename F>
+int tgv_dispatch(int ndim, int64_t nz, int64_t ny, int64_t nx, bool aligned, F f) {
+  return dispatch_stencil<T>(nz, ny, nx, aligned, [&](auto vec, auto rows, auto rag) {
+    int rc;
+    switch (ndim) {
+      case 1: rc = f(vec, rows, rag, std::integral_constant<int, 1>()); break;
+      case 2: rc = f(vec, rows, rag, std::integral_constant<int, 2>()); break;
+      default: rc = f(vec, rows, rag, std::integral_constant<int, 3>()); break;
+    }
+    if (rc == 0) g_tgv_launches.fetch_add(1, std::memory_order_relaxed);
+    return rc;
+  });
+}
+
+template <typename T>
+int tgv_dual_impl(const T *xbar, const T *wbar, T *p, T *q, int ndim, int64_t nz,
+                  int64_t ny, int64_t nx, double wx, double wy, double wz, double sigma,
+                  double beta, int flags, void *stream) {
+  const int gr = tgv_geometry(ndim, nz, ny, nx, flags);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t nb = nz * ny * nx * (int64_t)sizeof(T), M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{xbar, nb}, {wbar, ndim * nb}, {p, ndim * nb}, {q, M * nb}};
+  if (spans_bad(spans) || !positive(sigma) || !positive(beta)) return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(xbar) && aligned16(wbar) && aligned16(p) && aligned16(q);
+  const hipStream_t st = as_stream(stream);
+  return tgv_dispatch<T>(ndim, nz, ny, nx, al, [&](auto vec, auto rows, auto rag, auto nd) {
+    constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+    constexpr int D = decltype(nd)::value;
+    constexpr bool RG = decltype(rag)::value;
+    const dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+    if (flags & NSOL_PD_REG_ISOTROPIC)
+      hipLaunchKernelGGL((k_tgv_dual<T, V, R, D, RG, true>), grid, dim3(kBlock), 0, st,
+                         xbar, wbar, p, q, G, (T)sigma, (T)beta);
+    else
+      hipLaunchKernelGGL((k_tgv_dual<T, V, R, D, RG, false>), grid, dim3(kBlock), 0, st,
+                         xbar, wbar, p, q, G, (T)sigma, (T)beta);
+    return launch_status();
+  });
+}
+
+template <typename T>
+int tgv_primal_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, const T *bt,
+                    int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+                    double wz, double tau, double tl, double theta, int flags,
+                    void *stream) {
+  const int gr = tgv_geometry(ndim, nz, ny, nx, flags);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t nb = nz * ny * nx * (int64_t)sizeof(T), M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{p, ndim * nb}, {q, M * nb},       {x, nb}, {xbar, nb},
+                        {w, ndim * nb}, {wbar, ndim * nb}, {bt, nb}};
+  if (spans_bad(spans) || !positive(tau) || !(isfinite(tl) && tl >= 0.0) ||
+      !isfinite(theta))
+    return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(p) && aligned16(q) && aligned16(x) && aligned16(xbar) &&
+                  aligned16(w) && aligned16(wbar) && aligned16(bt);
+  const hipStream_t st = as_stream(stream);
+  const T den = prox_den<T>(tl);
+  const bool l1 = (flags & NSOL_PD_DATA_L1) != 0;
+  return tgv_dispatch<T>(ndim, nz, ny, nx, al, [&](auto vec, auto rows, auto rag, auto nd) {
+    constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+    constexpr int D = decltype(nd)::value;
+    constexpr bool RG = decltype(rag)::value;
+    const dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+    // (the projection does not enter the primal step: one instantiation serves both)
+    if (l1)
+      hipLaunchKernelGGL((k_tgv_primal<T, V, R, D, RG, false, true>), grid, dim3(kBlock),
+                         0, st, p, q, x, xbar, w, wbar, bt, G, (T)tau, (T)tl, den,
+                         (T)theta);
+    else
+      hipLaunchKernelGGL((k_tgv_primal<T, V, R, D, RG, false, false>), grid, dim3(kBlock),
+                         0, st, p, q, x, xbar, w, wbar, bt, G, (T)tau, (T)tl, den,
+                         (T)theta);
+    return launch_status();
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int nsol_tgv_launches(void) { return g_tgv_launches.load(std::memory_order_relaxed); }
+
+#define NSOL_TGV_DEF(T, SUF)                                                              \
+  int nsol_tgv_dual_##SUF(const T *xbar, const T *wbar, T *p, T *q, int ndim, int64_t nz, \
+                          int64_t ny, int64_t nx, double wx, double wy, double wz,        \
+                          double sigma, double beta, int flags, void *s) {                \
+    return tgv_dual_impl<T>(xbar, wbar, p, q, ndim, nz, ny, nx, wx, wy, wz, sigma, beta,  \
+                            flags, s);                                                    \
+  }                                                                                       \
+  int nsol_tgv_primal_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,         \
+                            const T *bt, int ndim, int64_t nz, int64_t ny, int64_t nx,    \
+                            double wx, double wy, double wz, double tau, double tl,       \
+                            double theta, int flags, void *s) {                           \
+    return tgv_primal_impl<T>(p, q, x, xbar, w, wbar, bt, ndim, nz, ny, nx, wx, wy, wz,   \
+                              tau, tl, theta, flags, s);                                  \
+  }
+
+NSOL_TGV_DEF(float, f32)
+NSOL_TGV_DEF(double, f64)
+#undef NSOL_TGV_DEF
+
+}  // extern "C"

@@ -1839,6 +1839,60 @@ def pdl_iter(xbar_in, xbar_out, x, g, p_in, p_out, shape, w, sigma, hden, tau, t
     return True
 
 
+# --------------------------- second-order TGV (nsol_tgv.hip, tgv_numpy.py) ----
+def tgv_launches():
+    """Successful launches of k_tgv_dual / k_tgv_primal so far (for tests and tools)."""
+    return int(_lib.load().nsol_tgv_launches())
+
+
+def _tgv_operands(shape, x_like, vectors, tensors):
+    """Checks the stacks of a TGV call: every tensor of `vectors` holds ndim * n values
+    and every one of `tensors` M * n, in the element type of x_like (n values)."""
+    ndim, nz, ny, nx = dims3(shape)
+    n = nz * ny * nx
+    for group, size in ((vectors, ndim * n), (tensors, ndim * (ndim + 1) // 2 * n),
+                        ((x_like,), n)):
+        for t in group:
+            if _chk(t).dtype != x_like.dtype or t.numel() != size:
+                raise ValueError("operand mismatch: %s[%d] where %s[%d] is expected for "
+                                 "shape %r" % (str(t.dtype), t.numel(), str(x_like.dtype),
+                                               size, tuple(shape)))
+    return ndim, nz, ny, nx
+
+
+def tgv_dual(xbar, wbar, p, q, shape, w, sigma, beta, flags=0):
+    """The dual half of a TGV iteration, p and q in place: p_a <- P_1(p_a + sigma (D_a
+    xbar - wbar_a)), q <- P_beta(q + sigma E wbar).  flags: PD_REG_ISOTROPIC.  Returns
+    False when the library declined the geometry (nothing was launched).  Does not
+    synchronise."""
+    ndim, nz, ny, nx = _tgv_operands(shape, xbar, (wbar, p), (q,))
+    rc = _fn("tgv_dual", xbar)(
+        _p(xbar), _p(wbar), _p(p), _p(q), ndim, nz, ny, nx, w[0], w[1], w[2],
+        float(sigma), float(beta), int(flags), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_dual")
+    _wrote(p, q)
+    return True
+
+
+def tgv_primal(p, q, x, xbar, w_field, wbar, bt, shape, w, tau, tl, theta=1., flags=0):
+    """The primal half, x, w_field, xbar and wbar in place: x <- prox_{tl D}(x - tau
+    grad^T p), w_a <- w_a - tau (-p_a + D_a^T q_aa + sum_{b != a} D_b^T q_ab), the bars
+    extrapolated by theta.  flags: PD_DATA_L1.  Returns False when the library declined
+    the geometry (nothing was launched).  Does not synchronise."""
+    _same(x, xbar, bt)
+    ndim, nz, ny, nx = _tgv_operands(shape, x, (p, w_field, wbar), (q,))
+    rc = _fn("tgv_primal", x)(
+        _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(bt), ndim, nz, ny, nx,
+        w[0], w[1], w[2], float(tau), float(tl), float(theta), int(flags), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_primal")
+    _wrote(x, xbar, w_field, wbar)
+    return True
+
+
 # ------------------------------ the same, member-stacked (nsol_pdls.hip) ----
 # An alpha sweep on one observation or a stack of images of one shape
 # (nsol_amd/linear_stack.py).  A member's state is x, two xbar, q, g = A^T q and two p
