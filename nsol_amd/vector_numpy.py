@@ -1,0 +1,248 @@
+"""NumPy restatement of the generic vector kernels of csrc/nsol_ops.hip (reached through
+nsol_amd/ops.py): the written specification of their arithmetic and the reference of
+tests/test_vector_ops_host.py and tests/test_vector_ops_gpu.py.
+
+Every function works in float64 and performs the kernel's operations in the kernel's
+order, so that a float64 kernel (built without FMA contraction) yields the same bits.
+`dtype` names the kernel's element type where the kernel rounds a scalar to it or uses
+a reciprocal formed on the host: with dtype=np.float32 the scalars are the float32
+values the kernel sees, held in float64, and the arithmetic stays float64 -- the
+reference a float32 kernel is measured against, on float32-rounded inputs.
+
+Sums are math.fsum of the terms the kernel adds (the kernels accumulate in double);
+the `*_terms` functions hand out the terms themselves so that a test can bound the
+summation error by their magnitudes.
+
+Stencils: x is the LAST array axis, component a of a gradient field acts on array axis
+ndim - 1 - a, w = (wx, wy, wz) are the inverse spacings 1/h as the C ABI takes them;
+everything beyond the boundary is zero (the library's one boundary convention).
+"""
+import math
+
+import numpy as np
+
+LOSSES = ("linear", "soft_l1", "huber", "cauchy", "arctan")
+HUBER_GAMMA = 1.345            # loss_functions.py's default, fixed in loss_cost_grad
+
+
+def as_scalar(v, dtype):
+    """The scalar v as the kernel of element type dtype sees it: (T)v, in float64."""
+    with np.errstate(over="ignore"):
+        return float(np.dtype(dtype).type(v))
+
+
+def _f(x):
+    return np.asarray(x, dtype=np.float64)
+
+
+# ------------------------------------------------------------------ element-wise
+def lincomb2(a, x, b, y, dtype=np.float64):
+    return as_scalar(a, dtype) * _f(x) + as_scalar(b, dtype) * _f(y)
+
+
+def lincomb3(a, x, b, y, c, z, dtype=np.float64):
+    return (as_scalar(a, dtype) * _f(x) + as_scalar(b, dtype) * _f(y)
+            + as_scalar(c, dtype) * _f(z))
+
+
+def scale(x, a, divide=False, dtype=np.float64):
+    return _f(x) / as_scalar(a, dtype) if divide else _f(x) * as_scalar(a, dtype)
+
+
+def clip(x, lo, hi, dtype=np.float64):
+    """v < lo ? lo : v, then v > hi ? hi : v (bounds of +-inf stay +-inf)."""
+    lo, hi = as_scalar(lo, dtype), as_scalar(hi, dtype)
+    v = _f(x)
+    v = np.where(v < lo, lo, v)
+    return np.where(v > hi, hi, v)
+
+
+def extrapolate(a, b, theta, dtype=np.float64):
+    a = _f(a)
+    return a + as_scalar(theta, dtype) * (a - _f(b))
+
+
+def prox_ell1(u, bt, tau, dtype=np.float64):
+    """bt + max(|u - bt| - tau, 0) * sign(u - bt)."""
+    u, bt = _f(u), _f(bt)
+    d = u - bt
+    return bt + np.maximum(np.abs(d) - as_scalar(tau, dtype), 0.) * np.sign(d)
+
+
+def prox_ell2(u, bt, tau, dtype=np.float64):
+    """float64: (u + tau bt) / (1 + tau); float32: (u + tau bt) * float32(1 / (1 + tau)),
+    the reciprocal formed in double on the host."""
+    num = _f(u) + as_scalar(tau, dtype) * _f(bt)
+    if np.dtype(dtype) == np.float64:
+        return num / (1.0 + float(tau))
+    return num * as_scalar(1.0 / (1.0 + float(tau)), dtype)
+
+
+def prox_dual_clamp(x, den=1.0, dtype=np.float64):
+    """q / max(1, |q|) = min(max(q, -1), 1) with q = x / den; float32 multiplies by
+    float32(1 / den)."""
+    if np.dtype(dtype) == np.float64:
+        q = _f(x) / float(den)
+    else:
+        q = _f(x) * as_scalar(1.0 / float(den), dtype)
+    return np.minimum(np.maximum(q, -1.), 1.)
+
+
+def _norm2(t, ndim):
+    """t_0^2 + t_1^2 + ... added in this order; t: (ndim, m)."""
+    t = _f(t).reshape(ndim, -1)
+    n2 = t[0] * t[0]
+    for a in range(1, ndim):
+        n2 = n2 + t[a] * t[a]
+    return t, n2
+
+
+def vector_shrink(t, ndim, thr, dtype=np.float64):
+    """Isotropic soft threshold of the ndim-vectors of a stacked field (ndim blocks):
+    max(|nrm| - thr, 0) * sign(nrm) * t_a / nrm where nrm > thr, else 0 -- also where
+    nrm = 0 = thr (never 0 / 0)."""
+    shape = np.shape(t)
+    t, n2 = _norm2(t, ndim)
+    thr = as_scalar(thr, dtype)
+    nrm = np.sqrt(n2)
+    on = nrm > thr
+    mag = np.maximum(np.abs(nrm) - thr, 0.) * np.sign(nrm)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = np.where(on[None], mag[None] * t / nrm[None], 0.)
+    return v.reshape(shape)
+
+
+# ------------------------------------------------------------------- robust losses
+def loss_eval(name, f2, f_scale=1.0, gamma=HUBER_GAMMA, dtype=np.float64):
+    """(rho, rho') of loss_functions.py at f2 = r^2 with z = f2 / f_scale^2:
+    linear   f2                           1
+    soft_l1  2 (sqrt(1 + z) - 1) s2       1 / sqrt(1 + z)
+    huber    z s2 | (2 g sqrt(z) - g^2) s2      1 | g / sqrt(z)      (z < g^2 | else)
+    cauchy   log1p(z) s2                  1 / (1 + z)
+    arctan   atan(z) s2                   1 / (1 + z^2)"""
+    f2 = _f(f2)
+    s2 = as_scalar(float(f_scale) * float(f_scale), dtype)
+    z = f2 / s2
+    if name == "linear":
+        return f2.copy(), np.ones_like(f2)
+    if name == "soft_l1":
+        q = np.sqrt(1. + z)
+        return 2. * (q - 1.) * s2, 1. / q
+    if name == "huber":
+        gm = as_scalar(gamma, dtype)
+        g2 = gm * gm
+        q = np.sqrt(z)
+        with np.errstate(divide="ignore"):
+            return (np.where(z < g2, z * s2, (2. * gm * q - g2) * s2),
+                    np.where(z < g2, 1., gm / q))
+    if name == "cauchy":
+        return np.log1p(z) * s2, 1. / (1. + z)
+    if name == "arctan":
+        return np.arctan(z) * s2, 1. / (1. + z * z)
+    raise ValueError(name)
+
+
+def loss_terms(r, name, f_scale=1.0, minus=None, dtype=np.float64):
+    """(rho_i, g_i) of loss_cost_grad: the residual r (1 * r + (-1) * minus when given),
+    rho(r^2) and rho'(r^2) * r, Huber's gamma at its default."""
+    rv = _f(r) if minus is None else 1. * _f(r) + (-1.) * _f(minus)
+    rho, drho = loss_eval(name, rv * rv, f_scale, HUBER_GAMMA, dtype)
+    return rho, drho * rv
+
+
+def loss_cost_grad(r, name, f_scale=1.0, minus=None, dtype=np.float64):
+    """(0.5 * sum rho, gradient)."""
+    rho, g = loss_terms(r, name, f_scale, minus, dtype)
+    return 0.5 * math.fsum(rho), g
+
+
+# ---------------------------------------------------------------------- reductions
+def dot_terms(x, y):
+    return _f(x).reshape(-1) * _f(y).reshape(-1)
+
+
+def dot(x, y):
+    return math.fsum(dot_terms(x, y))
+
+
+def norm2(x):
+    return math.sqrt(dot(x, x))
+
+
+def vector_norm_terms(t, ndim, mode=0, gamma=0.05, dtype=np.float64):
+    """Per voxel: mode 0 sqrt(sum_a t_a^2); mode 1 huber(sum_a t_a^2; gamma) / (2 gamma)
+    with f_scale = 1 (prior_measures.py:27-52)."""
+    _, n2 = _norm2(t, ndim)
+    if mode == 0:
+        return np.sqrt(n2)
+    if mode != 1:
+        raise ValueError("mode must be 0 or 1")
+    rho, _ = loss_eval("huber", n2, 1.0, gamma, dtype)
+    return rho / (2. * as_scalar(gamma, dtype))
+
+
+def vector_norm_sum(t, ndim, mode=0, gamma=0.05, dtype=np.float64):
+    return math.fsum(vector_norm_terms(t, ndim, mode, gamma, dtype))
+
+
+def pair_terms(x, y, mx=0.0, my=0.0):
+    """The terms of the eight statistics of one (x, y) pair, a row each:
+    (x-mx)(y-my), (x-mx)^2, (y-my)^2, |x-y|, (x-y)^2, y, x, y.  Row 5 is reduced by a
+    maximum, every other row by a sum."""
+    x, y = _f(x).reshape(-1), _f(y).reshape(-1)
+    dx, dy, d = x - float(mx), y - float(my), x - y
+    return np.stack([dx * dy, dx * dx, dy * dy, np.abs(d), d * d, y, x, y])
+
+
+def pair_stats(x, y, mx=0.0, my=0.0):
+    t = pair_terms(x, y, mx, my)
+    return np.array([float(np.max(t[k])) if k == 5 else math.fsum(t[k])
+                     for k in range(8)])
+
+
+# ------------------------------------------------------------------------ stencils
+def shifted(u, axis, forward):
+    """u moved by one along axis: forward -> the neighbour at +1, else at -1; zero
+    where there is none."""
+    nb = np.zeros_like(u)
+    src = [slice(None)] * u.ndim
+    dst = [slice(None)] * u.ndim
+    if forward:
+        src[axis], dst[axis] = slice(1, None), slice(0, -1)
+    else:
+        src[axis], dst[axis] = slice(0, -1), slice(1, None)
+    nb[tuple(dst)] = u[tuple(src)]
+    return nb
+
+
+def diff_axis(x, direction, adjoint, w, dtype=np.float64):
+    """Difference along direction 0 (x, the last axis), 1 (y) or 2 (z) of an array of
+    up to three axes: forward nb * w + x * (-w) with nb the neighbour at +1, adjoint
+    x * (-w) + nb * w with nb the neighbour at -1."""
+    x = _f(x)
+    w = as_scalar(w, dtype)
+    axis = x.ndim - 1 - direction
+    if adjoint:
+        return x * (-w) + shifted(x, axis, False) * w
+    return shifted(x, axis, True) * w + x * (-w)
+
+
+def grad(x, w=(1., 1., 1.), dtype=np.float64):
+    """Forward differences of every axis, stacked on a new first axis (component 0 = x)."""
+    x = _f(x)
+    return np.stack([diff_axis(x, a, False, w[a], dtype) for a in range(x.ndim)])
+
+
+def grad_adj(p, w=(1., 1., 1.), dtype=np.float64):
+    """The exact transpose of grad: p of shape (d,) + volume; the components are added
+    x, y, z."""
+    p = _f(p)
+    acc = diff_axis(p[0], 0, True, w[0], dtype)
+    for a in range(1, p.shape[0]):
+        acc = acc + diff_axis(p[a], a, True, w[a], dtype)
+    return acc
+
+
+def grad_adj_axpy(p, x, tau, w=(1., 1., 1.), dtype=np.float64):
+    """x - tau * grad_adj(p)."""
+    return _f(x) - as_scalar(tau, dtype) * grad_adj(p, w, dtype)

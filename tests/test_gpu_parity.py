@@ -29,6 +29,9 @@ def _lo(dim, spacing=None):
 
 
 # ---------------------------------------------------------------- operators
+# (the generic kernels used as "the parts" below -- lincomb, scale, clip, the proxes,
+# dot, the losses, shrink, grad and its adjoint -- are held to a float64 reference of
+# their own, at their edge lengths and off alignment, in test_vector_ops_gpu.py)
 @pytest.mark.parametrize("k", ["1d", "2d", "3d"])
 @pytest.mark.parametrize("tag", ["unit", "sp"])
 def test_grad_ops_match_reference_goldens(nsol, golden, k, tag):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from device_arena import Arena
 from nsol_amd import tgv_numpy as tg
 
 pytestmark = pytest.mark.gpu
@@ -17,8 +18,6 @@ F32_TOL = 1e-5      # the project's standing gate
 BOTH = [np.float64, np.float32]
 SPACING = (0.8, 1.3, 2.0)          # spacing[0] belongs to the last array axis
 BETA, SIGMA, TAU, TL, THETA = 1.7, 0.3, 0.4, 0.6, 0.9
-GUARD = 64                          # elements before and after every array
-SENTINEL = 12345.0
 ISO, L1 = 4, 2                      # NSOL_PD_REG_ISOTROPIC, NSOL_PD_DATA_L1
 
 # first / last index on every axis, extents of 1, rows shorter than a vector, ragged and
@@ -101,46 +100,6 @@ def _want_primal(shape, dtype, l1):
     return tg.primal_step(s["p"], s["q"], s["x"], s["w"], s["bt"], c(TAU), c(TL),
                           c(THETA), _rounded_spacing(shape, dtype),
                           "ell1" if l1 else "ell2")
-
-
-class Arena(object):
-    """Device arrays inside one allocation, each with GUARD sentinel elements before and
-    after it.  offset: elements by which every array is shifted off 16-byte alignment.
-    last: the name of the array that ends exactly where the allocation ends."""
-
-    def __init__(self, arrays, dtype, offset=0, last=None):
-        import torch
-        from nsol_amd.device import to_device
-        names = [k for k in arrays if k != last] + ([last] if last else [])
-        pos, at = GUARD + offset, {}
-        for k in names:
-            at[k] = pos
-            size = arrays[k].size
-            pos += size + GUARD
-            pos += (-pos) % 4 + offset             # starts: 16-byte aligned + offset
-        total = at[last] + arrays[last].size if last else pos
-        host = np.full(total, SENTINEL, dtype=dtype)
-        self.mask = np.ones(total, dtype=bool)     # True: guard
-        for k in names:
-            host[at[k]:at[k] + arrays[k].size] = arrays[k].reshape(-1)
-            self.mask[at[k]:at[k] + arrays[k].size] = False
-        self.dtype, self.at, self.sizes = dtype, at, {k: arrays[k].size for k in names}
-        self.buf = to_device(host, dtype)
-        assert self.buf.data_ptr() % 16 == 0
-        self.t = {k: self.buf[at[k]:at[k] + self.sizes[k]] for k in names}
-        torch.cuda.synchronize()
-
-    def ptr(self, k):
-        return self.t[k].data_ptr()
-
-    def get(self, k, shape):
-        from nsol_amd.device import to_numpy
-        return to_numpy(self.t[k], self.dtype).astype(np.float64).reshape(shape)
-
-    def guards_intact(self):
-        from nsol_amd.device import to_numpy
-        host = to_numpy(self.buf, self.dtype)
-        return bool(np.all(host[self.mask] == self.dtype(SENTINEL)))
 
 
 def _call_dual(shape, dtype, flags, ar, sigma=SIGMA, beta=BETA):
