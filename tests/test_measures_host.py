@@ -12,12 +12,13 @@ from scipy.ndimage import uniform_filter
 K1, K2 = 0.01, 0.03
 
 
-def ssim_restated(x, y, win=7, data_range=2.0):
-    """skimage compare_ssim (box window, sample covariance) as published."""
+def ssim_restated(x, y, win=7, data_range=2.0, sample_cov=True):
+    """skimage compare_ssim (box window, sample covariance unless sample_cov is false) as
+    published."""
     X = np.asarray(x, np.float64)
     Y = np.asarray(y, np.float64)
     npix = win ** X.ndim
-    cov_norm = npix / (npix - 1.0)
+    cov_norm = npix / (npix - 1.0) if sample_cov else 1.0
     ux = uniform_filter(X, size=win)
     uy = uniform_filter(Y, size=win)
     uxx = uniform_filter(X * X, size=win)
@@ -35,7 +36,7 @@ def ssim_restated(x, y, win=7, data_range=2.0):
     return S[tuple(slice(pad, n - pad) for n in S.shape)].mean()
 
 
-def ssim_direct_1d(x, y, win=7, data_range=2.0):
+def ssim_direct_1d(x, y, win=7, data_range=2.0, sample_cov=True):
     """The 1-D form with every window summed on its own (no running sum).
     SciPy's uniform_filter1d carries one running sum along the whole line;
     on a flattened volume that sum drifts (5e-9 on the mean SSIM of the
@@ -43,7 +44,7 @@ def ssim_direct_1d(x, y, win=7, data_range=2.0):
     from numpy.lib.stride_tricks import sliding_window_view
     X = np.asarray(x, np.float64)
     Y = np.asarray(y, np.float64)
-    cov_norm = win / (win - 1.0)
+    cov_norm = win / (win - 1.0) if sample_cov else 1.0
 
     def box(a):
         return sliding_window_view(a, win).sum(axis=-1) / win
@@ -58,11 +59,12 @@ def ssim_direct_1d(x, y, win=7, data_range=2.0):
     return S.mean()
 
 
-def ssim_brute(x, y, win=7, data_range=2.0):
+def ssim_brute(x, y, win=7, data_range=2.0, sample_cov=True):
     """One window at a time, straight from the definition."""
     X = np.asarray(x, np.float64)
     Y = np.asarray(y, np.float64)
     npix = win ** X.ndim
+    div = npix - 1 if sample_cov else npix
     C1 = (K1 * data_range) ** 2
     C2 = (K2 * data_range) ** 2
     vals = []
@@ -70,9 +72,9 @@ def ssim_brute(x, y, win=7, data_range=2.0):
         sl = tuple(slice(c, c + win) for c in corner)
         a, b = X[sl].ravel(), Y[sl].ravel()
         mx, my = a.mean(), b.mean()
-        vx = ((a - mx) ** 2).sum() / (npix - 1)
-        vy = ((b - my) ** 2).sum() / (npix - 1)
-        vxy = ((a - mx) * (b - my)).sum() / (npix - 1)
+        vx = ((a - mx) ** 2).sum() / div
+        vy = ((b - my) ** 2).sum() / div
+        vxy = ((a - mx) * (b - my)).sum() / div
         vals.append(((2 * mx * my + C1) * (2 * vxy + C2)) /
                     ((mx * mx + my * my + C1) * (vx + vy + C2)))
     return float(np.mean(vals))
@@ -89,6 +91,20 @@ def test_restated_ssim_matches_brute_force_windows(shape):
     assert abs(ssim_restated(x, x) - 1.0) < 1e-13
     if x.ndim == 1:
         assert abs(ssim_direct_1d(x, y) - ssim_brute(x, y)) < 1e-13
+    # every window the kernel is built for (7: above), on extents grown with the window
+    for win in (3, 5, 9, 11):
+        grown = tuple(s + max(0, win - 7) for s in shape)
+        rng = np.random.default_rng(sum(grown) + win)
+        x = rng.standard_normal(grown)
+        y = 0.7 * x + 0.3 * rng.standard_normal(grown)
+        for dr in (2.0, 255.0):
+            want = ssim_brute(x, y, win, dr)
+            assert abs(ssim_restated(x, y, win, dr) - want) < 1e-13, (win, dr)
+            if x.ndim == 1:
+                assert abs(ssim_direct_1d(x, y, win, dr) - want) < 1e-13, (win, dr)
+        assert abs(ssim_restated(x, y, win, sample_cov=False) -
+                   ssim_brute(x, y, win, sample_cov=False)) < 1e-13, win
+        assert abs(ssim_restated(x, x, win) - 1.0) < 1e-13
 
 
 def _edge_cases():
