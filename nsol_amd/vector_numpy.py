@@ -13,6 +13,11 @@ Sums are math.fsum of the terms the kernel adds (the kernels accumulate in doubl
 the `*_terms` functions hand out the terms themselves so that a test can bound the
 summation error by their magnitudes.
 
+The last section restates one Chambolle-Pock iteration of csrc/nsol_pd.hip and
+csrc/nsol_pdi.hip (k_dual_step, k_primal_step, k_pd_fused and their isotropic twins) from
+the functions above: the reference of tests/test_pd_steps_host.py and
+tests/test_pd_steps_gpu.py.
+
 Stencils: x is the LAST array axis, component a of a gradient field acts on array axis
 ndim - 1 - a, w = (wx, wy, wz) are the inverse spacings 1/h as the C ABI takes them;
 everything beyond the boundary is zero (the library's one boundary convention).
@@ -246,3 +251,60 @@ def grad_adj(p, w=(1., 1., 1.), dtype=np.float64):
 def grad_adj_axpy(p, x, tau, w=(1., 1., 1.), dtype=np.float64):
     """x - tau * grad_adj(p)."""
     return _f(x) - as_scalar(tau, dtype) * grad_adj(p, w, dtype)
+
+
+# ------------------------------------------- one primal-dual iteration (nsol_pd*.hip)
+def project_iso(q, dimension, den=None):
+    """q: `dimension` stacked blocks.  q_a <- q_a / den (Huber only), then
+    s = ((q0 q0) + q1 q1) + q2 q2, m = max(1, sqrt(s)), p_a = q_a / m: dual_project of
+    csrc/nsol_pd_iso_body.hpp.  Works in q's own precision."""
+    if den is not None:
+        q = q / den
+    parts = np.array_split(q, dimension)
+    s = parts[0] * parts[0]
+    for a in range(1, dimension):
+        s = s + parts[a] * parts[a]
+    m = np.maximum(1, np.sqrt(s))
+    return np.concatenate([pa / m for pa in parts])
+
+
+def pd_dual_q(xbar, p, sigma, w, dtype=np.float64):
+    """q_a = p_a + sigma * (hi * w_a + lo * (-w_a)), stacked on a new first axis: the
+    argument of the dual prox (dual_update / dual_q).  p = None: zero."""
+    xbar = _f(xbar)
+    sg = as_scalar(sigma, dtype)
+    return np.stack([(0. if p is None else _f(p)[a])
+                     + sg * diff_axis(xbar, a, False, w[a], dtype)
+                     for a in range(xbar.ndim)])
+
+
+def pd_dual_step(xbar, p, sigma, hden, w, dtype=np.float64, iso=False):
+    """The new dual field, shape (ndim,) + volume.  Huber (hden != 1): float64 q / hden,
+    float32 q * float32(1 / hden); then min(max(q, -1), 1) per component, or (iso) the
+    projection of the voxel's vector onto the unit ball, project_iso."""
+    q = pd_dual_q(xbar, p, sigma, w, dtype)
+    if not iso:
+        return prox_dual_clamp(q, hden, dtype)
+    den = None
+    if float(hden) != 1.0:
+        if np.dtype(dtype) == np.float64:
+            den = float(hden)
+        else:
+            q = q * as_scalar(1.0 / float(hden), dtype)
+    return project_iso(q.reshape(-1), q.shape[0], den).reshape(q.shape)
+
+
+def pd_primal_step(p, x, bt, tau, tl, theta, w, l1, dtype=np.float64):
+    """(x_new, xbar_new): kt = grad_adj(p) (components added x, y, z), u = x - tau * kt,
+    x_new = prox_ell1 / prox_ell2 (u, bt, tl), xbar_new = x_new + theta * (x_new - x)."""
+    u = grad_adj_axpy(p, x, tau, w, dtype)
+    x_new = prox_ell1(u, bt, tl, dtype) if l1 else prox_ell2(u, bt, tl, dtype)
+    return x_new, extrapolate(x_new, x, theta, dtype)
+
+
+def pd_iteration(xbar, x, bt, p, sigma, hden, tau, tl, theta, w, l1, dtype=np.float64,
+                 iso=False):
+    """(p_new, x_new, xbar_new) of one iteration: pd_dual_step, then pd_primal_step on
+    its result."""
+    p_new = pd_dual_step(xbar, p, sigma, hden, w, dtype, iso)
+    return (p_new,) + pd_primal_step(p_new, x, bt, tau, tl, theta, w, l1, dtype)

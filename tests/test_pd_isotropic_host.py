@@ -8,24 +8,14 @@ import re
 import numpy as np
 import pytest
 
+# the projection itself is stated once, beside the rest of the kernels' arithmetic
+# (the other test modules take it from here)
+from nsol_amd.vector_numpy import project_iso    # noqa: F401
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 # ------------------------------------------------------------------ yardstick
-def project_iso(q, dimension, den=None):
-    """q: `dimension` stacked blocks.  q_a <- q_a / den (Huber only), then
-    s = ((q0 q0) + q1 q1) + q2 q2, m = max(1, sqrt(s)), p_a = q_a / m.  Works
-    in q's own precision."""
-    if den is not None:
-        q = q / den
-    parts = np.array_split(q, dimension)
-    s = parts[0] * parts[0]
-    for a in range(1, dimension):
-        s = s + parts[a] * parts[a]
-    m = np.maximum(1, np.sqrt(s))
-    return np.concatenate([pa / m for pa in parts])
-
-
 def pd_iso_denoise(b, shape, reg="TV", data="L2", alpha=0.03, iterations=10,
                    L2=8., alg_type="ALG2", x_scale=None, spacing=None,
                    gamma=0.05, scaled=False):
