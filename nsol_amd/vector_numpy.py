@@ -16,7 +16,11 @@ summation error by their magnitudes.
 The last section restates one Chambolle-Pock iteration of csrc/nsol_pd.hip and
 csrc/nsol_pdi.hip (k_dual_step, k_primal_step, k_pd_fused and their isotropic twins) from
 the functions above: the reference of tests/test_pd_steps_host.py and
-tests/test_pd_steps_gpu.py.
+tests/test_pd_steps_gpu.py; then the same iteration with the tile bodies' WGT switch (the
+weighted data prox of csrc/nsol_pd_weighted.hpp: k_pd_w, k_prox_w) and LIN switch (the
+explicit step into a box: k_pd_lin, k_pdl_stack) and the element-wise update of the linear
+data term's dual variable (k_pdl_dual_data): the reference of
+tests/test_pd_weighted_linear_host.py and tests/test_pd_weighted_linear_gpu.py.
 
 Stencils: x is the LAST array axis, component a of a gradient field acts on array axis
 ndim - 1 - a, w = (wx, wy, wz) are the inverse spacings 1/h as the C ABI takes them;
@@ -308,3 +312,103 @@ def pd_iteration(xbar, x, bt, p, sigma, hden, tau, tl, theta, w, l1, dtype=np.fl
     its result."""
     p_new = pd_dual_step(xbar, p, sigma, hden, w, dtype, iso)
     return (p_new,) + pd_primal_step(p_new, x, bt, tau, tl, theta, w, l1, dtype)
+
+
+# ------------------------- the weighted (WGT) and the linear (LIN) form of the iteration
+def prox_data_w(u, bt, w, tl, l1, dtype=np.float64):
+    """prox_data_w of csrc/nsol_pd_weighted.hpp: t = tl * w, then (u + t bt) / (1 + t) --
+    a division in either type -- or (l1) bt + max(|u - bt| - t, 0) sign(u - bt); u ITSELF
+    where w == 0, whatever bt holds there (a select on w, not a product with 0).  Works in
+    the arrays' own precision, as project_iso does: float64 arrays give the reference."""
+    u, bt, w = np.asarray(u), np.asarray(bt), np.asarray(w)
+    t = as_scalar(tl, dtype) * w
+    with np.errstate(invalid="ignore", over="ignore"):
+        if l1:
+            d = u - bt
+            r = bt + np.maximum(np.abs(d) - t, 0.) * np.sign(d)
+        else:
+            r = (u + t * bt) / (1. + t)
+    return np.where(w == 0, u, r)
+
+
+def box_in(lo, hi, dtype=np.float64):
+    """(lo, hi) as the linear kernels see the caller's float64 box (box_in of
+    csrc/nsol_pd_launch.hpp): float64 as given; float32 rounded to nearest and then moved
+    one spacing INWARD where that left the box -- except lo == hi, and a box that holds no
+    float32 at all, which stay as rounded to nearest."""
+    lo, hi = float(lo), float(hi)
+    if np.dtype(dtype) == np.float64:
+        return lo, hi
+    with np.errstate(over="ignore"):
+        l, h = np.float32(lo), np.float32(hi)
+    if lo != hi:
+        li, hj = l, h
+        if float(li) < lo:
+            li = np.nextafter(li, np.float32(np.inf))
+        if float(hj) > hi:
+            hj = np.nextafter(hj, np.float32(-np.inf))
+        if li <= hj:
+            l, h = li, hj
+    return float(l), float(h)
+
+
+def pd_lin_step(x, kt, g, tau, lo, hi, dtype=np.float64):
+    """lin_step of csrc/nsol_pd_fused_body.hpp: u = x - tau * (kt + g), then
+    c = u < lo ? lo : u and c > hi ? hi : c on the box box_in(lo, hi): the selects as the
+    kernel makes them (u == lo keeps u, so -0.0 stays -0.0 on lo = 0)."""
+    lo, hi = box_in(lo, hi, dtype)
+    u = _f(x) - as_scalar(tau, dtype) * (_f(kt) + _f(g))
+    cl = np.where(u < lo, lo, u)
+    return np.where(cl > hi, hi, cl)
+
+
+def pd_weighted_primal_step(p, x, bt, wt, tau, tl, theta, w, l1, dtype=np.float64):
+    """(x_new, xbar_new) of k_pd_w: pd_primal_step with prox_data_w as the data prox."""
+    u = grad_adj_axpy(p, x, tau, w, dtype)
+    x_new = prox_data_w(u, bt, wt, tl, l1, dtype)
+    return x_new, extrapolate(x_new, x, theta, dtype)
+
+
+def pd_lin_primal_step(p, x, g, tau, theta, lo, hi, w, dtype=np.float64):
+    """(x_new, xbar_new) of k_pd_lin: kt = grad_adj(p), x_new = pd_lin_step(x, kt, g)."""
+    x_new = pd_lin_step(x, grad_adj(p, w, dtype), g, tau, lo, hi, dtype)
+    return x_new, extrapolate(x_new, x, theta, dtype)
+
+
+def pd_weighted_iteration(xbar, x, bt, wt, p, sigma, hden, tau, tl, theta, w, l1,
+                          dtype=np.float64, iso=False):
+    """(p_new, x_new, xbar_new): pd_dual_step, then pd_weighted_primal_step on its result."""
+    p_new = pd_dual_step(xbar, p, sigma, hden, w, dtype, iso)
+    return (p_new,) + pd_weighted_primal_step(p_new, x, bt, wt, tau, tl, theta, w, l1,
+                                              dtype)
+
+
+def pd_lin_iteration(xbar, x, g, p, sigma, hden, tau, theta, lo, hi, w, dtype=np.float64,
+                     iso=False):
+    """(p_new, x_new, xbar_new): pd_dual_step, then pd_lin_primal_step on its result."""
+    p_new = pd_dual_step(xbar, p, sigma, hden, w, dtype, iso)
+    return (p_new,) + pd_lin_primal_step(p_new, x, g, tau, theta, lo, hi, w, dtype)
+
+
+def pdl_dual_prox(v, c, sigma, w, l1):
+    """The prox of the data term's conjugate as k_pdl_dual_data writes it: (v c) / (c + sigma)
+    or (l1) r = v < -c ? -c : v, then r > c ? c : r; +0 where w == 0, whatever v holds.  Works
+    in the arrays' own precision."""
+    v, c, w = np.asarray(v), np.asarray(c), np.asarray(w)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if l1:
+            r = np.where(v < -c, -c, v)
+            r = np.where(r > c, c, r)
+        else:
+            r = (v * c) / (c + sigma)
+    return np.where(w == 0, np.zeros_like(r), r)
+
+
+def pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1, dtype=np.float64):
+    """k_pdl_dual_data of csrc/nsol_pdl.hip: v = q + sigma * (t - bt), or q - sigma * bt
+    with t None; c = lmbda * w (w = 1 with wt None); pdl_dual_prox."""
+    sg, lm = as_scalar(sigma, dtype), as_scalar(lmbda, dtype)
+    w = np.ones_like(_f(q)) if wt is None else _f(wt)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = _f(q) + sg * (_f(t) - _f(bt)) if t is not None else _f(q) - sg * _f(bt)
+    return pdl_dual_prox(v, lm * w, sg, w, l1)

@@ -41,6 +41,39 @@ primal step (k_primal_step, nsol_pd.hip; the same lines in both tile bodies):
 The dual and the primal step are bounded separately: the primal outputs of any call are
 compared with pd_primal_step applied to the call's OWN p_out, so that no dual error is
 propagated into the primal bound.
+
+The WGT and LIN forms of the two tile bodies (k_pd_w, nsol_pdw.hip; k_pd_lin, nsol_pdl.hip;
+k_pdl_stack, nsol_pdls.hip) and the element-wise kernels beside them, counted from the
+source in the same way before any of them ran against these gates.  The dual half is the
+plain kernels'.  kt (4 d - 1) and S_u are as above:
+LIN (lin_step, nsol_pd_fused_body.hpp):
+    u = x - tau * (kt + g)                      kt + g, tau *, x -             : 3
+    c = u < lo ? lo : u;  c > hi ? hi : c       selects: exact, 1-Lipschitz in u
+    x_new:  R = 4 d + 2,  S = |x| + |tau| (sum_a (|p_a| + |p_a[i - e_a]|) |w_a| + |g|)
+  on the box the kernel itself uses (box_in), so the clip adds nothing.  Where u lies outside
+  the box by more than R u S the kernel's u lies outside it too and x_new is the bound
+  itself: R = 0 there, the bits of box_in's lo or hi.  A clipped x_new may be larger than S
+  (u = -0.1, lo = 0.5), so xbar_new's S takes max(S, |x_new|) for S_x.
+WGT (prox_data_w, nsol_pd_weighted.hpp), u = x - tau * kt as above (4 d + 1):
+    t = tl * w                                                                 : 1
+    l2: (u + t * bt) / (1 + t)                  t bt, u +, 1 +, divide 3       : 6
+    l1: d = u - bt, |d| - t, bt +                                              : 3
+    x_new:  R = 4 d + 8,  S = (S_u + |t bt|) / (1 + t)     (l2)
+            R = 4 d + 5,  S = S_u + 2 |bt| + t             (l1)
+            R = 4 d + 1,  S = S_u                          (w == 0: u itself)
+    xbar_new: 3 more, as above.
+k_prox_w (nsol_pdw.hip) is prox_data_w on a given u: R = 7 (l2), 4 (l1), and w == 0 hands u
+  back: R = 0, the bits of u.
+k_pdl_dual_data (nsol_pdl.hip) and its stacked twin (nsol_pdls.hip):
+    v = q + sigma * (t - bt)                    -, sigma *, q +                : 3
+        q - sigma * bt            (t NULL)      sigma *, q -                   : 2
+    c = lmbda * w                               (wt NULL: lmbda * 1, exact)    : 1 / 0
+    l2: (v * c) / (c + sigma)                   v c, c +, divide 3             : 5
+    l1: v < -c ? -c : v;  r > c ? c : r         selects: exact, 1-Lipschitz in v
+    S_v = |q| + |sigma| (|t| + |bt|)
+    l2:  R = R_v + R_c + 5,  S = S_v c / (c + sigma)
+    l1:  R = R_v + R_c,      S = S_v + c     (what comes out is v or +-c, c one rounding)
+    w == 0: +0 exactly.
 """
 import collections
 import functools
@@ -231,11 +264,11 @@ def primal_expected(p, st, sc, w, dtype, l1):
 
 def excess(got, want, R, S, dtype, exact=False, vector=False):
     """(bad, worst): the elements outside the gate and the largest err / bound (float32
-    only).  float64, exact and R == 0: bad = not equal.  vector: got, want of shape
+    only).  float64, exact and R zero everywhere: bad = not equal.  vector: got, want of shape
     (d,) + volume are judged per voxel, by the Euclidean norm of the difference."""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     assert got.shape == want.shape
-    if is64(dtype) or exact or R == 0:
+    if is64(dtype) or exact or not np.any(R):
         # bit for bit: the sign of a zero counts
         bad = (got != want) | ~np.isfinite(got) | (np.signbit(got) != np.signbit(want))
         if vector:
@@ -251,17 +284,21 @@ def excess(got, want, R, S, dtype, exact=False, vector=False):
     return ~(err <= bound), float(np.max(ratio)) if ratio.size else 0.
 
 
-def judge(got, st, sc, w, dtype, huber, l1, iso, has_p, exact=False, which="pxb"):
+def judge(got, st, sc, w, dtype, huber, l1, iso, has_p, exact=False, which="pxb",
+          primal=None):
     """The outputs (p, x, xbar) of one iteration against the restatement: p against
     pd_dual_step, x and xbar against pd_primal_step of the call's own p.  Returns
-    [(array name, bad, worst ratio)]; which: the letters of the outputs to judge."""
+    [(array name, bad, worst ratio)]; which: the letters of the outputs to judge.
+    primal: p -> ((x_new, R, S), (xbar_new, R, S)) of another primal half (weighted_expected,
+    lin_expected) in pd_primal_step's place."""
     out = []
     p = np.asarray(got[0], np.float64)
     if "p" in which:
         want, R, S = dual_expected(st, sc, w, dtype, huber, iso, has_p)
         out.append(("p_out",) + excess(p, want, R, S, dtype, exact, vector=iso))
     if "x" in which or "b" in which:
-        ex, eb = primal_expected(p, st, sc, w, dtype, l1)
+        ex, eb = (primal_expected(p, st, sc, w, dtype, l1) if primal is None
+                  else primal(p))
         if "x" in which:
             out.append(("x",) + excess(got[1], ex[0], ex[1], ex[2], dtype, exact))
         if "b" in which:
@@ -287,11 +324,15 @@ def _ceil(a, b):
     return -(-a // b)
 
 
-def plan(shape, dtype, offset=0, ry=0, rag=1, zchunk=0, iso=False, xcd_map=1):
+def plan(shape, dtype, offset=0, ry=0, rag=1, zchunk=0, iso=False, xcd_map=1, members=1):
     """What pd_launch, FusedKernel::launch / IsoKernel::launch, pd_auto_rows_per_lane and
     pd_plan_grid (nsol_pd_launch.hpp, nsol_pd.hip, nsol_pdi.hip) make of a single volume
     whose arrays all start `offset` elements behind a 16-byte boundary, under the knobs
-    pd_ry, pd_rag, pd_zchunk."""
+    pd_ry, pd_rag, pd_zchunk.  members: the volumes of a stacked launch; they count as tiles
+    in the automatic rows per lane and in the automatic z chunk.  The stacked, the weighted
+    and the linear launchers (pd_launch_forms) have one or two rows per lane and take no
+    knobs (kPdStackTune): that is ry = 0, rag = 1, zchunk = 0 here, where iso makes no
+    difference."""
     VW = vw(dtype)
     ndim, nz, ny, nx = dims3(shape)
     n = nz * ny * nx
@@ -303,7 +344,7 @@ def plan(shape, dtype, offset=0, ry=0, rag=1, zchunk=0, iso=False, xcd_map=1):
     else:
         kind, VEC, LX = "elem", 1, 64 if nx >= K_WAVE else 16
     TX, LY = LX * VEC, K_WAVE // LX
-    auto = lambda: 1 if (_ceil(nx, TX) * _ceil(ny, (K_BLOCK // K_WAVE) * LY * 2)
+    auto = lambda: 1 if (_ceil(nx, TX) * _ceil(ny, (K_BLOCK // K_WAVE) * LY * 2) * members
                          * ((nz + 1) // 2) < 512) else 2
     if iso:
         RY = ry if ry in (1, 2) else auto()
@@ -319,7 +360,7 @@ def plan(shape, dtype, offset=0, ry=0, rag=1, zchunk=0, iso=False, xcd_map=1):
     ntx, nty = _ceil(nx, TX), _ceil(ny, TY)
     zc = zchunk
     if zc <= 0:
-        zc = max(2, _ceil(nz, _ceil(4096, ntx * nty)))
+        zc = max(2, _ceil(nz, _ceil(4096, ntx * nty * members)))
     zc = min(zc, nz)
     slab = _ceil(nty, 8) if xcd_map and nty >= 16 else 0
     return Plan(Form(kind, LX, RY, ndim, ntx, nty, _ceil(nz, zc), slab), TX, TY, zc)
@@ -441,4 +482,359 @@ def branch_shares(case, dtype, huber=False):
         u = vn.grad_adj_axpy(p, st["x"], TAU, w, dtype)
         out["l1 shrunk onto bt (%s)" % ("iso" if iso else "aniso")] = np.mean(
             np.abs(u - st["bt"]) <= TL)
+    return {k: float(v) for k, v in out.items()}
+
+
+# =========================================================================================
+# The WGT and LIN forms (k_pd_w, k_pd_lin, k_pdl_stack) and their element-wise kernels
+# =========================================================================================
+LMBDA = 1.25
+# the weighted entry takes its scalars from a table row: tl = tau * lmbda, in double
+WEIGHTED = Scalars(SIGMA, HDEN, TAU, TAU * LMBDA, THETA)
+# neither bound is a float32, and float32(lo) < lo, float32(hi) > hi: rounded to nearest,
+# both bounds of the float32 box would lie outside the caller's
+BOX = (-0.46, 0.55)
+BOXES = (BOX, (-0.46, np.inf), (-np.inf, 0.55), (-np.inf, np.inf))
+DD_SIGMA, DD_LMBDA = 0.3, 1.7       # the element-wise dual update of the data term
+SCase = collections.namedtuple("SCase", "name shape unit offset members")
+
+
+def scase_plan(cs, dtype, members=None):
+    """The plan of the launchers without knobs (kPdStackTune) for the case's stack, or for
+    `members` of its volumes."""
+    return plan(cs.shape, dtype, cs.offset, members=cs.members if members is None else members)
+
+
+def scase_weights(cs):
+    return weights(cs.shape, cs.unit)
+
+
+@functools.lru_cache(maxsize=None)
+def catalogue_stack(dtype):
+    """Shapes (and member counts) that reach every form the launchers WITHOUT knobs have:
+    (vec | rag) x (64 | 16 lanes) and single elements where nx < 2 VW (16 lanes only),
+    1-D, 2-D and 3-D at one and two rows per lane, each with two tiles along x (not elem)
+    and y whose last one is partial and two z chunks in 3-D.  Two rows per lane need
+    tiles * members * ((nz + 1) / 2) >= 512, which no single volume under MAX_VOXELS has
+    with 2 x 2 tiles: those cases are stacks.  Then the edges the forms do not ask for."""
+    VW = vw(dtype)
+    cases = []
+
+    def add(name, shape, members=1, unit=False, offset=0):
+        cases.append(SCase(name, tuple(shape), unit, offset, members))
+
+    for kind in ("vec", "rag", "elem"):
+        for LX in (64, 16) if kind != "elem" else (16,):
+            TX = LX * (1 if kind == "elem" else VW)
+            nx = {"vec": TX + VW, "rag": TX + VW + 1, "elem": 2 * VW - 1}[kind]
+            ntx = 1 if kind == "elem" else 2
+            TY1 = 4 * (64 // LX)
+            add("%s%d-1d" % (kind, LX), (nx,))
+            add("%s%d-2d-ry1" % (kind, LX), (TY1 + 1, nx))
+            add("%s%d-2d-ry2" % (kind, LX), (2 * TY1 + 1, nx), members=512 // (2 * ntx))
+            add("%s%d-3d-ry1" % (kind, LX), (3, TY1 + 1, nx))
+            add("%s%d-3d-ry2" % (kind, LX), (3, 2 * TY1 + 1, nx), members=256 // (2 * ntx))
+    # the stack switches the form: ragged rows, 16 lanes, one tile along x and two tile rows
+    # of two rows per lane; 2 x 32 = 64 < 512 alone, 8 x 2 x 32 = 512 stacked (both types)
+    add("switch-3d-alone", (64, 33, 17))
+    add("switch-3d-stack", (64, 33, 17), members=8)
+    add("switch-2d-alone", (33, 17))                # 2 tiles alone, 512 in 256 members
+    add("switch-2d-stack", (33, 17), members=256)
+    add("unit-1d", (259,), unit=True)
+    add("unit-2d", (6, 259), unit=True)
+    add("unit-3d", (4, 6, 259), unit=True)
+    add("spaced-3d", (4, 6, 259))
+    add("small-3d", (3, 5, 7))
+    tail = lambda k: k if VW == 4 else 1         # (float64: a vector is two elements)
+    add("rag-2-valid", (3, 5, 64 * VW + VW + tail(2)))
+    add("rag-3-valid", (2, 5, 64 * VW + VW + tail(3)))
+    add("rag16-2-valid", (2, 9, 16 * VW + tail(2)))
+    add("rag16-3-valid", (9, 16 * VW + tail(3)))
+    add("rag-64-vectors", (2, 3, 64 * VW - VW + 1))
+    add("ones", (1, 1, 1))
+    add("one-1d", (1,))
+    add("nx1-2d", (7, 1))
+    add("ny1-2d", (1, 7))
+    add("ny1-3d", (3, 1, 9))
+    add("nx1-3d", (3, 9, 1))
+    add("ones-stack", (1, 1, 1), members=3)
+    # nty = 17 >= 16: the XCD slab map, 24 block rows for 17 tile rows
+    add("slab", (3, 67, 64 * VW + VW))
+    # arrays off 16-byte alignment: whole-vector shapes fall to the ragged form
+    add("off1-3d", (3, 9, 16 * VW + VW), offset=1)
+    add("off3-3d", (2, 5, 64 * VW + VW), offset=3)
+    add("off3-1d", (259,), offset=3)
+    add("off1-2d", (6, 259), offset=1)
+    add("off1-stack", (3, 9, 16 * VW + VW), offset=1, members=3)
+    for cs in cases:
+        assert int(np.prod(cs.shape)) <= MAX_VOXELS, cs
+    assert len({cs.name for cs in cases}) == len(cases)
+    return tuple(cases)
+
+
+def scase_named(name, dtype):
+    return [cs for cs in catalogue_stack(dtype) if cs.name == name][0]
+
+
+# the cases that carry the tie states of the two forms and the other boxes
+STACK_TIE_CASES = ("rag16-3d-ry1", "vec64-2d-ry1", "unit-1d", "unit-3d", "off1-3d")
+
+
+# -------------------------------------------------------------------------- states
+@functools.lru_cache(maxsize=None)
+def member_state(shape, dtype, m=0):
+    """state() for member m of a stack: member 0 is state() itself, the others differ."""
+    if m == 0:
+        return state(shape, dtype)
+    d = len(shape)
+    rng = np.random.default_rng([5100 + 7 * sum(shape) + 31 * d + np.dtype(dtype).itemsize, m])
+    r = lambda scale, *s: rounded(scale * rng.standard_normal(s), dtype)
+    return _frozen(dict(xbar=r(1., *shape), x=r(1., *shape), bt=r(1., *shape),
+                        p=r(P_SCALE, d, *shape)))
+
+
+@functools.lru_cache(maxsize=None)
+def lin_state(shape, dtype, m=0):
+    """member_state plus g ~ N(0, 1), the array in bt's place: u = x - tau (kt + g) has a
+    standard deviation above 1, so about a third of it falls on either side of BOX."""
+    st = dict(member_state(shape, dtype, m))
+    rng = np.random.default_rng([5300 + 7 * sum(shape) + np.dtype(dtype).itemsize, m])
+    st["g"] = rounded(rng.standard_normal(shape), dtype)
+    return _frozen(st)
+
+
+def _zero_weight_sites(shape):
+    """Flat voxels whose weight is forced to zero: the two corners that lie on every face
+    between them, and in the first and the last row both sides of every tile seam along
+    x that a form can have (TX = 16, 32, 64, 128 or 256 elements)."""
+    n, nx = int(np.prod(shape)), shape[-1]
+    sites = {0, n - 1}
+    for TX in (16, 32, 64, 128, 256):
+        if nx > TX:
+            sites |= {TX - 1, TX, n - nx + TX - 1, n - nx + TX}
+    return np.array(sorted(sites))
+
+
+@functools.lru_cache(maxsize=None)
+def weights_state(shape, dtype, m=0):
+    """member_state plus the weights wt: about 30 % exact zeros (the sites of
+    _zero_weight_sites among them), 15 % exact ones, the rest in (0, 3]; and under three
+    in four of the zeros bt holds NaN, +inf or -inf."""
+    st = dict(member_state(shape, dtype, m))
+    n = int(np.prod(shape))
+    rng = np.random.default_rng([5400 + 7 * sum(shape) + np.dtype(dtype).itemsize, m])
+    kind = rng.random(n)
+    wt = np.where(kind < 0.3, 0., np.where(kind < 0.45, 1., 3. - 3. * rng.random(n)))
+    wt[_zero_weight_sites(shape)] = 0.
+    wt = rounded(wt, dtype)
+    assert np.all(wt >= 0) and np.all(wt <= 3)
+    bt = st["bt"].reshape(-1).copy()
+    zeros = np.flatnonzero(wt == 0)
+    for k, junk in enumerate((np.nan, np.inf, -np.inf)):
+        bt[zeros[k::4]] = junk
+    st["wt"], st["bt"] = wt.reshape(shape), bt.reshape(shape)
+    return _frozen(st)
+
+
+def _nb(dtype):
+    t = np.dtype(dtype).type
+    return (lambda v: float(np.nextafter(t(v), t(np.inf))),
+            lambda v: float(np.nextafter(t(v), t(-np.inf))))
+
+
+def _plant_rows(n, seam, k):
+    """Where k planted values start: the first voxels, from the tile seam on, the last."""
+    starts = [0, n - k]
+    if seam is not None and k <= seam and seam + k <= n - k:
+        starts.append(seam)
+    return [s for s in starts if 0 <= s and s + k <= n]
+
+
+LIN_TIE_BOXES = {"box": (-0.5, 0.75), "zero": (0., 0.75), "point": (0.375, 0.375)}
+
+
+@functools.lru_cache(maxsize=None)
+def lin_tie_state(shape, dtype, seam, kind):
+    """xbar = 0 and has_p = 0: p_new = 0 and kt = +0 exactly, tau = 0.5, so u = x - g / 2
+    with x, g on 1/64.  Planted (g = 0 there): u on lo, on hi and one ulp either side of
+    each, u = -0.0 (which stays -0.0 on lo = 0), u = +0.0, far below and far above.
+    kind: "box" [-0.5, 0.75], "zero" [0, 0.75], "point" lo == hi == 0.375
+    (inside a binade: the mirror image of either neighbour is a number of the type)."""
+    n = int(np.prod(shape))
+    lo, hi = LIN_TIE_BOXES[kind]
+    up, dn = _nb(dtype)
+    rng = np.random.default_rng(6300 + 7 * sum(shape) + len(shape))
+    x, g = _grid(rng, n), _grid(rng, n)
+    us = [lo, hi, up(lo), dn(lo), up(hi), dn(hi), -0., 0., -2.5, 2.5]
+    for s in _plant_rows(n, seam, len(us)):
+        x[s:s + len(us)] = us
+        g[s:s + len(us)] = 0.
+    return _frozen(dict(xbar=np.zeros(shape), x=x.reshape(shape), g=g.reshape(shape),
+                        bt=np.zeros(shape), p=np.zeros((len(shape),) + shape)))
+
+
+def _l1_chain(T, u, bt, t):
+    """x_new and xbar_new (theta = 1) of the l1 prox at u in the arithmetic of type T."""
+    u, bt, t = T(u), T(bt), T(t)
+    d = u - bt
+    r = bt + np.maximum(np.abs(d) - t, T(0)) * np.sign(d)
+    return float(r), float(r + (r - u))
+
+
+def _l1_tie_pairs(dtype, t, bts=(0.25, -0.25, 0.5, 0.)):
+    """(u, bt) with u - bt on +-t, one ulp either side of each, and on 0 -- for the first
+    bt of bts at which u = bt + (u - bt) is a number of the type and no operation of the
+    prox and of the extrapolation behind it rounds in the type (theta = 1 mirrors x at
+    x_new, which next to a power of two need not be a number of the type)."""
+    up, dn = _nb(dtype)
+    T = np.dtype(dtype).type
+    out = []
+    for dv in (t, -t, up(t), dn(t), up(-t), dn(-t), 0.):
+        for bt in bts:
+            u = bt + dv
+            if float(T(u)) == u and u - bt == dv and \
+                    _l1_chain(T, u, bt, t) == _l1_chain(np.float64, u, bt, t):
+                out.append((u, bt))
+                break
+        else:
+            raise AssertionError((dtype, t, dv))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def wgt_tie_state(shape, dtype, seam):
+    """xbar = 0, has_p = 0: u = x exactly; tl = 0.5 and w in {0, 0.5, 1, 2}, so t = tl w is
+    exact, with x and bt on 1/64.  Planted: for w = 0.5, 1, 2 and 2^-20 the pairs of
+    _l1_tie_pairs (|u - bt| on and beside t), and w = 0 over NaN beside w = 2^-20.  (l1
+    only: the quotient of the l2 prox is not exact.)"""
+    n = int(np.prod(shape))
+    rng = np.random.default_rng(6400 + 7 * sum(shape) + len(shape))
+    x, bt = _grid(rng, n), _grid(rng, n)
+    wt = rng.choice([0., 0.5, 1., 2.], n)
+    us, bs, ws = [], [], []
+    for wv in (0.5, 1., 2., 2. ** -20):
+        for u, b in _l1_tie_pairs(dtype, TIE.tl * wv):
+            us.append(u), bs.append(b), ws.append(wv)
+        us.append(0.375), bs.append(np.nan), ws.append(0.)     # (w = 0 beside 2^-20 last)
+    for s in _plant_rows(n, seam, len(us)):
+        x[s:s + len(us)], bt[s:s + len(us)], wt[s:s + len(us)] = us, bs, ws
+    return _frozen(dict(xbar=np.zeros(shape), x=x.reshape(shape), bt=bt.reshape(shape),
+                        wt=wt.reshape(shape), p=np.zeros((len(shape),) + shape)))
+
+
+@functools.lru_cache(maxsize=None)
+def dual_data_tie_state(n, dtype, lmbda):
+    """q, t, bt on 1/64 and sigma = 0.25: v = q + sigma (t - bt) is exact; w in
+    {0, 0.5, 1, 2} and lmbda 1 or 0, so c = lmbda w is exact.  Planted (t = bt = 0): q on
+    +-c and one ulp either side of each, and w = 0 over NaN in bt."""
+    up, dn = _nb(dtype)
+    rng = np.random.default_rng(6500 + n)
+    q, t, bt = _grid(rng, n), _grid(rng, n), _grid(rng, n)
+    wt = rng.choice([0., 0.5, 1., 2.], n)
+    qs, ws = [], []
+    for wv in (0.5, 1., 2.):
+        cv = lmbda * wv
+        qs += [cv, -cv, up(cv), dn(cv), up(-cv), dn(-cv), 0., -0.]
+        ws += [wv] * 8
+    k = len(qs)
+    if n >= 2 * k + 2:
+        for s in (0, n - k):
+            q[s:s + k], wt[s:s + k], t[s:s + k], bt[s:s + k] = qs, ws, 0., 0.
+        wt[k], bt[k] = 0., np.nan
+    return _frozen(dict(q=q, t=t, bt=bt, wt=wt))
+
+
+# ----------------------------------------------------------------- want, R and S
+def _S_u(p, x, tau, w, dtype, g=None):
+    d = x.ndim
+    inner = sum(_abs_pair(p[a], d - 1 - a, False) * abs(c(w[a], dtype)) for a in range(d))
+    if g is not None:
+        inner = inner + np.abs(g)
+    return np.abs(x) + abs(c(tau, dtype)) * inner
+
+
+def _xbar_bound(x_new, R, S_x, x, theta, dtype):
+    th = abs(c(theta, dtype))
+    return R + 3, (1. + th) * np.maximum(S_x, np.abs(x_new)) + th * np.abs(x)
+
+
+def lin_expected(p, st, sc, w, dtype, box):
+    """((x_new, R, S), (xbar_new, R, S)) of the LIN primal half on the dual field p."""
+    x, g = st["x"], st["g"]
+    d = x.ndim
+    x_new, xbar_new = vn.pd_lin_primal_step(p, x, g, sc.tau, sc.theta, box[0], box[1], w,
+                                            dtype)
+    S_x = _S_u(p, x, sc.tau, w, dtype, g)
+    R = 4 * d + 2
+    # a u that lies outside the box by more than its own bound is outside it in the kernel
+    # as well: there x_new is the bound of the box itself, bit for bit (R = 0)
+    lo, hi = vn.box_in(box[0], box[1], dtype)
+    u = x - c(sc.tau, dtype) * (vn.grad_adj(p, w, dtype) + g)
+    margin = R * U32 * S_x
+    R_x = np.where((u < lo - margin) | (u > hi + margin), 0, R)
+    return (x_new, R_x, S_x), (xbar_new,) + _xbar_bound(x_new, R, S_x, x, sc.theta, dtype)
+
+
+def weighted_expected(p, st, sc, w, dtype, l1):
+    """The same of the WGT primal half; R is an array: 4 d + 1 where the weight is zero."""
+    x, bt, wt = st["x"], st["bt"], st["wt"]
+    d = x.ndim
+    x_new, xbar_new = vn.pd_weighted_primal_step(p, x, bt, wt, sc.tau, sc.tl, sc.theta, w,
+                                                 l1, dtype)
+    S_u = _S_u(p, x, sc.tau, w, dtype)
+    t = c(sc.tl, dtype) * wt
+    with np.errstate(invalid="ignore"):
+        S_on = S_u + 2. * np.abs(bt) + t if l1 else (S_u + np.abs(t * bt)) / (1. + t)
+    S_x = np.where(wt == 0, S_u, S_on)
+    R = np.where(wt == 0, 4 * d + 1, 4 * d + (5 if l1 else 8))
+    return (x_new, R, S_x), (xbar_new,) + _xbar_bound(x_new, R, S_x, x, sc.theta, dtype)
+
+
+def prox_w_expected(u, bt, wt, tl, l1, dtype):
+    """(want, R, S) of k_prox_w; where the weight is zero R = 0: the bits of u."""
+    want = vn.prox_data_w(u, bt, wt, tl, l1, dtype)
+    t = c(tl, dtype) * wt
+    with np.errstate(invalid="ignore"):
+        S = np.abs(u) + 2. * np.abs(bt) + t if l1 else (np.abs(u) + np.abs(t * bt)) / (1. + t)
+    return want, np.where(wt == 0, 0, 4 if l1 else 7), np.where(wt == 0, 0., S)
+
+
+def dual_data_expected(q, t, bt, wt, sigma, lmbda, l1, dtype):
+    """(want, R, S) of k_pdl_dual_data; where the weight is zero R = 0: +0."""
+    want = vn.pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1, dtype)
+    sg, lm = abs(c(sigma, dtype)), c(lmbda, dtype)
+    w = np.ones_like(q) if wt is None else wt
+    cc = lm * w
+    with np.errstate(invalid="ignore"):
+        S_v = np.abs(q) + sg * ((np.abs(t) if t is not None else 0.) + np.abs(bt))
+        S = S_v + cc if l1 else S_v * cc / (cc + sg)
+    R = (3 if t is not None else 2) + (0 if wt is None else 1) + (0 if l1 else 5)
+    return want, np.where(w == 0, 0, R), np.where(w == 0, 0., S)
+
+
+def box_holds_a_number(box, dtype):
+    """Whether the type has a number in the caller's [lo, hi]: then every iterate the
+    linear kernels hand back lies in it, in double."""
+    lo, hi = vn.box_in(box[0], box[1], dtype)
+    return box[0] <= lo <= hi <= box[1]
+
+
+# ----------------------------------------------------------------- branch shares
+def stack_branch_shares(cs, dtype, m=0):
+    """The shares of the voxels of member m's random states on each side of the branches
+    of the two forms, from the restatement alone (TV, anisotropic, p_in given)."""
+    w = scase_weights(cs)
+    st = lin_state(cs.shape, dtype, m)
+    p = vn.pd_dual_step(st["xbar"], st["p"], SIGMA, 1., w, dtype)
+    lo, hi = vn.box_in(BOX[0], BOX[1], dtype)
+    u = st["x"] - vn.as_scalar(TAU, dtype) * (vn.grad_adj(p, w, dtype) + st["g"])
+    out = {"below lo": np.mean(u < lo), "above hi": np.mean(u > hi),
+           "inside the box": np.mean((u >= lo) & (u <= hi))}
+    st = weights_state(cs.shape, dtype, m)
+    u = vn.grad_adj_axpy(p, st["x"], TAU, w, dtype)
+    on = st["wt"] != 0
+    with np.errstate(invalid="ignore"):
+        shrunk = on & (np.abs(u - st["bt"]) <= vn.as_scalar(WEIGHTED.tl, dtype) * st["wt"])
+    out.update({"w == 0": np.mean(~on), "l1 shrunk onto bt": np.mean(shrunk),
+                "l1 not shrunk (w > 0)": np.mean(on & ~shrunk)})
     return {k: float(v) for k, v in out.items()}

@@ -6,6 +6,7 @@ symbols and the command-line arguments."""
 import numpy as np
 import pytest
 
+from nsol_amd import vector_numpy as vn
 from test_pd_isotropic_host import project_iso
 
 
@@ -103,11 +104,10 @@ def grad_adj(p, spacing=None):
 
 
 def dual_data(v, c, sigma, w, data):
-    """The prox of the data term's conjugate: l2 (v c) / (c + sigma), l1 clamp(v, -c, c);
-    exactly 0 where w == 0, whatever v holds there."""
-    with np.errstate(invalid="ignore"):
-        r = (v * c) / (c + sigma) if data == "ell2" else np.minimum(np.maximum(v, -c), c)
-    return np.where(w == 0, 0., r)
+    """nsol_amd.vector_numpy.pdl_dual_prox (the restatement of k_pdl_dual_data's prox): l2
+    (v c) / (c + sigma), l1 the two selects onto [-c, c]; exactly 0 where w == 0, whatever
+    v holds there."""
+    return vn.pdl_dual_prox(v, c, sigma, w, data == "ell1")
 
 
 def default_steps(shape, kernel, spacing=None, tau=None, sigma=None):

@@ -84,9 +84,9 @@ class _Ctx(object):
                                  % (array, np.count_nonzero(bad),
                                     pc.first_bad(bad, self.shape)))
 
-    def judge(self, got, what, kernel, huber, l1, has_p, which, exact=False):
+    def judge(self, got, what, kernel, huber, l1, has_p, which, exact=False, primal=None):
         for array, bad, ratio in pc.judge(got, self.st, self.sc, self.w, self.dtype, huber,
-                                          l1, self.iso, has_p, exact, which):
+                                          l1, self.iso, has_p, exact, which, primal):
             if not pc.is64(self.dtype) and not exact:
                 key = "%s %s" % (kernel, array)
                 WORST[key] = max(WORST.get(key, 0.), ratio)

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+from nsol_amd import vector_numpy as vn
 from test_pd_isotropic_host import project_iso
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -16,15 +17,9 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 # ------------------------------------------------------------------ yardstick
 def prox_weighted(u, tl, bt, w, data):
-    """t = tl w; l2: (u + t bt) / (1 + t); l1: bt + max(|u - bt| - t, 0) sign(u - bt);
-    u itself where w == 0, whatever bt holds there."""
-    t = tl * w
-    with np.errstate(invalid="ignore"):
-        if data == "L2":
-            r = (u + t * bt) / (1. + t)
-        else:
-            r = bt + np.maximum(np.abs(u - bt) - t, 0) * np.sign(u - bt)
-    return np.where(w == 0, u, r)
+    """nsol_amd.vector_numpy.prox_data_w (the restatement of the kernels' helper) in the
+    argument order of the loops here."""
+    return vn.prox_data_w(u, bt, w, tl, data == "L1")
 
 
 def pd_weighted_denoise(obs, weights, shape, reg, data, alpha, iters, L2, alg,
