@@ -557,6 +557,26 @@ int nsol_pd_shift_min_iters(int elem_size, int ndim, int64_t nz, int64_t ny, int
 int nsol_pd_fusedk_plan_form(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
                              int form, int *waves, int *ntx, int64_t *zchunk);
 int nsol_pd_run_parts(int iterations, int min_iters, int *lead, int *launches);
+/* The block -> (tile, z-chunk) map of k_pd_fusedk and k_pd_shift3 on the host (no GPU):
+ * fills out[2 b], out[2 b + 1] with the tile (x-fastest, tile = ty * ntx + tx) and the
+ * z-chunk of block b of a launch over ntx x nty tiles and nzc z-chunks, -1, -1 for a block
+ * that returns at once; returns the number of blocks of the launch, NSOL_EINVAL if that
+ * exceeds max_blocks.  mode is the knob "pdk_xcd_map": 0 = plain order (tile = b mod
+ * tiles); 1 = XCD b mod 8 owns a contiguous run of WHOLE tile rows, dealt so that the
+ * shares differ by at most one tile row (the larger shares last, with the volume's clipped
+ * last tile row), plain order with fewer than 8 tile rows; 2 = the earlier map, slabs of
+ * ceil(tiles / 8) tiles per XCD (plain order with fewer than 16 tiles), for A/B runs.
+ * Further knobs of the footprint: "pdk_rows" n > 0 forces footprints of n rows (fewer than
+ * fit: trimmed; more: the kernel does not apply) next to "pdk_nw", "pdk_ntx" and
+ * "pdk_zchunk"; 0 = the tiling's own.  The tuner offers trimmed footprints by itself on
+ * the volumes it measures on; nsol_pd_fusedk_plan keeps reporting three numbers, the
+ * "pdk_verbose" lines name the rows. */
+int nsol_pdk_block_map(int mode, int ntx, int nty, int nzc, int *out, int max_blocks);
+/* Measurement only: a library built with -DNSOL_PDK_FINISH_PROBE keeps, per block of the
+ * depth-3 launches since the last call, the 100 MHz wall clock at its start (word 2 b) and
+ * behind its last plane step (word 2 b + 1); this copies `words` words out (after a device
+ * synchronisation) and clears the table.  -2: built without the probe. */
+int nsol_pdk_finish_probe(int64_t *out, int words);
 /* The whole loop of primal_dual_solver.py:232-261 in ONE launch for cache-
  * resident volumes (BASELINE configs 1-2; at most one tile of <= 1024 lanes x one
  * 16-byte vector per CU, i.e. up to ~1 Mi float voxels): every workgroup keeps its

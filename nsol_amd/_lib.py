@@ -112,7 +112,7 @@ PARAM_DEFAULTS = {
     "max_grid_blocks": 2048, "stencil_slabs": 1, "stencil_blocks": 65536,
     "pd2_zchunk": 0, "pd2_enable": 1, "pd2_variant": 0, "pd2_xcd_map": 1,
     "pdk_enable": 1, "pdk_kmax": 3, "pdk_nw": 0, "pdk_zchunk": 0, "pdk_ntx": 0,
-    "pdk_xcd_map": 1, "pdk_verbose": 0, "pdk_autotune": 1, "pdk_pf2": -1,
+    "pdk_xcd_map": 1, "pdk_rows": 0, "pdk_verbose": 0, "pdk_autotune": 1, "pdk_pf2": -1,
     "pdk_split": -1, "pdk_tail2": 1, "pdk_min_kvox": 1024, "pdk_tune_min_mvox": 16,
     "pdk_shift": -1, "pdk_shift_min_iters": 30,
     "pdp_max_spin": 1 << 21, "pdp_mute_tile": -1,

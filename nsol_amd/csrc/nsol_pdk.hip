@@ -77,6 +77,24 @@ using namespace nsol;
 #define PDK_LOAD_AUX 0
 #endif
 
+// Measurement only (-DNSOL_PDK_FINISH_PROBE, off by default): when does each workgroup of
+// the last depth-3 launch start and finish?  Wave 0 of block b writes the 100 MHz wall
+// clock into words 2 b (after the block -> tile map) and 2 b + 1 (behind its last plane
+// step) of a device table that nsol_pdk_finish_probe() copies out; surplus blocks leave
+// zeros.  tools/pdk_finish_probe.py turns the table into finish times per XCD and tile
+// row.
+#ifdef NSOL_PDK_FINISH_PROBE
+constexpr int kProbeBlocks = 8192;
+__device__ unsigned long long g_finish_probe[2 * kProbeBlocks];
+#define PDK_PROBE_MARK(w)                                                      \
+  do {                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < (unsigned)kProbeBlocks)               \
+      g_finish_probe[2 * blockIdx.x + (w)] = wall_clock64();                   \
+  } while (0)
+#else
+#define PDK_PROBE_MARK(w) do { } while (0)
+#endif
+
 namespace nsol_pdk {
 
 template <typename T, int K>
@@ -250,7 +268,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_fusedk(
     const T *__restrict__ x_in, T *__restrict__ x_out,
     const T *__restrict__ bt, const T *__restrict__ p_in,
     T *__restrict__ p_out, Geom<T> G, StageScalars<T, K> S, Tiling Q, int zchunk,
-    int slab) {
+    PdkBlockMap M) {
   constexpr int NT = NW * 64;
   constexpr int H = K - 1;
   constexpr int HX = ((H + VEC - 1) / VEC) * VEC;
@@ -270,21 +288,11 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_fusedk(
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  // Block -> (tile, z-chunk).  blockIdx % 8 names the XCD under the round-robin
-  // dispatch; each XCD walks `slab` consecutive tiles so that footprints which
-  // overlap mostly meet in one L2.  A whole workgroup leaves together.
-  const int ntiles = Q.ntx * Q.nty;
+  // Block -> (tile, z-chunk): pdk_block_tile (nsol_pd_common.hpp).  A whole workgroup
+  // leaves together.
   int tile, zc;
-  if (slab > 0) {
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    tile = xcd * slab + j % slab;
-    zc = j / slab;
-    if (tile >= ntiles) return;
-  } else {
-    tile = blockIdx.x % ntiles;
-    zc = blockIdx.x / ntiles;
-  }
+  if (!pdk_block_tile(M, (int)blockIdx.x, tile, zc)) return;
+  PDK_PROBE_MARK(0);
   const int tx = tile % Q.ntx;
   const int ty = tile / Q.ntx;
 
@@ -896,6 +904,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_fusedk(
   }
   for (; s <= s_last; ++s)       // at most K-1 drain steps
     step(std::false_type{}, s, LA, LA, CA, CA);
+  PDK_PROBE_MARK(1);
 }
 
 // ---------------------------------------------------------------------------
@@ -941,7 +950,7 @@ template <typename T, int VEC, int NW, int WPE, bool HUBER, bool L1, bool PF2, b
 __global__ __launch_bounds__(NW * 64, WPE) void k_pd_shift3(
     const T *__restrict__ x_in, T *__restrict__ x_out, const T *__restrict__ bt,
     const T *__restrict__ p_in, T *__restrict__ p_out, Geom<T> G, ShiftScalars<T> S,
-    Tiling Q, int zchunk, int slab) {
+    Tiling Q, int zchunk, PdkBlockMap M) {
   constexpr int K = 3;
   constexpr int NT = NW * 64;
   constexpr int HA = 2, HB = 3;                      // rows lost above / below
@@ -954,18 +963,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_shift3(
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int ntiles = Q.ntx * Q.nty;
   int tile, zc;
-  if (slab > 0) {
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    tile = xcd * slab + j % slab;
-    zc = j / slab;
-    if (tile >= ntiles) return;
-  } else {
-    tile = blockIdx.x % ntiles;
-    zc = blockIdx.x / ntiles;
-  }
+  if (!pdk_block_tile(M, (int)blockIdx.x, tile, zc)) return;
+  PDK_PROBE_MARK(0);
   const int tx = tile % Q.ntx;
   const int ty = tile / Q.ntx;
 
@@ -1306,6 +1306,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_shift3(
   }
   for (; s <= s_last; ++s)       // at most K drain steps
     step(std::false_type{}, s, LA, LA, CA, CA);
+  PDK_PROBE_MARK(1);
 }
 
 struct Tuning {
@@ -1314,7 +1315,8 @@ struct Tuning {
   int nw = 0;         // 0 = choose (12 or 8 waves for K = 3; 16 / 12 for K = 2)
   int zchunk = 0;     // 0 = choose
   int ntx = 0;        // 0 = choose
-  int xcd_map = 1;
+  int xcd_map = 1;    // 0 plain block order, 1 whole tile rows per XCD, 2 tile-count slabs
+  int rows = 0;       // 0 = the tiling's own footprint rows; n forces n (a trimmed footprint)
   int verbose = 0;
   int autotune = 1;   // time the best few model candidates once per problem shape
   int tune_min_mvox = 16;   // ... for volumes of at least this many Mi voxels
@@ -1326,12 +1328,17 @@ struct Tuning {
                         // measured between 96^3 and 128^3, tools/crossover_pd.py)
 };
 Tuning g_tunek;
+// a knob pins the geometry: experiments and tests, no plan and no tuning
+inline bool geometry_forced() {
+  return g_tunek.nw > 0 || g_tunek.ntx > 0 || g_tunek.zchunk > 0 || g_tunek.rows > 0;
+}
 
 int g_split = -1;   // -1 / 1: split lane mapping where it applies; 0: never (experiment)
 
 struct Config {
   int nw = 0;
   int pf2 = 0;       // 1 = two prefetch register sets
+  int trimmed = 0;   // 1 = fewer footprint rows than fit (a plan lists these by rank only)
   Tiling q{};
   int64_t zchunk = 0;
   double cost = 0.0;      // modelled bytes through L2 -> fabric per launch
@@ -1341,8 +1348,11 @@ struct Config {
 // xv_fixed > 0: that many valid voxels per tile (the last tile may be shorter)
 // instead of nx spread evenly over ntx tiles
 // lost: footprint rows that are overlap (2 h; the shifted form: 2 above + 3 below)
+// rows > 0: a trimmed footprint of that many rows (at most the nt / lxb that fit); the
+// lanes of the rows left out idle (`active` in the kernels)
 inline bool make_tiling(int64_t nx, int64_t ny, int nt, int vec, int h, int hx,
-                        int lxm, int ntx, Tiling *out, int64_t xv_fixed = 0, int lost = -1) {
+                        int lxm, int ntx, Tiling *out, int64_t xv_fixed = 0, int lost = -1,
+                        int rows = 0) {
   if (lost < 0) lost = 2 * h;
   Tiling q;
   if (ntx == 1) {
@@ -1357,6 +1367,8 @@ inline bool make_tiling(int64_t nx, int64_t ny, int nt, int vec, int h, int hx,
   }
   if (q.lxb < 1 || q.lxb > lxm) return false;
   q.rows = nt / q.lxb;
+  if (rows > q.rows) return false;
+  if (rows > 0) q.rows = rows;
   if (q.rows - lost < 1) return false;
   q.ntx = ntx;
   q.nty = (int)((ny + (q.rows - lost) - 1) / (q.rows - lost));
@@ -1364,6 +1376,12 @@ inline bool make_tiling(int64_t nx, int64_t ny, int nt, int vec, int h, int hx,
   q.split = (ntx > 1 && (q.xv / vec) % 32 == 0 && g_split != 0) ? 1 : 0;
   *out = q;
   return true;
+}
+
+// The block -> tile map of a launch under the knob pdk_xcd_map (nsol_pd_common.hpp has
+// the three modes); one place, should a form ever have to stay with another mode.
+inline PdkBlockMap launch_map(const Tiling &q, int64_t nzc, bool /*shift*/) {
+  return pdk_block_map(g_tunek.xcd_map, q.ntx, q.nty, (int)nzc);
 }
 
 // z-chunk length: trade the 2(K-1) extra planes per chunk against filling the
@@ -1404,13 +1422,32 @@ inline double model_cost(const Tiling &q, int64_t nx, int64_t ny, int64_t nz,
     if (hi <= lo) continue;
     lines += (double)((hi * esize - 1) / 128 - (lo * esize) / 128 + 1);
   }
-  double rows = 0.0;
+  // footprint rows inside the volume.  Under the whole-tile-row map eight times the rows of
+  // the heaviest XCD stand for the sum, so a tiling whose tile rows deal evenly to the XCDs
+  // ranks ahead of one with a nearly empty last tile row.  (Measured at 512^3 the lighter
+  // XCDs do not idle -- a launch is as long as one workgroup's march, DESIGN.md section 5 --
+  // but the tilings this charge puts first are the ones the tuner then keeps.)
   const int64_t tyv = q.rows - (shift ? 2 * h + 1 : 2 * h);
-  for (int ty = 0; ty < q.nty; ++ty) {
-    int64_t lo = (int64_t)ty * tyv - h, hi = lo + q.rows;
-    if (lo < 0) lo = 0;
-    if (hi > ny) hi = ny;
-    if (hi > lo) rows += (double)(hi - lo);
+  auto rows_of = [&](int ty0, int ty1) {
+    double r = 0.0;
+    for (int ty = ty0; ty < ty1; ++ty) {
+      int64_t lo = (int64_t)ty * tyv - h, hi = lo + q.rows;
+      if (lo < 0) lo = 0;
+      if (hi > ny) hi = ny;
+      if (hi > lo) r += (double)(hi - lo);
+    }
+    return r;
+  };
+  double rows = rows_of(0, q.nty);
+  const PdkBlockMap M = launch_map(q, 1, shift);
+  if (M.mode == 1) {
+    double heavy = 0.0;
+    for (int x = 0; x < 8; ++x) {
+      int first, count;
+      pdk_map_xcd_rows(M, x, first, count);
+      heavy = std::max(heavy, rows_of(first, first + count));
+    }
+    rows = 8.0 * heavy;
   }
   const double reads = lines * 128.0 * rows * (double)nz * (shift ? 5.0 : 6.0);
   const double writes = (shift ? 4.0 : 5.0) * (double)nx * ny * nz * esize;
@@ -1425,21 +1462,18 @@ int launch_f(const Config &c, const T *xbar_in, T *xbar_out, const T *x_in, T *x
   const Tiling &Q = c.q;
   const int64_t tiles = (int64_t)Q.ntx * Q.nty;
   const int64_t nzc = (G.nz + c.zchunk - 1) / c.zchunk;
-  int64_t blocks = tiles * nzc;
-  int64_t slab = 0;
-  if (g_tunek.xcd_map && tiles >= 16) {
-    slab = (tiles + 7) / 8;
-    blocks = 8 * slab * nzc;
-  }
+  if (tiles * nzc > 0x3fffffff) return NSOL_EINVAL;
+  const PdkBlockMap M = launch_map(Q, nzc, false);
+  const int64_t blocks = pdk_map_blocks(M);
   if (blocks > 0x7fffffff) return NSOL_EINVAL;
   if (g_tunek.verbose == 1)
     fprintf(stderr, "k_pd_fusedk K=%d waves=%d pf2=%d split=%d: lxb=%d rows=%d xv=%d tiles=%dx%d "
-            "zchunk=%lld blocks=%lld slab=%lld model=%.3f GB\n", K, NW, (int)PF2, Q.split, Q.lxb, Q.rows,
+            "zchunk=%lld blocks=%lld map=%d:%d model=%.3f GB\n", K, NW, (int)PF2, Q.split, Q.lxb, Q.rows,
             Q.xv, Q.ntx, Q.nty, (long long)c.zchunk, (long long)blocks,
-            (long long)slab, c.cost * 1e-9);
+            M.mode, M.q, c.cost * 1e-9);
   hipLaunchKernelGGL((k_pd_fusedk<T, VEC, NW, K, WPE, HUBER, L1, PF2, UNIT, RAG>),
                      dim3((unsigned)blocks), dim3(NW * 64), 0, st, xbar_in, xbar_out,
-                     x_in, x_out, bt, p_in, p_out, G, S, Q, (int)c.zchunk, (int)slab);
+                     x_in, x_out, bt, p_in, p_out, G, S, Q, (int)c.zchunk, M);
   g_launches[K == 3 ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   return launch_status();
 }
@@ -1500,7 +1534,7 @@ template <int NT, int K> constexpr int lxm_of() { return LdsShape<NT, K>::LXM; }
 // SHIFT: footprints of k_pd_shift3 (rows - 5 valid rows, an x halo of >= K voxels, one
 // more plane of overlap per z-chunk)
 template <typename T, int K, bool SHIFT = false>
-std::vector<Config> candidates(const Geom<T> &G) {
+std::vector<Config> candidates(const Geom<T> &G, bool twins = false) {
   constexpr int VW = 16 / sizeof(T);
   constexpr int H = K - 1;
   constexpr int HX = (((SHIFT ? K : H) + VW - 1) / VW) * VW;
@@ -1536,31 +1570,64 @@ std::vector<Config> candidates(const Geom<T> &G) {
       c.nw = nw;
       c.pf2 = (nw == 8) ? 1 : 0;
       if (g_tunek.pf2 == 0) c.pf2 = 0;
-      if (!make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &c.q, sp.xv, LOST)) continue;
-      const int64_t tiles = (int64_t)c.q.ntx * c.q.nty;
-      double zeff;
-      if (g_tunek.zchunk > 0) {
-        c.zchunk = g_tunek.zchunk < max_chunk ? g_tunek.zchunk : max_chunk;
-        if (c.zchunk > G.nz) c.zchunk = G.nz;
-        zeff = (double)c.zchunk / (double)(c.zchunk + LOST);
-      } else {
-        zeff = pick_zchunk(G.nz, tiles, LOST, max_chunk, &c.zchunk);
-      }
-      c.cost = model_cost(c.q, G.nx, G.ny, G.nz, VW, (int)sizeof(T), H, HX, zeff, SHIFT);
-      // fewer waves hide less latency: mild penalty so that ties go to more waves
-      c.cost *= 1.0 + 0.02 * (16 - nw) / 4.0;
-      if (c.q.split) {
-        // rows of whole waves stream ~15 % better (measured); rows of half waves
-        // gain less and not always: the plain mapping stays a candidate there
-        const bool whole = ((c.q.lxb - 2 * (HX / VW)) % 64) == 0;
-        if (!whole) {
-          Config d = c;
-          d.q.split = 0;
-          out.push_back(d);
+      if (!make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &c.q, sp.xv, LOST, g_tunek.rows))
+        continue;
+      // z-chunk and modelled cost of a tiling
+      auto price = [&](Config &c) {
+        const int64_t tiles = (int64_t)c.q.ntx * c.q.nty;
+        double zeff;
+        if (g_tunek.zchunk > 0) {
+          c.zchunk = g_tunek.zchunk < max_chunk ? g_tunek.zchunk : max_chunk;
+          if (c.zchunk > G.nz) c.zchunk = G.nz;
+          zeff = (double)c.zchunk / (double)(c.zchunk + LOST);
+        } else {
+          zeff = pick_zchunk(G.nz, tiles, LOST, max_chunk, &c.zchunk);
         }
-        c.cost *= whole ? 0.88 : 0.97;
+        c.cost = model_cost(c.q, G.nx, G.ny, G.nz, VW, (int)sizeof(T), H, HX, zeff, SHIFT);
+        // fewer waves hide less latency: mild penalty so that ties go to more waves
+        c.cost *= 1.0 + 0.02 * (16 - nw) / 4.0;
+      };
+      auto push = [&](Config c) {
+        if (c.q.split) {
+          // rows of whole waves stream ~15 % better (measured); rows of half waves
+          // gain less and not always: the plain mapping stays a candidate there
+          const bool whole = ((c.q.lxb - 2 * (HX / VW)) % 64) == 0;
+          if (!whole) {
+            Config d = c;
+            d.q.split = 0;
+            out.push_back(d);
+          }
+          c.cost *= whole ? 0.88 : 0.97;
+        }
+        out.push_back(c);
+      };
+      price(c);
+      push(c);
+      // Trimmed twins (the tuner's lists only): the same tiling with fewer footprint rows
+      // than fit -- the largest count within 3 rows that makes nty a multiple of 8 (whole
+      // tile rows deal evenly to the XCDs), and the largest that wastes fewer rows behind
+      // the volume's end than the untrimmed tiling.  A twin stays if the model charges it
+      // less than the untrimmed tiling, and gets on a plan's list by the model's rank alone
+      // (never by the "few tiles along x" rule): exploration is paid in real launches.
+      if (twins && g_tunek.rows == 0) {
+        auto nty_of = [&](int r) { return (int64_t)((G.ny + (r - LOST) - 1) / (r - LOST)); };
+        const int rmax = c.q.rows;
+        int twin[2] = {0, 0};
+        for (int r = rmax - 1; r >= rmax - 3 && r > LOST && !twin[0]; --r)
+          if (nty_of(r) % 8 == 0) twin[0] = r;
+        const int64_t waste = (int64_t)c.q.nty * (rmax - LOST) - G.ny;
+        for (int r = rmax - 1; r > LOST && !twin[1]; --r)
+          if (nty_of(r) * (r - LOST) - G.ny < waste) twin[1] = r;
+        if (twin[1] == twin[0]) twin[1] = 0;
+        for (int r : twin) {
+          Config d = c;
+          if (!r || !make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &d.q, sp.xv, LOST, r))
+            continue;
+          d.trimmed = 1;
+          price(d);
+          if (d.cost < c.cost) push(d);
+        }
       }
-      out.push_back(c);
     }
   }
   std::sort(out.begin(), out.end(),
@@ -1673,8 +1740,8 @@ inline void plan_poll(Plan &P, int K) {
     if (g_tunek.verbose) {
       for (int i = 0; i < n; ++i)
       {
-        fprintf(stderr, "k_pd_fusedk tune K=%d waves=%d ntx=%d zchunk=%lld: %.3f ms%s  [",
-                K, P.cand[i].nw, P.cand[i].q.ntx, (long long)P.cand[i].zchunk,
+        fprintf(stderr, "k_pd_fusedk tune K=%d waves=%d ntx=%d zchunk=%lld rows=%d: %.3f ms%s  [",
+                K, P.cand[i].nw, P.cand[i].q.ntx, (long long)P.cand[i].zchunk, P.cand[i].q.rows,
                 P.best_ms[i], i == arg ? "  <- kept" : (P.dropped[i] ? "  (dropped)" : ""));
         for (float v : P.samples[i]) fprintf(stderr, " %.3f", v);
         fprintf(stderr, " ]\n");
@@ -1692,7 +1759,7 @@ inline std::vector<Config> short_list(const std::vector<Config> &cand) {
   std::vector<Config> out;
   int per_nw[17] = {0};
   for (const Config &c : cand)
-    if (per_nw[c.nw]++ < 1 || c.q.ntx <= 4) out.push_back(c);
+    if (per_nw[c.nw]++ < 1 || (c.q.ntx <= 4 && !c.trimmed)) out.push_back(c);
   return out;
 }
 
@@ -1718,7 +1785,7 @@ int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt
 template <typename T, int K, bool SHIFT, typename Go>
 int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go) {
 #define NSOL_GO(cfg) go(cfg)
-  const bool forced = g_tunek.nw > 0 || g_tunek.ntx > 0 || g_tunek.zchunk > 0;
+  const bool forced = geometry_forced();
   if (forced) {                     // experiments and tests: no plan, no tuning
     std::vector<Config> cand = candidates<T, K, SHIFT>(G);
     if (cand.empty()) return -2;
@@ -1730,9 +1797,10 @@ int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go) {
   auto it = g_plans.find(key);
   if (it == g_plans.end()) {
     Plan P;
-    std::vector<Config> cand = candidates<T, K, SHIFT>(G);
-    if (cand.empty()) return -2;
     const bool big = G.n >= ((int64_t)g_tunek.tune_min_mvox << 20);
+    // (trimmed footprints: depth 3 of the volumes the tuner measures on)
+    std::vector<Config> cand = candidates<T, K, SHIFT>(G, K == 3 && g_tunek.autotune && big);
+    if (cand.empty()) return -2;
     // Depth 2 only ever runs the trailing pair of a run: ONE launch per run, far too
     // few to explore on.  Where the depth-3 plan of the shape has settled, depth 2
     // does not explore either: it takes 12-wave workgroups on whole rows where a row
@@ -1778,7 +1846,7 @@ int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go) {
       int per_nw[17] = {0};
       for (const Config &c : cand) {
         const int rank = per_nw[c.nw]++;
-        if (rank >= 3 && c.q.ntx > 4) continue;
+        if (rank >= 3 && (c.q.ntx > 4 || c.trimmed)) continue;
         P.cand.push_back(c);
         const int64_t zc = c.zchunk > 96 ? 64 : 24;
         if (rank < 2 && zc < c.zchunk && zc <= G.nz) {
@@ -1793,7 +1861,7 @@ int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go) {
       // flight).  The model ranks; the measurement decides.
       int per_nw[17] = {0};
       for (const Config &c : cand) {
-        if (per_nw[c.nw]++ >= 5 && c.q.ntx > 8) continue;
+        if (per_nw[c.nw]++ >= 5 && (c.q.ntx > 8 || c.trimmed)) continue;
         P.cand.push_back(c);
         const int64_t zc = c.zchunk > 96 ? 64 : 24;
         if (zc < c.zchunk && zc <= G.nz) {
@@ -1885,22 +1953,19 @@ int launch_shift(const Config &c, const T *x_in, T *x_out, const T *bt, const T 
   const Tiling &Q = c.q;
   const int64_t tiles = (int64_t)Q.ntx * Q.nty;
   const int64_t nzc = (G.nz + c.zchunk - 1) / c.zchunk;
-  int64_t blocks = tiles * nzc;
-  int64_t slab = 0;
-  if (g_tunek.xcd_map && tiles >= 16) {
-    slab = (tiles + 7) / 8;
-    blocks = 8 * slab * nzc;
-  }
+  if (tiles * nzc > 0x3fffffff) return NSOL_EINVAL;
+  const PdkBlockMap M = launch_map(Q, nzc, true);
+  const int64_t blocks = pdk_map_blocks(M);
   if (blocks > 0x7fffffff) return NSOL_EINVAL;
   if (g_tunek.verbose == 1)
     fprintf(stderr, "k_pd_shift3 waves=%d pf2=%d split=%d: lxb=%d rows=%d xv=%d tiles=%dx%d "
-            "zchunk=%lld blocks=%lld slab=%lld model=%.3f GB\n", NW, (int)PF2, Q.split, Q.lxb,
+            "zchunk=%lld blocks=%lld map=%d:%d model=%.3f GB\n", NW, (int)PF2, Q.split, Q.lxb,
             Q.rows, Q.xv, Q.ntx, Q.nty, (long long)c.zchunk, (long long)blocks,
-            (long long)slab, c.cost * 1e-9);
+            M.mode, M.q, c.cost * 1e-9);
 #define NSOL_S(HB, L, U)                                                             \
   hipLaunchKernelGGL((k_pd_shift3<T, VEC, NW, WPE, HB, L, PF2, U>), dim3((unsigned)blocks), \
                      dim3(NW * 64), 0, st, x_in, x_out, bt, p_in, p_out, G, S, Q,    \
-                     (int)c.zchunk, (int)slab)
+                     (int)c.zchunk, M)
 #define NSOL_SU(HB, L) do { if (unit) NSOL_S(HB, L, true); else NSOL_S(HB, L, false); } while (0)
   const bool unit = G.wx == T(1) && G.wy == T(1) && G.wz == T(1);
   const bool huber = (flags & NSOL_PD_REG_HUBER) != 0;
@@ -1922,8 +1987,7 @@ int launch_shift(const Config &c, const T *x_in, T *x_out, const T *bt, const T 
 // explore on the very runs that are too short to gain from the block, or never.
 template <typename T>
 int shift_donation(const Geom<T> &G) {
-  if (!g_tunek.autotune || G.n < ((int64_t)g_tunek.tune_min_mvox << 20) || g_tunek.nw > 0 ||
-      g_tunek.ntx > 0 || g_tunek.zchunk > 0)
+  if (!g_tunek.autotune || G.n < ((int64_t)g_tunek.tune_min_mvox << 20) || geometry_forced())
     return -1;
   std::lock_guard<std::mutex> lock(g_plans_mutex);
   const int dev = current_device();
@@ -1940,7 +2004,7 @@ int shift_donation(const Geom<T> &G) {
   }
   auto it = g_plans.find(PlanKey{dev, (int)sizeof(T), 3, G.nz, G.ny, G.nx, 0, 0});
   if (it == g_plans.end()) {        // not made yet: every candidate is owed kFinalRounds
-    const std::vector<Config> cand = candidates<T, 3, false>(G);
+    const std::vector<Config> cand = candidates<T, 3, false>(G, true);
     if (cand.size() < 2) return -1;
     return (int)short_list(cand).size() * kFinalRounds + 1;
   }
@@ -1980,7 +2044,7 @@ int shift_min_iters_t(int ndim, int64_t nz, int64_t ny, int64_t nx, int64_t pitc
   if (!shift_shape_ok<T>(ndim, nz, ny, nx, pitch)) return 0;
   const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
   std::lock_guard<std::mutex> lock(g_plans_mutex);
-  const bool forced = g_tunek.nw > 0 || g_tunek.ntx > 0 || g_tunek.zchunk > 0;
+  const bool forced = geometry_forced();
   if (forced || g_plans.find(PlanKey{current_device(), (int)sizeof(T), 3, nz, ny, nx, 0,
                                      1}) == g_plans.end())
     if (candidates<T, 3, true>(G).empty()) return 0;
@@ -2118,6 +2182,7 @@ int nsol_hip_set_param_pdk(const char *name, int value) {
   else if (!strcmp(name, "pdk_zchunk")) nsol_pdk::g_tunek.zchunk = value;
   else if (!strcmp(name, "pdk_ntx")) nsol_pdk::g_tunek.ntx = value;
   else if (!strcmp(name, "pdk_xcd_map")) nsol_pdk::g_tunek.xcd_map = value;
+  else if (!strcmp(name, "pdk_rows")) nsol_pdk::g_tunek.rows = value;
   else if (!strcmp(name, "pdk_verbose")) nsol_pdk::g_tunek.verbose = value;
   else if (!strcmp(name, "pdk_autotune")) nsol_pdk::g_tunek.autotune = value;
   else if (!strcmp(name, "pdk_pf2")) nsol_pdk::g_tunek.pf2 = value;
@@ -2248,6 +2313,39 @@ int nsol_pd_fusedk_plan(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx
   if (ntx) *ntx = c.q.ntx;
   if (zchunk) *zchunk = c.zchunk;
   return 0;
+}
+
+int nsol_pdk_block_map(int mode, int ntx, int nty, int nzc, int *out, int max_blocks) {
+  if (mode < 0 || mode > 2 || ntx < 1 || nty < 1 || nzc < 1 || !out ||
+      (int64_t)ntx * nty * nzc > 0x3fffffff)
+    return NSOL_EINVAL;
+  const nsol::PdkBlockMap M = nsol::pdk_block_map(mode, ntx, nty, nzc);
+  const long long blocks = nsol::pdk_map_blocks(M);
+  if (blocks > max_blocks) return NSOL_EINVAL;
+  for (int b = 0; b < (int)blocks; ++b) {
+    int tile, zc;
+    const bool live = nsol::pdk_block_tile(M, b, tile, zc);
+    out[2 * b] = live ? tile : -1;
+    out[2 * b + 1] = live ? zc : -1;
+  }
+  return (int)blocks;
+}
+
+int nsol_pdk_finish_probe(int64_t *out, int words) {
+#ifdef NSOL_PDK_FINISH_PROBE
+  if (!out || words < 0 || words > 2 * kProbeBlocks) return NSOL_EINVAL;
+  if (hipDeviceSynchronize() != hipSuccess) return launch_status();
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_finish_probe), (size_t)words * 8) != hipSuccess)
+    return launch_status();
+  void *table = nullptr;
+  if (hipGetSymbolAddress(&table, HIP_SYMBOL(g_finish_probe)) != hipSuccess ||
+      hipMemset(table, 0, sizeof(unsigned long long) * 2 * kProbeBlocks) != hipSuccess)
+    return launch_status();
+  return 0;
+#else
+  (void)out; (void)words;
+  return -2;      /* the library was built without the probe */
+#endif
 }
 
 #define NSOL_PDK_DEF(T, SUF)                                                           \
