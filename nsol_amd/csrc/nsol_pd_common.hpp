@@ -187,77 +187,6 @@ int pd_shift3_iter(const T *x_in, T *x_out, const T *bt, const T *p_in, T *p_out
                    const double *sigma, const double *hden, const double *tau,
                    const double *tl, const double *theta, int flags, void *stream);
 
-// Block -> (tile, z-chunk) of the depth-2 / depth-3 kernels of nsol_pdk.hip; one function
-// for both kernels, their launchers and the host-side test entry.  blockIdx % 8 names the
-// XCD under the round-robin dispatch, and the eight L2s are not coherent with each other.
-//   mode 0  plain order: tile = b % tiles, z-chunk = b / tiles.
-//   mode 1  XCD x owns a contiguous run of WHOLE tile rows, so the x-tiles of a tile row,
-//           which share halo lines, always meet in one L2.  nty = 8 q + r tile rows: the
-//           first 8 - r XCDs take q of them, the last r take q + 1.  The volume's last tile
-//           row -- the only one that may be clipped by ny -- lies in XCD 7, which is among
-//           the larger shares whenever there are any: the volume rows the XCDs cover
-//           differ by at most one tile row's valid rows, and no split of whole tile rows
-//           has a lighter heaviest XCD.  An XCD walks its tiles x-fastest, then y, then
-//           z-chunk; the blocks it has left over return at once.
-//   mode 2  the earlier map, for A/B runs: XCD x owns tiles [x slab, (x + 1) slab) with
-//           slab = ceil(tiles / 8), whether or not that cuts a tile row in two.
-struct PdkBlockMap {
-  int mode;
-  int ntx, nty;
-  int nzc;      // z-chunks
-  int q;        // mode 1: tile rows of the smaller share; mode 2: slab (tiles per XCD)
-  int big;      // mode 1: first XCD of the larger share (8: none)
-};
-// want: 0 / 1 / 2 as above; 1 falls back to 0 with fewer than 8 tile rows, 2 with fewer
-// than 16 tiles (as the earlier map did)
-__host__ __device__ inline PdkBlockMap pdk_block_map(int want, int ntx, int nty, int nzc) {
-  PdkBlockMap M{0, ntx, nty, nzc, 0, 8};
-  if (want == 1 && nty >= 8) {
-    M.mode = 1;
-    M.q = nty / 8;
-    M.big = 8 - nty % 8;
-  } else if (want == 2 && ntx * nty >= 16) {
-    M.mode = 2;
-    M.q = (ntx * nty + 7) / 8;
-  }
-  return M;
-}
-__host__ __device__ inline long long pdk_map_blocks(const PdkBlockMap &M) {
-  if (M.mode == 1) return 8LL * (M.q + (M.big < 8 ? 1 : 0)) * M.ntx * M.nzc;
-  if (M.mode == 2) return 8LL * M.q * M.nzc;
-  return (long long)M.ntx * M.nty * M.nzc;
-}
-// tile rows [first, first + count) of XCD x under mode 1
-__host__ __device__ inline void pdk_map_xcd_rows(const PdkBlockMap &M, int x, int &first,
-                                                 int &count) {
-  const int over = x > M.big ? x - M.big : 0;
-  first = x * M.q + over;
-  count = M.q + (x >= M.big ? 1 : 0);
-}
-// false: block b is surplus
-__host__ __device__ inline bool pdk_block_tile(const PdkBlockMap &M, int b, int &tile,
-                                               int &zc) {
-  const int ntiles = M.ntx * M.nty;
-  if (M.mode == 1) {
-    int first, count;
-    pdk_map_xcd_rows(M, b & 7, first, count);
-    const int j = b >> 3;
-    const int per = count * M.ntx;
-    zc = j / per;
-    tile = first * M.ntx + (j - zc * per);
-    return zc < M.nzc;
-  }
-  if (M.mode == 2) {
-    const int j = b >> 3;
-    tile = (b & 7) * M.q + j % M.q;
-    zc = j / M.q;
-    return tile < ntiles;
-  }
-  tile = b % ntiles;
-  zc = b / ntiles;
-  return true;
-}
-
 template <bool L1, typename T>
 __device__ __forceinline__ T prox_data_s(T u, T bt, T tl, T one_plus_tl) {
   if constexpr (L1) return prox_ell1(u, bt, tl);

@@ -35,8 +35,9 @@
 // the loop body has no exec-mask branches.  The arithmetic per voxel is that of K
 // launches of k_pd_fused in the same order, so results are bit-identical.
 //
-// Host side (bottom of the file): a cost model ranks footprint shapes; for large
-// volumes an online tuner measures the best few on the run's own launches.
+// Host side: a cost model ranks footprint shapes; for large volumes an online tuner
+// measures the best few on the run's own launches.  Both are plain C++ in
+// nsol_pdk_plan.hpp; the bottom of this file launches, keeps the plans and times samples.
 #include <stdio.h>
 #include <string.h>
 
@@ -51,6 +52,7 @@
 
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
+#include "nsol_pdk_plan.hpp"
 
 using namespace nsol;
 
@@ -107,14 +109,6 @@ struct StageScalars {
 std::atomic<int> g_launches[2];
 // ... and those of them that were launches of the shifted form (k_pd_shift3)
 std::atomic<int> g_shift_launches;
-
-struct Tiling {
-  int lxb;    // lanes per footprint row
-  int rows;   // footprint rows
-  int xv;     // valid voxels per tile along x; 0 = one tile spans the row
-  int ntx, nty;
-  int split;  // 1: whole waves hold the interior lanes of a row, halo lanes at the end
-};
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -288,7 +282,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_fusedk(
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  // Block -> (tile, z-chunk): pdk_block_tile (nsol_pd_common.hpp).  A whole workgroup
+  // Block -> (tile, z-chunk): pdk_block_tile (nsol_pdk_plan.hpp).  A whole workgroup
   // leaves together.
   int tile, zc;
   if (!pdk_block_tile(M, (int)blockIdx.x, tile, zc)) return;
@@ -1309,149 +1303,29 @@ __global__ __launch_bounds__(NW * 64, WPE) void k_pd_shift3(
   PDK_PROBE_MARK(1);
 }
 
-struct Tuning {
-  int enable = 1;
-  int kmax = 3;
-  int nw = 0;         // 0 = choose (12 or 8 waves for K = 3; 16 / 12 for K = 2)
-  int zchunk = 0;     // 0 = choose
-  int ntx = 0;        // 0 = choose
-  int xcd_map = 1;    // 0 plain block order, 1 whole tile rows per XCD, 2 tile-count slabs
-  int rows = 0;       // 0 = the tiling's own footprint rows; n forces n (a trimmed footprint)
-  int verbose = 0;
-  int autotune = 1;   // time the best few model candidates once per problem shape
-  int tune_min_mvox = 16;   // ... for volumes of at least this many Mi voxels
-  int pf2 = -1;       // -1 = where the registers allow; 0 / 1 force
-  int tail2 = 1;        // a run's trailing pair through depth 2 of this kernel once the
-                        // shape's depth-3 plan has settled (else k_pd_fused2)
-  int min_kvox = 1024;  // smaller volumes (Ki voxels) stay with the one-iteration kernel:
-                        // cache resident, they want many short workgroups (crossover
-                        // measured between 96^3 and 128^3, tools/crossover_pd.py)
-};
-Tuning g_tunek;
-// a knob pins the geometry: experiments and tests, no plan and no tuning
-inline bool geometry_forced() {
-  return g_tunek.nw > 0 || g_tunek.ntx > 0 || g_tunek.zchunk > 0 || g_tunek.rows > 0;
-}
+// ---- host side: the knobs, the launchers, the plans and their events.  Which footprints
+// there are, what they cost, which of them a plan lists and what the tuner makes of the
+// times it gets: nsol_pdk_plan.hpp.
+Tuning g_tunek;     // the knobs as they stand (nsol_hip_set_param_pdk)
 
-int g_split = -1;   // -1 / 1: split lane mapping where it applies; 0: never (experiment)
-
-struct Config {
-  int nw = 0;
-  int pf2 = 0;       // 1 = two prefetch register sets
-  int trimmed = 0;   // 1 = fewer footprint rows than fit (a plan lists these by rank only)
-  Tiling q{};
-  int64_t zchunk = 0;
-  double cost = 0.0;      // modelled bytes through L2 -> fabric per launch
-};
-
-// Footprint of `nt` lanes cut into ntx columns of tiles.
-// xv_fixed > 0: that many valid voxels per tile (the last tile may be shorter)
-// instead of nx spread evenly over ntx tiles
-// lost: footprint rows that are overlap (2 h; the shifted form: 2 above + 3 below)
-// rows > 0: a trimmed footprint of that many rows (at most the nt / lxb that fit); the
-// lanes of the rows left out idle (`active` in the kernels)
-inline bool make_tiling(int64_t nx, int64_t ny, int nt, int vec, int h, int hx,
-                        int lxm, int ntx, Tiling *out, int64_t xv_fixed = 0, int lost = -1,
-                        int rows = 0) {
-  if (lost < 0) lost = 2 * h;
-  Tiling q;
-  if (ntx == 1) {
-    q.xv = 0;
-    q.lxb = (int)((nx + vec - 1) / vec);
-  } else {
-    int64_t xv = xv_fixed > 0 ? xv_fixed : (nx + ntx - 1) / ntx;
-    xv = (xv + vec - 1) / vec * vec;
-    if (xv * (ntx - 1) >= nx) return false;   // fewer tiles would do
-    q.xv = (int)xv;
-    q.lxb = (int)(xv / vec) + 2 * (hx / vec);
-  }
-  if (q.lxb < 1 || q.lxb > lxm) return false;
-  q.rows = nt / q.lxb;
-  if (rows > q.rows) return false;
-  if (rows > 0) q.rows = rows;
-  if (q.rows - lost < 1) return false;
-  q.ntx = ntx;
-  q.nty = (int)((ny + (q.rows - lost) - 1) / (q.rows - lost));
-  // interior of a row = whole half-waves: give them to whole half-waves
-  q.split = (ntx > 1 && (q.xv / vec) % 32 == 0 && g_split != 0) ? 1 : 0;
-  *out = q;
-  return true;
-}
-
-// The block -> tile map of a launch under the knob pdk_xcd_map (nsol_pd_common.hpp has
-// the three modes); one place, should a form ever have to stay with another mode.
-inline PdkBlockMap launch_map(const Tiling &q, int64_t nzc, bool /*shift*/) {
-  return pdk_block_map(g_tunek.xcd_map, q.ntx, q.nty, (int)nzc);
-}
-
-// z-chunk length: trade the 2(K-1) extra planes per chunk against filling the
-// last round of workgroups (one workgroup per CU).  Returns the efficiency.
-inline double pick_zchunk(int64_t nz, int64_t tiles, int extra, int64_t max_chunk,
-                          int64_t *chunk_out) {
-  const double slots = (double)cu_count();
-  double best = -1.0;
-  int64_t best_chunk = nz < max_chunk ? nz : max_chunk;
-  for (int64_t nzc = 1; nzc <= nz; ++nzc) {
-    const int64_t chunk = (nz + nzc - 1) / nzc;
-    if (chunk < 8 && nzc > 1) break;
-    if (chunk > max_chunk) continue;
-    if ((nz + chunk - 1) / chunk != nzc) continue;
-    const double blocks = (double)tiles * nzc;
-    const double rounds = (double)(int64_t)((blocks + slots - 1) / slots);
-    const double fill = blocks / (rounds * slots);
-    const double eff = fill * (double)chunk / (double)(chunk + extra);
-    if (eff > best) { best = eff; best_chunk = chunk; }
-  }
-  *chunk_out = best_chunk;
-  return best > 0.0 ? best : 1.0;
-}
-
-// Bytes one launch pulls through L2 if no overlap is shared between footprints:
-// whole 128-byte lines per footprint row (the x halo costs a line on each side,
-// which is what makes narrow tiles expensive), six input arrays, plus the five
-// output arrays once.  (The shifted form: five input arrays, four output arrays, and
-// rows - 5 valid rows that start h = 2 rows inside the footprint.)
-inline double model_cost(const Tiling &q, int64_t nx, int64_t ny, int64_t nz,
-                         int vec, int esize, int h, int hx, double zeff, bool shift = false) {
-  double lines = 0.0;
-  for (int tx = 0; tx < q.ntx; ++tx) {
-    int64_t lo = q.xv ? (int64_t)tx * q.xv - hx : 0;
-    int64_t hi = lo + (int64_t)q.lxb * vec;
-    if (lo < 0) lo = 0;
-    if (hi > nx) hi = nx;
-    if (hi <= lo) continue;
-    lines += (double)((hi * esize - 1) / 128 - (lo * esize) / 128 + 1);
-  }
-  // footprint rows inside the volume.  Under the whole-tile-row map eight times the rows of
-  // the heaviest XCD stand for the sum, so a tiling whose tile rows deal evenly to the XCDs
-  // ranks ahead of one with a nearly empty last tile row.  (Measured at 512^3 the lighter
-  // XCDs do not idle -- a launch is as long as one workgroup's march, DESIGN.md section 5 --
-  // but the tilings this charge puts first are the ones the tuner then keeps.)
-  const int64_t tyv = q.rows - (shift ? 2 * h + 1 : 2 * h);
-  auto rows_of = [&](int ty0, int ty1) {
-    double r = 0.0;
-    for (int ty = ty0; ty < ty1; ++ty) {
-      int64_t lo = (int64_t)ty * tyv - h, hi = lo + q.rows;
-      if (lo < 0) lo = 0;
-      if (hi > ny) hi = ny;
-      if (hi > lo) r += (double)(hi - lo);
-    }
-    return r;
-  };
-  double rows = rows_of(0, q.nty);
-  const PdkBlockMap M = launch_map(q, 1, shift);
-  if (M.mode == 1) {
-    double heavy = 0.0;
-    for (int x = 0; x < 8; ++x) {
-      int first, count;
-      pdk_map_xcd_rows(M, x, first, count);
-      heavy = std::max(heavy, rows_of(first, first + count));
-    }
-    rows = 8.0 * heavy;
-  }
-  const double reads = lines * 128.0 * rows * (double)nz * (shift ? 5.0 : 6.0);
-  const double writes = (shift ? 4.0 : 5.0) * (double)nx * ny * nz * esize;
-  return (reads + writes) / zeff;
+// The grid of one launch of `c`: its blocks from the tiling and the block map, refused
+// beyond what the kernels' 32-bit indices hold; the pdk_verbose line (`head`: the kernel).
+inline int launch_grid(const Config &c, int64_t nz, const char *head, int nw, int pf2,
+                       PdkBlockMap *M, unsigned *blocks) {
+  const Tiling &Q = c.q;
+  const int64_t tiles = (int64_t)Q.ntx * Q.nty;
+  const int64_t nzc = (nz + c.zchunk - 1) / c.zchunk;
+  if (tiles * nzc > 0x3fffffff) return NSOL_EINVAL;
+  *M = launch_map(g_tunek, Q, nzc);
+  const int64_t n = pdk_map_blocks(*M);
+  if (n > 0x7fffffff) return NSOL_EINVAL;
+  if (g_tunek.verbose == 1)
+    fprintf(stderr, "%s waves=%d pf2=%d split=%d: lxb=%d rows=%d xv=%d tiles=%dx%d "
+            "zchunk=%lld blocks=%lld map=%d:%d model=%.3f GB\n", head, nw, pf2, Q.split, Q.lxb,
+            Q.rows, Q.xv, Q.ntx, Q.nty, (long long)c.zchunk, (long long)n, M->mode, M->q,
+            c.cost * 1e-9);
+  *blocks = (unsigned)n;
+  return 0;
 }
 
 template <typename T, int VEC, int NW, int K, int WPE, bool HUBER, bool L1, bool PF2,
@@ -1459,21 +1333,14 @@ template <typename T, int VEC, int NW, int K, int WPE, bool HUBER, bool L1, bool
 int launch_f(const Config &c, const T *xbar_in, T *xbar_out, const T *x_in, T *x_out,
              const T *bt, const T *p_in, T *p_out, const Geom<T> &G,
              const StageScalars<T, K> &S, hipStream_t st) {
-  const Tiling &Q = c.q;
-  const int64_t tiles = (int64_t)Q.ntx * Q.nty;
-  const int64_t nzc = (G.nz + c.zchunk - 1) / c.zchunk;
-  if (tiles * nzc > 0x3fffffff) return NSOL_EINVAL;
-  const PdkBlockMap M = launch_map(Q, nzc, false);
-  const int64_t blocks = pdk_map_blocks(M);
-  if (blocks > 0x7fffffff) return NSOL_EINVAL;
-  if (g_tunek.verbose == 1)
-    fprintf(stderr, "k_pd_fusedk K=%d waves=%d pf2=%d split=%d: lxb=%d rows=%d xv=%d tiles=%dx%d "
-            "zchunk=%lld blocks=%lld map=%d:%d model=%.3f GB\n", K, NW, (int)PF2, Q.split, Q.lxb, Q.rows,
-            Q.xv, Q.ntx, Q.nty, (long long)c.zchunk, (long long)blocks,
-            M.mode, M.q, c.cost * 1e-9);
+  PdkBlockMap M;
+  unsigned blocks;
+  if (int rc = launch_grid(c, G.nz, K == 3 ? "k_pd_fusedk K=3" : "k_pd_fusedk K=2", NW,
+                           (int)PF2, &M, &blocks))
+    return rc;
   hipLaunchKernelGGL((k_pd_fusedk<T, VEC, NW, K, WPE, HUBER, L1, PF2, UNIT, RAG>),
-                     dim3((unsigned)blocks), dim3(NW * 64), 0, st, xbar_in, xbar_out,
-                     x_in, x_out, bt, p_in, p_out, G, S, Q, (int)c.zchunk, M);
+                     dim3(blocks), dim3(NW * 64), 0, st, xbar_in, xbar_out,
+                     x_in, x_out, bt, p_in, p_out, G, S, c.q, (int)c.zchunk, M);
   g_launches[K == 3 ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   return launch_status();
 }
@@ -1495,12 +1362,7 @@ int launch_k(const Config &c, const T *xbar_in, T *xbar_out, const T *x_in, T *x
 #undef NSOL_F
 }
 
-// workgroup sizes compiled per depth (16 waves: neither the registers nor the
-// LDS of K = 3 fit)
-template <int K> struct Waves;
-template <> struct Waves<2> { static constexpr int n = 3; static constexpr int v[3] = {16, 12, 8}; };
-template <> struct Waves<3> { static constexpr int n = 2; static constexpr int v[2] = {12, 8}; };
-
+// the workgroup sizes candidates() offers per depth, each with its compiled form
 template <typename T, int K>
 int launch_cfg(const Config &c, const T *xbar_in, T *xbar_out, const T *x_in,
                T *x_out, const T *bt, const T *p_in, T *p_out, const Geom<T> &G,
@@ -1528,443 +1390,16 @@ int launch_cfg(const Config &c, const T *xbar_in, T *xbar_out, const T *x_in,
   return NSOL_EINVAL;
 }
 
-template <int NT, int K> constexpr int lxm_of() { return LdsShape<NT, K>::LXM; }
-
-// candidate configurations for a shape, cheapest (by model) first
-// SHIFT: footprints of k_pd_shift3 (rows - 5 valid rows, an x halo of >= K voxels, one
-// more plane of overlap per z-chunk)
-template <typename T, int K, bool SHIFT = false>
-std::vector<Config> candidates(const Geom<T> &G, bool twins = false) {
-  constexpr int VW = 16 / sizeof(T);
-  constexpr int H = K - 1;
-  constexpr int HX = (((SHIFT ? K : H) + VW - 1) / VW) * VW;
-  constexpr int LOST = SHIFT ? 2 * H + 1 : 2 * H;   // rows, and planes per z-chunk
-  std::vector<Config> out;
-  const int64_t plane_bytes = G.sz * (int64_t)sizeof(T);
-  // 32-bit buffer offsets: the planes one workgroup touches span < 2^30 bytes
-  const int64_t max_planes = ((int64_t)1 << 30) / plane_bytes - 1;
-  const int64_t max_chunk = max_planes - 2 * K - 1;
-  if (max_chunk < 8) return out;
-  for (int wi = 0; wi < Waves<K>::n; ++wi) {
-    const int nw = Waves<K>::v[wi];
-    if (g_tunek.nw > 0 && g_tunek.nw != nw) continue;
-    if (G.nx % VW != 0 && nw != 12) continue;     // see launch_cfg
-    if (SHIFT && g_tunek.pf2 == 0 && nw == 8) continue;   // 8 waves: the two-set form only
-    const int nt = nw * 64;
-    const int lxm = nt / (2 * K);
-    // tile counts 1..64 with nx spread evenly, plus tiles whose interior is exactly
-    // one or two waves wide (256 / 512 B-aligned rows for the split lane mapping)
-    // where nx is not a multiple of that
-    struct Spec { int ntx; int64_t xv; };
-    std::vector<Spec> specs;
-    for (int ntx = 1; ntx <= 64; ++ntx) specs.push_back({ntx, 0});
-    for (int lanes : {64, 128}) {
-      const int64_t xv = (int64_t)lanes * VW;
-      if (G.nx > xv && G.nx % xv != 0)
-        specs.push_back({(int)((G.nx + xv - 1) / xv), xv});
-    }
-    for (const Spec &sp : specs) {
-      const int ntx = sp.ntx;
-      if (g_tunek.ntx > 0 && ntx != g_tunek.ntx) continue;
-      Config c;
-      c.nw = nw;
-      c.pf2 = (nw == 8) ? 1 : 0;
-      if (g_tunek.pf2 == 0) c.pf2 = 0;
-      if (!make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &c.q, sp.xv, LOST, g_tunek.rows))
-        continue;
-      // z-chunk and modelled cost of a tiling
-      auto price = [&](Config &c) {
-        const int64_t tiles = (int64_t)c.q.ntx * c.q.nty;
-        double zeff;
-        if (g_tunek.zchunk > 0) {
-          c.zchunk = g_tunek.zchunk < max_chunk ? g_tunek.zchunk : max_chunk;
-          if (c.zchunk > G.nz) c.zchunk = G.nz;
-          zeff = (double)c.zchunk / (double)(c.zchunk + LOST);
-        } else {
-          zeff = pick_zchunk(G.nz, tiles, LOST, max_chunk, &c.zchunk);
-        }
-        c.cost = model_cost(c.q, G.nx, G.ny, G.nz, VW, (int)sizeof(T), H, HX, zeff, SHIFT);
-        // fewer waves hide less latency: mild penalty so that ties go to more waves
-        c.cost *= 1.0 + 0.02 * (16 - nw) / 4.0;
-      };
-      auto push = [&](Config c) {
-        if (c.q.split) {
-          // rows of whole waves stream ~15 % better (measured); rows of half waves
-          // gain less and not always: the plain mapping stays a candidate there
-          const bool whole = ((c.q.lxb - 2 * (HX / VW)) % 64) == 0;
-          if (!whole) {
-            Config d = c;
-            d.q.split = 0;
-            out.push_back(d);
-          }
-          c.cost *= whole ? 0.88 : 0.97;
-        }
-        out.push_back(c);
-      };
-      price(c);
-      push(c);
-      // Trimmed twins (the tuner's lists only): the same tiling with fewer footprint rows
-      // than fit -- the largest count within 3 rows that makes nty a multiple of 8 (whole
-      // tile rows deal evenly to the XCDs), and the largest that wastes fewer rows behind
-      // the volume's end than the untrimmed tiling.  A twin stays if the model charges it
-      // less than the untrimmed tiling, and gets on a plan's list by the model's rank alone
-      // (never by the "few tiles along x" rule): exploration is paid in real launches.
-      if (twins && g_tunek.rows == 0) {
-        auto nty_of = [&](int r) { return (int64_t)((G.ny + (r - LOST) - 1) / (r - LOST)); };
-        const int rmax = c.q.rows;
-        int twin[2] = {0, 0};
-        for (int r = rmax - 1; r >= rmax - 3 && r > LOST && !twin[0]; --r)
-          if (nty_of(r) % 8 == 0) twin[0] = r;
-        const int64_t waste = (int64_t)c.q.nty * (rmax - LOST) - G.ny;
-        for (int r = rmax - 1; r > LOST && !twin[1]; --r)
-          if (nty_of(r) * (r - LOST) - G.ny < waste) twin[1] = r;
-        if (twin[1] == twin[0]) twin[1] = 0;
-        for (int r : twin) {
-          Config d = c;
-          if (!r || !make_tiling(G.nx, G.ny, nt, VW, H, HX, lxm, ntx, &d.q, sp.xv, LOST, r))
-            continue;
-          d.trimmed = 1;
-          price(d);
-          if (d.cost < c.cost) push(d);
-        }
-      }
-    }
-  }
-  std::sort(out.begin(), out.end(),
-            [](const Config &a, const Config &b) { return a.cost < b.cost; });
-  return out;
-}
-
-// A plan belongs to one device (its events live there and boxes differ), one
-// element size, one depth and one volume shape.  The kernel variants of a shape
-// (TV / Huber, l1 / l2, unit / non-unit spacing) share it on purpose: they differ
-// in arithmetic per voxel, not in the footprint geometry the plan chooses.
-struct PlanKey {
-  int device, esize, k;
-  int64_t nz, ny, nx;
-  int64_t pitch = 0;     // row pitch of a padded layout (0: contiguous rows)
-  int form = 0;          // 1: the shifted form (other tile counts and z-chunks)
-  bool operator<(const PlanKey &o) const {
-    return std::tie(device, esize, k, nz, ny, nx, pitch, form) <
-           std::tie(o.device, o.esize, o.k, o.nz, o.ny, o.nx, o.pitch, o.form);
-  }
-};
-inline int current_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  return dev;
-}
-// Online autotuner.  A plan holds the model's best few configurations; while a
-// plan is exploring, every REAL launch of the run uses the next candidate and
-// is bracketed by two events that are read back later with hipEventQuery -- no
-// trial launches, no host synchronisation.  After `kRounds` samples per
-// candidate and `kFinalRounds` for those within 6 % of the best, the finalist
-// with the smallest median is kept for the life of the process.
-struct Sample { hipEvent_t e0, e1; int cand; };
-struct Plan {
-  std::vector<Config> cand;
-  std::vector<std::vector<float>> samples;
-  std::vector<float> best_ms;
-  std::vector<int> issued, done;
-  std::vector<char> dropped;
-  std::deque<Sample> pending;
-  int chosen = -1;
-};
-constexpr int kRounds = 2;
-// ... and the finalists -- whoever is within 6 % of the best after those -- are sampled
-// up to kFinalRounds times, taking turns: two samples each, minutes apart on a part whose
-// clock drifts, settled 511^3 on plans 14 % apart from run to run
-constexpr int kFinalRounds = 6;     // (the first sample of a configuration is cold: 5 that count)
-constexpr float kFinalBand = 1.06f;
-std::map<PlanKey, Plan> g_plans;
-
-// samples candidate i is owed (0: dropped)
-inline int plan_target(const Plan &P, int i, float best) {
-  if (P.dropped[i]) return 0;
-  if (P.done[i] >= kRounds && best > 0.f && P.best_ms[i] > kFinalBand * best) return kRounds;
-  return kFinalRounds;
-}
-inline float plan_best(const Plan &P) {
-  float best = -1.f;
-  for (int i = 0; i < (int)P.cand.size(); ++i)
-    if (!P.dropped[i] && P.done[i] >= 1 && (best < 0.f || P.best_ms[i] < best))
-      best = P.best_ms[i];
-  return best;
-}
-std::mutex g_plans_mutex;
-
-inline void plan_poll(Plan &P, int K) {
-  while (!P.pending.empty()) {
-    Sample sm = P.pending.front();
-    hipError_t q = hipEventQuery(sm.e1);
-    if (q == hipErrorNotReady) break;
-    float ms = 0.f;
-    if (q == hipSuccess && hipEventElapsedTime(&ms, sm.e0, sm.e1) == hipSuccess) {
-      if (P.best_ms[sm.cand] < 0.f || ms < P.best_ms[sm.cand]) P.best_ms[sm.cand] = ms;
-      P.samples[sm.cand].push_back(ms);
-      P.done[sm.cand]++;
-    } else {
-      (void)hipGetLastError();
-      P.issued[sm.cand]--;              // lost sample: take it again
-    }
-    (void)hipEventDestroy(sm.e0);
-    (void)hipEventDestroy(sm.e1);
-    P.pending.pop_front();
-  }
-  if (P.chosen >= 0) return;
-  const int n = (int)P.cand.size();
-  // (nobody is dropped on ONE sample: a single slow launch -- the part's clock, another
-  // process -- would bar the best tiling for the life of the process; candidates
-  // outside the band simply stop at kRounds samples)
-  bool all = true;
-  const float best_now = plan_best(P);
-  for (int i = 0; i < n; ++i)
-    if (P.done[i] < plan_target(P, i, best_now)) all = false;
-  if (all) {
-    // the finalists by the SECOND SMALLEST of their warm samples -- the first launch of a
-    // configuration is always slow (1.2 - 1.5 ms where the others take 1.13), and what
-    // disturbs a launch afterwards only ever slows it down: the median of five let two or
-    // three disturbed launches decide (a battery settled on 12 : 3 : 256, 1.20 ms, once in
-    // three runs); one lucky launch must not decide either.  Everybody else by the minimum
-    // of two.
-    auto score = [&](int i) {
-      if ((int)P.samples[i].size() < kFinalRounds) return P.best_ms[i] * kFinalBand;
-      std::vector<float> v(P.samples[i].begin() + 1, P.samples[i].end());
-      std::sort(v.begin(), v.end());
-      return v[1];
-    };
-    int arg = 0;
-    for (int i = 0; i < n; ++i)
-      if (!P.dropped[i] && (P.dropped[arg] || score(i) < score(arg))) arg = i;
-    P.chosen = arg;
-    if (g_tunek.verbose) {
-      for (int i = 0; i < n; ++i)
-      {
-        fprintf(stderr, "k_pd_fusedk tune K=%d waves=%d ntx=%d zchunk=%lld rows=%d: %.3f ms%s  [",
-                K, P.cand[i].nw, P.cand[i].q.ntx, (long long)P.cand[i].zchunk, P.cand[i].q.rows,
-                P.best_ms[i], i == arg ? "  <- kept" : (P.dropped[i] ? "  (dropped)" : ""));
-        for (float v : P.samples[i]) fprintf(stderr, " %.3f", v);
-        fprintf(stderr, " ]\n");
-      }
-    }
-  }
-}
-
-template <typename T, int K, bool SHIFT, typename Go>
-int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go);
-
-// the unshifted depth-3 plan's candidates on a shape that has a shifted plan: per
-// workgroup size the model's best and the tilings with up to 4 tiles along x
-inline std::vector<Config> short_list(const std::vector<Config> &cand) {
-  std::vector<Config> out;
-  int per_nw[17] = {0};
-  for (const Config &c : cand)
-    if (per_nw[c.nw]++ < 1 || (c.q.ntx <= 4 && !c.trimmed)) out.push_back(c);
-  return out;
-}
-
-template <typename T, int K>
-int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
-             const T *p_in, T *p_out, const Geom<T> &G, const double *sigma,
-             const double *hden, const double *tau, const double *tl,
-             const double *theta, int flags, hipStream_t st) {
-  StageScalars<T, K> S;
-  for (int i = 0; i < K; ++i) {
-    S.sigma[i] = (T)sigma[i]; S.hden[i] = huber_den<T>(hden[i]); S.tau[i] = (T)tau[i];
-    S.tl[i] = (T)tl[i]; S.optl[i] = prox_den<T>(tl[i]); S.theta[i] = (T)theta[i];
-  }
-  S.has_p = p_in != nullptr ? 1 : 0;
-  return planned_launch<T, K, false>(G, S.has_p != 0, st, [&](const Config &cfg) {
-    return launch_cfg<T, K>(cfg, xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, S,
-                            flags, st);
-  });
-}
-
-// One launch under the shape's plan: `go(config)` launches; `sample`: this launch may be
-// timed as a sample of an exploring plan.
-template <typename T, int K, bool SHIFT, typename Go>
-int planned_launch(const Geom<T> &G, bool sample, hipStream_t st, Go go) {
-#define NSOL_GO(cfg) go(cfg)
-  const bool forced = geometry_forced();
-  if (forced) {                     // experiments and tests: no plan, no tuning
-    std::vector<Config> cand = candidates<T, K, SHIFT>(G);
-    if (cand.empty()) return -2;
-    return NSOL_GO(cand[0]);
-  }
-  const PlanKey key{current_device(), (int)sizeof(T), K, G.nz, G.ny, G.nx,
-                    G.padded ? G.sy : 0, SHIFT ? 1 : 0};
-  std::lock_guard<std::mutex> lock(g_plans_mutex);
-  auto it = g_plans.find(key);
-  if (it == g_plans.end()) {
-    Plan P;
-    const bool big = G.n >= ((int64_t)g_tunek.tune_min_mvox << 20);
-    // (trimmed footprints: depth 3 of the volumes the tuner measures on)
-    std::vector<Config> cand = candidates<T, K, SHIFT>(G, K == 3 && g_tunek.autotune && big);
-    if (cand.empty()) return -2;
-    // Depth 2 only ever runs the trailing pair of a run: ONE launch per run, far too
-    // few to explore on.  Where the depth-3 plan of the shape has settled, depth 2
-    // does not explore either: it takes 12-wave workgroups on whole rows where a row
-    // fits one (what 81 exploring launches settle on at 512^3 -- 12 : 1 : 256, 1.02 ms
-    // a pair against 1.19 for k_pd_fused2 and for the depth-3 plan's own tiling,
-    // tools/_probe/tail2_tuned.py), else the model's best tiling with the depth-3
-    // plan's workgroup size and tile count along x.
-    // (the depth-3 plan of a shape whose long runs take the shifted block: that form's)
-    int seeded = -1;
-    if (K == 2 && g_tunek.autotune && big) {
-      auto it3 = g_plans.find(PlanKey{key.device, key.esize, 3, G.nz, G.ny, G.nx, key.pitch});
-      if (it3 == g_plans.end() || it3->second.chosen < 0)
-        it3 = g_plans.find(PlanKey{key.device, key.esize, 3, G.nz, G.ny, G.nx, key.pitch, 1});
-      if (it3 != g_plans.end() && it3->second.chosen >= 0) {
-        const Config &c3 = it3->second.cand[it3->second.chosen];
-        for (int i = 0; i < (int)cand.size() && seeded < 0; ++i)
-          if (cand[i].nw == 12 && cand[i].q.ntx == 1) seeded = i;
-        for (int i = 0; i < (int)cand.size() && seeded < 0; ++i)
-          if (cand[i].nw == c3.nw && cand[i].q.ntx == c3.q.ntx) seeded = i;
-      }
-    }
-    // The unshifted depth-3 form of a shape that has a shifted plan runs only what
-    // the block leaves over -- the short runs -- and explores on launches that long runs
-    // give up for it (shift_donation below).  Its list is short then: per workgroup size
-    // the tilings with up to 4 tiles along x and the model's best, no shorter z-chunks
-    // (the full list settles on one of them at 512^3 and at 256^3).
-    bool shortlist = false;
-    if (K == 3 && !SHIFT && g_tunek.autotune && big) {
-      auto its = g_plans.find(PlanKey{key.device, key.esize, 3, G.nz, G.ny, G.nx, key.pitch, 1});
-      shortlist = its != g_plans.end();
-    }
-    if (seeded >= 0) {
-      P.cand.push_back(cand[seeded]);
-      P.chosen = 0;
-    } else if (shortlist && cand.size() > 1) {
-      P.cand = short_list(cand);
-    } else if (SHIFT && g_tunek.autotune && big && cand.size() > 1) {
-      // The shifted plan explores on the launches of the first long runs of a shape
-      // (bench.py's plan pass: 8 runs of 19 launches), so its list is shorter: per
-      // workgroup size the tilings with up to 4 tiles along x plus the model's best
-      // three, and a shorter z-chunk only for the model's two best -- at 512^3 about 14
-      // candidates, two launches each and four more for every finalist.
-      int per_nw[17] = {0};
-      for (const Config &c : cand) {
-        const int rank = per_nw[c.nw]++;
-        if (rank >= 3 && (c.q.ntx > 4 || c.trimmed)) continue;
-        P.cand.push_back(c);
-        const int64_t zc = c.zchunk > 96 ? 64 : 24;
-        if (rank < 2 && zc < c.zchunk && zc <= G.nz) {
-          Config d = c;
-          d.zchunk = zc;
-          P.cand.push_back(d);
-        }
-      }
-    } else if (g_tunek.autotune && big && cand.size() > 1) {
-      // per workgroup size: the tilings with up to 8 tiles along x plus the
-      // model's best five, each also with a shorter z-chunk (more workgroups in
-      // flight).  The model ranks; the measurement decides.
-      int per_nw[17] = {0};
-      for (const Config &c : cand) {
-        if (per_nw[c.nw]++ >= 5 && (c.q.ntx > 8 || c.trimmed)) continue;
-        P.cand.push_back(c);
-        const int64_t zc = c.zchunk > 96 ? 64 : 24;
-        if (zc < c.zchunk && zc <= G.nz) {
-          Config d = c;
-          d.zchunk = zc;
-          P.cand.push_back(d);
-        }
-      }
-    } else {
-      P.cand.push_back(cand[0]);
-      P.chosen = 0;
-    }
-    const size_t n = P.cand.size();
-    P.best_ms.assign(n, -1.f);
-    P.samples.assign(n, std::vector<float>());
-    P.issued.assign(n, 0);
-    P.done.assign(n, 0);
-    P.dropped.assign(n, 0);
-    it = g_plans.emplace(key, std::move(P)).first;
-  }
-  Plan &P = it->second;
-  // no event queries / records on a stream that is being captured into a graph:
-  // such launches use the settled plan, or the model's best while exploring
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess) (void)hipGetLastError();
-  if (cap != hipStreamCaptureStatusNone)
-    return NSOL_GO(P.cand[P.chosen >= 0 ? P.chosen : 0]);
-  plan_poll(P, K);
-  if (P.chosen >= 0) return NSOL_GO(P.cand[P.chosen]);
-  // exploring: next candidate that still needs a sample (the first launch of a
-  // run reads no dual variable, so it is cheaper than all others: not a sample)
-  int pick = -1;
-  {
-    const float best_now = plan_best(P);
-    for (int r = 1; r <= kFinalRounds && pick < 0 && sample; ++r)
-      for (int i = 0; i < (int)P.cand.size() && pick < 0; ++i) {
-        const int owed = plan_target(P, i, best_now);
-        if (P.issued[i] < (r < owed ? r : owed)) pick = i;
-      }
-  }
-  if (pick < 0) {
-    // every sample is in flight: run the best one known so far meanwhile
-    pick = 0;
-    for (int i = 0; i < (int)P.cand.size(); ++i)
-      if (!P.dropped[i] && P.best_ms[i] >= 0.f &&
-          (P.best_ms[pick] < 0.f || P.best_ms[i] < P.best_ms[pick]))
-        pick = i;
-    return NSOL_GO(P.cand[pick]);
-  }
-  Sample sm;
-  sm.cand = pick;
-  if (hipEventCreate(&sm.e0) != hipSuccess) { (void)hipGetLastError(); return NSOL_GO(P.cand[pick]); }
-  if (hipEventCreate(&sm.e1) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipEventDestroy(sm.e0);
-    return NSOL_GO(P.cand[pick]);
-  }
-  (void)hipEventRecord(sm.e0, st);
-  const int rc = NSOL_GO(P.cand[pick]);
-  (void)hipEventRecord(sm.e1, st);
-  if (rc == 0) {
-    P.issued[pick]++;
-    P.pending.push_back(sm);
-  } else {
-    (void)hipEventDestroy(sm.e0);
-    (void)hipEventDestroy(sm.e1);
-  }
-  return rc;
-#undef NSOL_GO
-}
-
-// ---- the shifted form: knobs, dispatch
-int g_shift = -1;             // -1: long runs of large volumes; 0: never; 1: wherever it applies
-// Shortest run that takes the shifted block when g_shift is -1: the block pays for a
-// stand-alone dual and a stand-alone primal pass (28 bytes per voxel each) with 8 bytes
-// per voxel saved per launch.  Measured at 512^3 and 256^3 (DESIGN.md section 5 has the
-// curves): even at 24 iterations, 4 - 5 % ahead at 30.
-int g_shift_min_iters = 30;
-
-inline int shift_threshold() {
-  if (g_shift > 0) return 4;            // one launch between the two stand-alone steps
-  return g_shift_min_iters > 4 ? g_shift_min_iters : 4;
-}
-
 template <typename T, int VEC, int NW, int WPE, bool PF2>
 int launch_shift(const Config &c, const T *x_in, T *x_out, const T *bt, const T *p_in,
                  T *p_out, const Geom<T> &G, const ShiftScalars<T> &S, int flags,
                  hipStream_t st) {
-  const Tiling &Q = c.q;
-  const int64_t tiles = (int64_t)Q.ntx * Q.nty;
-  const int64_t nzc = (G.nz + c.zchunk - 1) / c.zchunk;
-  if (tiles * nzc > 0x3fffffff) return NSOL_EINVAL;
-  const PdkBlockMap M = launch_map(Q, nzc, true);
-  const int64_t blocks = pdk_map_blocks(M);
-  if (blocks > 0x7fffffff) return NSOL_EINVAL;
-  if (g_tunek.verbose == 1)
-    fprintf(stderr, "k_pd_shift3 waves=%d pf2=%d split=%d: lxb=%d rows=%d xv=%d tiles=%dx%d "
-            "zchunk=%lld blocks=%lld map=%d:%d model=%.3f GB\n", NW, (int)PF2, Q.split, Q.lxb,
-            Q.rows, Q.xv, Q.ntx, Q.nty, (long long)c.zchunk, (long long)blocks,
-            M.mode, M.q, c.cost * 1e-9);
+  PdkBlockMap M;
+  unsigned blocks;
+  if (int rc = launch_grid(c, G.nz, "k_pd_shift3", NW, (int)PF2, &M, &blocks)) return rc;
 #define NSOL_S(HB, L, U)                                                             \
-  hipLaunchKernelGGL((k_pd_shift3<T, VEC, NW, WPE, HB, L, PF2, U>), dim3((unsigned)blocks), \
-                     dim3(NW * 64), 0, st, x_in, x_out, bt, p_in, p_out, G, S, Q,    \
+  hipLaunchKernelGGL((k_pd_shift3<T, VEC, NW, WPE, HB, L, PF2, U>), dim3(blocks),    \
+                     dim3(NW * 64), 0, st, x_in, x_out, bt, p_in, p_out, G, S, c.q,  \
                      (int)c.zchunk, M)
 #define NSOL_SU(HB, L) do { if (unit) NSOL_S(HB, L, true); else NSOL_S(HB, L, false); } while (0)
   const bool unit = G.wx == T(1) && G.wy == T(1) && G.wz == T(1);
@@ -1979,76 +1414,201 @@ int launch_shift(const Config &c, const T *x_in, T *x_out, const T *bt, const T 
   return launch_status();
 }
 
-// Launches a long run gives up for the unshifted depth-3 plan of its shape (they run
-// ahead of the block or behind it, three iterations each, bit-identical either way): 0
-// until the shifted plan has issued its samples, then exactly the samples the unshifted
-// plan is still owed (plan_target), -1 once there is nothing left to ask for -- the run
-// loop then stops asking.  Without them the unshifted form -- the short runs -- would
-// explore on the very runs that are too short to gain from the block, or never.
-template <typename T>
-int shift_donation(const Geom<T> &G) {
-  if (!g_tunek.autotune || G.n < ((int64_t)g_tunek.tune_min_mvox << 20) || geometry_forced())
-    return -1;
+// ---- the plans of this process and the events of their samples in flight: a sampled
+// launch is bracketed by two events that are read back later with hipEventQuery
+struct Sample { hipEvent_t e0, e1; int cand; };
+struct Tuned {
+  Plan P;
+  std::deque<Sample> pending;
+};
+std::map<PlanKey, Tuned> g_plans;
+std::mutex g_plans_mutex;
+
+inline int current_device() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  return dev;
+}
+// the plan of a shape on the current device, null if there is none (g_plans_mutex held)
+inline Tuned *find_plan(int esize, int k, int64_t nz, int64_t ny, int64_t nx, int64_t pitch,
+                        int form) {
+  auto it = g_plans.find(PlanKey{current_device(), esize, k, nz, ny, nx, pitch, form});
+  return it == g_plans.end() ? nullptr : &it->second;
+}
+
+// hand the samples that have come back to the plan; settle it once all are in
+inline void plan_poll(Tuned &E, int K) {
+  Plan &P = E.P;
+  while (!E.pending.empty()) {
+    Sample sm = E.pending.front();
+    hipError_t q = hipEventQuery(sm.e1);
+    if (q == hipErrorNotReady) break;
+    float ms = 0.f;
+    if (q == hipSuccess && hipEventElapsedTime(&ms, sm.e0, sm.e1) == hipSuccess) {
+      plan_record(P, sm.cand, ms);
+    } else {
+      (void)hipGetLastError();
+      plan_lost(P, sm.cand);
+    }
+    (void)hipEventDestroy(sm.e0);
+    (void)hipEventDestroy(sm.e1);
+    E.pending.pop_front();
+  }
+  if (plan_settle(P) && g_tunek.verbose) {
+    for (int i = 0; i < (int)P.cand.size(); ++i) {
+      fprintf(stderr, "k_pd_fusedk tune K=%d waves=%d ntx=%d zchunk=%lld rows=%d: %.3f ms%s  [",
+              K, P.cand[i].nw, P.cand[i].q.ntx, (long long)P.cand[i].zchunk, P.cand[i].q.rows,
+              P.best_ms[i], i == P.chosen ? "  <- kept" : (P.dropped[i] ? "  (dropped)" : ""));
+      for (float v : P.samples[i]) fprintf(stderr, " %.3f", v);
+      fprintf(stderr, " ]\n");
+    }
+  }
+}
+
+// One launch under the plan of `key`: `go(config)` launches; `sample`: this launch may be
+// timed as a sample of an exploring plan.
+template <typename Go>
+int planned_launch(const PlanKey &key, bool sample, hipStream_t st, Go go) {
+  if (geometry_forced(g_tunek)) {      // experiments and tests: no plan, no tuning
+    const std::vector<Config> cand = candidates(g_tunek, key, cu_count());
+    if (cand.empty()) return -2;
+    return go(cand[0]);
+  }
   std::lock_guard<std::mutex> lock(g_plans_mutex);
-  const int dev = current_device();
-  auto its = g_plans.find(PlanKey{dev, (int)sizeof(T), 3, G.nz, G.ny, G.nx, 0, 1});
-  if (its == g_plans.end()) return 0;
-  plan_poll(its->second, 3);
-  if (its->second.chosen < 0) {
-    // (the host runs ahead of the device: a long run has issued every sample of the
-    // shifted plan long before the first one is read back -- that is when it hands over)
-    const Plan &S = its->second;
-    const float sbest = plan_best(S);
-    for (int i = 0; i < (int)S.cand.size(); ++i)
-      if (S.issued[i] < plan_target(S, i, sbest)) return 0;
+  auto it = g_plans.find(key);
+  if (it == g_plans.end()) {
+    const std::vector<Config> cand = plan_candidates(g_tunek, key, cu_count());
+    if (cand.empty()) return -2;
+    // what the shape's depth-3 plans have to say about the new plan's list (list_kind;
+    // of a shape whose long runs take the shifted block the unshifted plan may lag)
+    const Tuned *u3 = find_plan(key.esize, 3, key.nz, key.ny, key.nx, key.pitch, 0);
+    const Tuned *s3 = find_plan(key.esize, 3, key.nz, key.ny, key.nx, key.pitch, 1);
+    const Tuned *set3 = (u3 && u3->P.chosen >= 0) ? u3 : s3;
+    const Config *settled3 =
+        (set3 && set3->P.chosen >= 0) ? &set3->P.cand[set3->P.chosen] : nullptr;
+    it = g_plans.emplace(key, Tuned{plan_make(g_tunek, key, cand, settled3, s3 != nullptr), {}})
+             .first;
   }
-  auto it = g_plans.find(PlanKey{dev, (int)sizeof(T), 3, G.nz, G.ny, G.nx, 0, 0});
-  if (it == g_plans.end()) {        // not made yet: every candidate is owed kFinalRounds
-    const std::vector<Config> cand = candidates<T, 3, false>(G, true);
-    if (cand.size() < 2) return -1;
-    return (int)short_list(cand).size() * kFinalRounds + 1;
+  Tuned &E = it->second;
+  Plan &P = E.P;
+  // no event queries / records on a stream that is being captured into a graph:
+  // such launches use the settled plan, or the model's best while exploring
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) (void)hipGetLastError();
+  if (cap != hipStreamCaptureStatusNone) return go(P.cand[P.chosen >= 0 ? P.chosen : 0]);
+  plan_poll(E, key.k);
+  if (P.chosen >= 0) return go(P.cand[P.chosen]);
+  const PlanNext next = plan_next(P, sample);     // exploring
+  const Config &c = P.cand[next.cand];
+  if (!next.timed) return go(c);
+  Sample sm;
+  sm.cand = next.cand;
+  if (hipEventCreate(&sm.e0) != hipSuccess) { (void)hipGetLastError(); return go(c); }
+  if (hipEventCreate(&sm.e1) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipEventDestroy(sm.e0);
+    return go(c);
   }
-  Plan &P = it->second;
-  plan_poll(P, 3);
-  if (P.chosen >= 0) return -1;
-  const float best = plan_best(P);
-  int want = 0;
-  for (int i = 0; i < (int)P.cand.size(); ++i) {
-    const int owed = plan_target(P, i, best) - P.issued[i];
-    if (owed > 0) want += owed;
+  (void)hipEventRecord(sm.e0, st);
+  const int rc = go(c);
+  (void)hipEventRecord(sm.e1, st);
+  if (rc == 0) {
+    P.issued[sm.cand]++;
+    E.pending.push_back(sm);
+  } else {
+    (void)hipEventDestroy(sm.e0);
+    (void)hipEventDestroy(sm.e1);
   }
-  return want + 1;      // (+ 1: a run's first launch may read no dual variable: no sample)
+  return rc;
+}
+
+template <typename T>
+PlanKey plan_key(const Geom<T> &G, int k, int form) {
+  return PlanKey{current_device(), (int)sizeof(T), k, G.nz, G.ny, G.nx, G.padded ? G.sy : 0,
+                 form};
+}
+
+template <typename T, int K>
+int fusedk_k(const T *xbar_in, T *xbar_out, const T *x_in, T *x_out, const T *bt,
+             const T *p_in, T *p_out, const Geom<T> &G, const double *sigma,
+             const double *hden, const double *tau, const double *tl,
+             const double *theta, int flags, hipStream_t st) {
+  StageScalars<T, K> S;
+  for (int i = 0; i < K; ++i) {
+    S.sigma[i] = (T)sigma[i]; S.hden[i] = huber_den<T>(hden[i]); S.tau[i] = (T)tau[i];
+    S.tl[i] = (T)tl[i]; S.optl[i] = prox_den<T>(tl[i]); S.theta[i] = (T)theta[i];
+  }
+  S.has_p = p_in != nullptr ? 1 : 0;
+  return planned_launch(plan_key(G, K, 0), S.has_p != 0, st, [&](const Config &cfg) {
+    return launch_cfg<T, K>(cfg, xbar_in, xbar_out, x_in, x_out, bt, p_in, p_out, G, S,
+                            flags, st);
+  });
+}
+
+// ---- the shifted form: where it applies, and what its long runs give the short ones
+// nsol_pdk_plan.hpp's plan_donation for a shape, its plans polled first
+inline int shift_donation(int esize, int64_t nz, int64_t ny, int64_t nx) {
+  if (!tuned_size(g_tunek, nz * ny * nx) || geometry_forced(g_tunek)) return -1;
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
+  Tuned *S = find_plan(esize, 3, nz, ny, nx, 0, 1);
+  if (!S) return 0;
+  plan_poll(*S, 3);
+  if (!plan_issued(S->P)) return 0;
+  if (Tuned *U = find_plan(esize, 3, nz, ny, nx, 0, 0)) {
+    plan_poll(*U, 3);
+    return plan_donation(S->P, U->P);
+  }
+  // not made yet: what its first launch will make of it
+  const PlanKey key{current_device(), esize, 3, nz, ny, nx, 0, 0};
+  const std::vector<Config> cand = plan_candidates(g_tunek, key, cu_count());
+  if (cand.empty()) return -1;
+  return plan_donation(S->P, plan_make(g_tunek, key, cand, nullptr, true));
 }
 
 // does the shifted form apply to this shape under the knobs as they stand
-template <typename T>
-bool shift_shape_ok(int ndim, int64_t nz, int64_t ny, int64_t nx, int64_t pitch) {
-  constexpr int VW = 16 / sizeof(T);
-  if (!g_shift || !g_tunek.enable || g_tunek.kmax < 3 || ndim != 3 || pitch > nx) return false;
+inline bool shift_shape_ok(int esize, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                           int64_t pitch) {
+  const int VW = esize == 4 ? 4 : 2;
+  if (!g_tunek.shift || !g_tunek.enable || g_tunek.kmax < 3 || ndim != 3 || pitch > nx)
+    return false;
   const int64_t n = nz * ny * nx;
   if (n < ((int64_t)g_tunek.min_kvox << 10) || nx % VW != 0 || nx / VW < 8 || ny < 8 ||
       nz < 8 || nz >= ((int64_t)1 << 30))
     return false;
   // by itself only on the volumes the online tuner handles (measured there)
-  return g_shift > 0 || n >= ((int64_t)g_tunek.tune_min_mvox << 20);
-}
-inline bool shift_shape_ok(int elem_size, int64_t nz, int64_t ny, int64_t nx) {
-  return elem_size == 4 ? shift_shape_ok<float>(3, nz, ny, nx, 0)
-                        : shift_shape_ok<double>(3, nz, ny, nx, 0);
+  return g_tunek.shift > 0 || n >= ((int64_t)g_tunek.tune_min_mvox << 20);
 }
 
 // the shortest run of this shape that takes the shifted block (0: none): the form
 // applies under the knobs as they stand and a footprint fits
-template <typename T>
-int shift_min_iters_t(int ndim, int64_t nz, int64_t ny, int64_t nx, int64_t pitch) {
-  if (!shift_shape_ok<T>(ndim, nz, ny, nx, pitch)) return 0;
-  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, 1.0, 1.0, 1.0);
+inline int shift_min_iters(int esize, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                           int64_t pitch) {
+  if (!shift_shape_ok(esize, ndim, nz, ny, nx, pitch)) return 0;
   std::lock_guard<std::mutex> lock(g_plans_mutex);
-  const bool forced = geometry_forced();
-  if (forced || g_plans.find(PlanKey{current_device(), (int)sizeof(T), 3, nz, ny, nx, 0,
-                                     1}) == g_plans.end())
-    if (candidates<T, 3, true>(G).empty()) return 0;
-  return shift_threshold();
+  if (geometry_forced(g_tunek) || !find_plan(esize, 3, nz, ny, nx, 0, 1))
+    if (candidates(g_tunek, PlanKey{0, esize, 3, nz, ny, nx, 0, 1}, cu_count()).empty())
+      return 0;
+  return shift_threshold(g_tunek);
+}
+
+// The depth-k plan the reporting entries speak of (g_plans_mutex held).  Depth 3 of a shape
+// whose long runs take the shifted block: that form's plan (*shifted = true) -- unless the
+// process has made short runs only so far: then the unshifted plan is all there is.
+inline Tuned *reported_plan(int esize, int k, int64_t nz, int64_t ny, int64_t nx,
+                            bool *shifted) {
+  Tuned *E = nullptr;
+  if (k == 3 && shift_shape_ok(esize, 3, nz, ny, nx, 0)) E = find_plan(esize, k, nz, ny, nx, 0, 1);
+  *shifted = E != nullptr;
+  return E ? E : find_plan(esize, k, nz, ny, nx, 0, 0);
+}
+// what a settled plan has chosen; NSOL_EINVAL: no plan, or not settled
+inline int report_choice(const Tuned *E, int *waves, int *ntx, int64_t *zchunk) {
+  if (!E || E->P.chosen < 0) return NSOL_EINVAL;
+  const Config &c = E->P.cand[E->P.chosen];
+  if (waves) *waves = c.nw;
+  if (ntx) *ntx = c.q.ntx;
+  if (zchunk) *zchunk = c.zchunk;
+  return 0;
 }
 
 }  // namespace nsol_pdk
@@ -2064,7 +1624,8 @@ int pd_shift3_min_iters(const T *x, const T *x_alt, const T *bt, const T *p0, co
   // (a run too short for the block under any shape asks nothing else: the short runs'
   // path gains no host work -- the plan lookup and, without a plan, the candidate list
   // cost tens of microseconds in front of a run's first launch)
-  if (!nsol_pdk::g_shift || iterations < nsol_pdk::shift_threshold()) return 0;
+  if (!nsol_pdk::g_tunek.shift || iterations < nsol_pdk::shift_threshold(nsol_pdk::g_tunek))
+    return 0;
   if (!x || !x_alt || !bt || !p0 || !p1 || !aligned16(x) || !aligned16(x_alt) ||
       !aligned16(bt) || !aligned16(p0) || !aligned16(p1))
     return 0;
@@ -2073,7 +1634,7 @@ int pd_shift3_min_iters(const T *x, const T *x_alt, const T *bt, const T *p0, co
 
 template <typename T>
 int pd_shift3_donation(int64_t nz, int64_t ny, int64_t nx) {
-  return nsol_pdk::shift_donation<T>(make_geom<T>(3, nz, ny, nx, 1.0, 1.0, 1.0));
+  return nsol_pdk::shift_donation((int)sizeof(T), nz, ny, nx);
 }
 
 // One launch of k_pd_shift3: iterations n .. n+2's primal steps and n+1 .. n+3's dual
@@ -2100,7 +1661,7 @@ int pd_shift3_iter(const T *x_in, T *x_out, const T *bt, const T *p_in, T *p_out
     S.theta[i] = (T)theta[i];
   }
   hipStream_t st = as_stream(stream);
-  return planned_launch<T, 3, true>(G, true, st, [&](const Config &c) {
+  return planned_launch(plan_key(G, 3, 1), true, st, [&](const Config &c) {
     if (c.nw == 12)
       return launch_shift<T, VW, 12, 3, false>(c, x_in, x_out, bt, p_in, p_out, G, S, flags, st);
     if (c.nw == 8)
@@ -2109,7 +1670,7 @@ int pd_shift3_iter(const T *x_in, T *x_out, const T *bt, const T *p_in, T *p_out
   });
 }
 
-#define NSOL_PDS_INST(T)                                                                 \
+#define NSOL_PDS_INST(T)                                                               \
   template int pd_shift3_donation<T>(int64_t, int64_t, int64_t);                         \
   template int pd_shift3_min_iters<T>(const T *, const T *, const T *, const T *,        \
                                       const T *, int, int64_t, int64_t, int64_t, int,    \
@@ -2175,61 +1736,52 @@ NSOL_PDK_INST(double)
 extern "C" {
 
 int nsol_hip_set_param_pdk(const char *name, int value) {
+  using namespace nsol_pdk;
+  static const struct { const char *name; int Tuning::*field; } knobs[] = {
+      {"pdk_enable", &Tuning::enable},       {"pdk_kmax", &Tuning::kmax},
+      {"pdk_nw", &Tuning::nw},               {"pdk_zchunk", &Tuning::zchunk},
+      {"pdk_ntx", &Tuning::ntx},             {"pdk_xcd_map", &Tuning::xcd_map},
+      {"pdk_rows", &Tuning::rows},           {"pdk_verbose", &Tuning::verbose},
+      {"pdk_autotune", &Tuning::autotune},   {"pdk_pf2", &Tuning::pf2},
+      {"pdk_split", &Tuning::split},         {"pdk_min_kvox", &Tuning::min_kvox},
+      {"pdk_tail2", &Tuning::tail2},         {"pdk_tune_min_mvox", &Tuning::tune_min_mvox},
+      {"pdk_shift", &Tuning::shift},         {"pdk_shift_min_iters", &Tuning::shift_min_iters},
+  };
   if (!name) return NSOL_EINVAL;
-  if (!strcmp(name, "pdk_enable")) nsol_pdk::g_tunek.enable = value;
-  else if (!strcmp(name, "pdk_kmax")) nsol_pdk::g_tunek.kmax = value;
-  else if (!strcmp(name, "pdk_nw")) nsol_pdk::g_tunek.nw = value;
-  else if (!strcmp(name, "pdk_zchunk")) nsol_pdk::g_tunek.zchunk = value;
-  else if (!strcmp(name, "pdk_ntx")) nsol_pdk::g_tunek.ntx = value;
-  else if (!strcmp(name, "pdk_xcd_map")) nsol_pdk::g_tunek.xcd_map = value;
-  else if (!strcmp(name, "pdk_rows")) nsol_pdk::g_tunek.rows = value;
-  else if (!strcmp(name, "pdk_verbose")) nsol_pdk::g_tunek.verbose = value;
-  else if (!strcmp(name, "pdk_autotune")) nsol_pdk::g_tunek.autotune = value;
-  else if (!strcmp(name, "pdk_pf2")) nsol_pdk::g_tunek.pf2 = value;
-  else if (!strcmp(name, "pdk_split")) nsol_pdk::g_split = value;
-  else if (!strcmp(name, "pdk_min_kvox")) nsol_pdk::g_tunek.min_kvox = value;
-  else if (!strcmp(name, "pdk_tail2")) nsol_pdk::g_tunek.tail2 = value;
-  else if (!strcmp(name, "pdk_tune_min_mvox")) nsol_pdk::g_tunek.tune_min_mvox = value;
-  else if (!strcmp(name, "pdk_shift")) nsol_pdk::g_shift = value < 0 ? -1 : (value ? 1 : 0);
-  else if (!strcmp(name, "pdk_shift_min_iters")) nsol_pdk::g_shift_min_iters = value;
-  else if (!strcmp(name, "pdk_forget")) {
-    std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
-    for (auto &kv : nsol_pdk::g_plans)
+  if (!strcmp(name, "pdk_forget")) {
+    std::lock_guard<std::mutex> lock(g_plans_mutex);
+    for (auto &kv : g_plans)
       for (auto &sm : kv.second.pending) {
         (void)hipEventDestroy(sm.e0);
         (void)hipEventDestroy(sm.e1);
       }
-    nsol_pdk::g_plans.clear();
+    g_plans.clear();
+    return 0;
   }
-  else return NSOL_EINVAL;
-  return 0;
+  for (const auto &kn : knobs)
+    if (!strcmp(name, kn.name)) {
+      if (kn.field == &Tuning::shift) value = value < 0 ? -1 : (value ? 1 : 0);
+      g_tunek.*kn.field = value;
+      return 0;
+    }
+  return NSOL_EINVAL;
 }
 
 int nsol_pd_fusedk_tuned(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx) {
-  std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
-  // (depth 3 of a shape whose long runs take the shifted block: that form's plan)
-  int form = (k == 3 && nsol_pdk::shift_shape_ok(elem_size, nz, ny, nx)) ? 1 : 0;
-  auto it = nsol_pdk::g_plans.find(
-      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, form});
-  if (form && it == nsol_pdk::g_plans.end()) {
-    /* a process that has made short runs only: the unshifted plan is all there is */
-    form = 0;
-    it = nsol_pdk::g_plans.find(
-        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, 0});
-  }
-  if (it == nsol_pdk::g_plans.end()) return -1;
-  nsol_pdk::plan_poll(it->second, k);
-  if (form && it->second.chosen >= 0 && nsol_pdk::g_tunek.autotune &&
-      nz * ny * nx >= ((int64_t)nsol_pdk::g_tunek.tune_min_mvox << 20)) {
+  using namespace nsol_pdk;
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
+  bool shifted;
+  Tuned *E = reported_plan(elem_size, k, nz, ny, nx, &shifted);
+  if (!E) return -1;
+  plan_poll(*E, k);
+  if (shifted && E->P.chosen >= 0 && tuned_size(g_tunek, nz * ny * nx)) {
     /* ... and the unshifted plan, which explores on launches the long runs give up for
      * it once the shifted plan has settled: the shape's short runs take that one */
-    auto iu = nsol_pdk::g_plans.find(
-        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, 0});
-    if (iu == nsol_pdk::g_plans.end()) return 0;
-    nsol_pdk::plan_poll(iu->second, k);
-    return iu->second.chosen >= 0 ? 1 : 0;
+    E = find_plan(elem_size, k, nz, ny, nx, 0, 0);
+    if (!E) return 0;
+    plan_poll(*E, k);
   }
-  return it->second.chosen >= 0 ? 1 : 0;
+  return E->P.chosen >= 0 ? 1 : 0;
 }
 
 /* 1 when a run's trailing pair of iterations should go through depth 2 of k_pd_fusedk
@@ -2241,15 +1793,14 @@ extern "C" int nsol_pd_fusedk_tail2(int elem_size, int64_t nz, int64_t ny, int64
 }
 extern "C" int nsol_pd_fusedk_tail2_pitched(int elem_size, int64_t nz, int64_t ny, int64_t nx,
                                             int64_t pitch) {
-  if (!nsol_pdk::g_tunek.tail2 || !nsol_pdk::g_tunek.enable || nsol_pdk::g_tunek.kmax < 3 ||
-      nz * ny * nx < ((int64_t)nsol_pdk::g_tunek.tune_min_mvox << 20))
+  using namespace nsol_pdk;
+  if (!g_tunek.tail2 || !g_tunek.enable || g_tunek.kmax < 3 ||
+      nz * ny * nx < ((int64_t)g_tunek.tune_min_mvox << 20))
     return 0;                       /* (measured on volumes the online tuner handles) */
-  std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
   for (int form = 0; form < 2; ++form) {      /* either form's depth-3 plan */
-    auto it = nsol_pdk::g_plans.find(
-        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, 3, nz, ny, nx,
-                          pitch > nx ? pitch : 0, form});
-    if (it != nsol_pdk::g_plans.end() && it->second.chosen >= 0) return 1;
+    const Tuned *E = find_plan(elem_size, 3, nz, ny, nx, pitch > nx ? pitch : 0, form);
+    if (E && E->P.chosen >= 0) return 1;
   }
   return 0;
 }
@@ -2278,41 +1829,25 @@ int nsol_pd_shift_min_iters(int elem_size, int ndim, int64_t nz, int64_t ny, int
                             int flags, int64_t pitch) {
   if (flags & (NSOL_PD_REG_ISOTROPIC | NSOL_PD_DATA_WEIGHTED)) return 0;
   if (ndim != 3 || nz < 1 || ny < 1 || nx < 1) return 0;
-  if (elem_size == 4) return nsol_pdk::shift_min_iters_t<float>(ndim, nz, ny, nx, pitch);
-  if (elem_size == 8) return nsol_pdk::shift_min_iters_t<double>(ndim, nz, ny, nx, pitch);
-  return 0;
+  if (elem_size != 4 && elem_size != 8) return 0;
+  return nsol_pdk::shift_min_iters(elem_size, ndim, nz, ny, nx, pitch);
 }
 
 int nsol_pd_fusedk_plan_form(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
                              int form, int *waves, int *ntx, int64_t *zchunk) {
-  std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
-  auto it = nsol_pdk::g_plans.find(nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k,
-                                                     nz, ny, nx, 0, form ? 1 : 0});
-  if (it == nsol_pdk::g_plans.end()) return NSOL_EINVAL;
-  nsol_pdk::plan_poll(it->second, k);
-  if (it->second.chosen < 0) return NSOL_EINVAL;
-  const nsol_pdk::Config &c = it->second.cand[it->second.chosen];
-  if (waves) *waves = c.nw;
-  if (ntx) *ntx = c.q.ntx;
-  if (zchunk) *zchunk = c.zchunk;
-  return 0;
+  using namespace nsol_pdk;
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
+  Tuned *E = find_plan(elem_size, k, nz, ny, nx, 0, form ? 1 : 0);
+  if (E) plan_poll(*E, k);
+  return report_choice(E, waves, ntx, zchunk);
 }
 
 int nsol_pd_fusedk_plan(int elem_size, int k, int64_t nz, int64_t ny, int64_t nx,
                         int *waves, int *ntx, int64_t *zchunk) {
-  std::lock_guard<std::mutex> lock(nsol_pdk::g_plans_mutex);
-  const int form = (k == 3 && nsol_pdk::shift_shape_ok(elem_size, nz, ny, nx)) ? 1 : 0;
-  auto it = nsol_pdk::g_plans.find(
-      nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, form});
-  if (form && it == nsol_pdk::g_plans.end())      /* short runs only so far: see _tuned */
-    it = nsol_pdk::g_plans.find(
-        nsol_pdk::PlanKey{nsol_pdk::current_device(), elem_size, k, nz, ny, nx, 0, 0});
-  if (it == nsol_pdk::g_plans.end() || it->second.chosen < 0) return NSOL_EINVAL;
-  const nsol_pdk::Config &c = it->second.cand[it->second.chosen];
-  if (waves) *waves = c.nw;
-  if (ntx) *ntx = c.q.ntx;
-  if (zchunk) *zchunk = c.zchunk;
-  return 0;
+  using namespace nsol_pdk;
+  std::lock_guard<std::mutex> lock(g_plans_mutex);
+  bool shifted;
+  return report_choice(reported_plan(elem_size, k, nz, ny, nx, &shifted), waves, ntx, zchunk);
 }
 
 int nsol_pdk_block_map(int mode, int ntx, int nty, int nzc, int *out, int max_blocks) {
