@@ -1080,7 +1080,22 @@ int nsol_pdl_stack_iter_f64(const double *xbar_in, double *xbar_out, double *x,
  * than 2^31 voxels; NSOL_EINVAL for a missing pointer, two arguments of one call that
  * overlap, sigma, tau or beta that is not positive and finite, tl < 0; 0 at once when
  * an extent is 0.
- * nsol_tgv_launches: successful launches of the two kernels by this process. */
+ * nsol_tgv_primal_w_*: nsol_tgv_primal_* with per-voxel weights wt >= 0 (n values, one
+ *   more read-only stream) on the data term, lambda/2 sum wt_i (x_i - bt_i)^2 or lambda
+ *   sum wt_i |x_i - bt_i|:
+ *   x+   = prox_data_w(x - tau sum_a D_a^T p_a, bt, wt, tl)     (nsol_prox_ell*_weighted_*:
+ *          t = tl * wt; l2 (u + t bt) / (1 + t), an IEEE division in both types; wt == 0
+ *          keeps u, whatever bt holds there, NaN included)
+ *   flags: NSOL_PD_DATA_L1; any other bit is NSOL_EINVAL.
+ * nsol_tgv_primal_lin_*: the primal half of the iteration whose data term sits behind a
+ *   linear operator A (lambda D_wt(A x, bt); nsol_pdl_dual_data_* holds its dual r): g
+ *   (n values) = A^T r stands in bt's place and the x step is explicit, clipped to the box,
+ *   x+   = clip(x - tau (sum_a D_a^T p_a + g), lo, hi)          (nsol_pdl_iter_*'s step;
+ *          float32 rounds [lo, hi] towards its inside)
+ *   w, xbar and wbar as in nsol_tgv_primal_*.  lo <= hi, infinities allowed.
+ * Both: the returns of nsol_tgv_primal_*, with wt / g among the pointers; NSOL_EINVAL
+ * also for a theta that is not finite and for !(lo <= hi).
+ * nsol_tgv_launches: successful launches of these kernels by this process. */
 int nsol_tgv_launches(void);
 int nsol_tgv_dual_f32(const float *xbar, const float *wbar, float *p, float *q,
     int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
@@ -1096,6 +1111,22 @@ int nsol_tgv_primal_f64(const double *p, const double *q, double *x, double *xba
     double *w, double *wbar, const double *bt, int ndim, int64_t nz, int64_t ny,
     int64_t nx, double wx, double wy, double wz, double tau, double tl, double theta,
     int flags, void *stream);
+int nsol_tgv_primal_w_f32(const float *p, const float *q, float *x, float *xbar,
+    float *w, float *wbar, const float *bt, const float *wt, int ndim, int64_t nz,
+    int64_t ny, int64_t nx, double wx, double wy, double wz, double tau, double tl,
+    double theta, int flags, void *stream);
+int nsol_tgv_primal_w_f64(const double *p, const double *q, double *x, double *xbar,
+    double *w, double *wbar, const double *bt, const double *wt, int ndim, int64_t nz,
+    int64_t ny, int64_t nx, double wx, double wy, double wz, double tau, double tl,
+    double theta, int flags, void *stream);
+int nsol_tgv_primal_lin_f32(const float *p, const float *q, float *x, float *xbar,
+    float *w, float *wbar, const float *g, int ndim, int64_t nz, int64_t ny,
+    int64_t nx, double wx, double wy, double wz, double tau, double theta, double lo,
+    double hi, void *stream);
+int nsol_tgv_primal_lin_f64(const double *p, const double *q, double *x, double *xbar,
+    double *w, double *wbar, const double *g, int ndim, int64_t nz, int64_t ny,
+    int64_t nx, double wx, double wy, double wz, double tau, double theta, double lo,
+    double hi, void *stream);
 
 /* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253

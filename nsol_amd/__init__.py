@@ -24,6 +24,9 @@ def __getattr__(name):
     if name == "TGVPrimalDualSolver":
         from .tgv_solver import TGVPrimalDualSolver
         return TGVPrimalDualSolver
+    if name == "TGVPrimalDualLinearSolver":
+        from .tgv_solver import TGVPrimalDualLinearSolver
+        return TGVPrimalDualLinearSolver
     if name in ("PrimalDualLinearBatch", "PrimalDualLinearSweep"):
         from . import linear_stack
         return getattr(linear_stack, name)

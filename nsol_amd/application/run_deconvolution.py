@@ -1,4 +1,4 @@
-"""TK0L2 / TK1L2 / TVL2 / HuberL2 deconvolution from the command line
+"""TK0L2 / TK1L2 / TVL2 / HuberL2 / TGVL2 deconvolution from the command line
 (nsol_run_deconvolution of the reference, nsol/application/
 run_deconvolution.py:28-245 and the wiring of
 deconvolution_solver_parameter_study_interface.py:217-325, without plotting).
@@ -41,6 +41,15 @@ read on that fine grid; the start is sampled_start (A^T b / A^T 1).  --mask / --
 keep the observation's shape, --reference has the result's.  Not with --slice-wise or
 --result-dir, whose stacked forms need b and x on one grid.
 
+--solver PDL --reconstruction-type TGVL2 [--beta B]: second-order total generalised
+variation as the regulariser (TGVPrimalDualLinearSolver, nsol_amd/tgv_solver.py), which
+keeps the smooth ramps TV turns into terraces; B (default 2) weighs |E w|_1 against
+|grad x - w|_1.  It takes what the other PDL types take -- --data-loss ell1, --mask /
+--weights, --nonnegative, --isotropic, --tolerance / --check-every, --upsample /
+--sample-offset, --observe-every, --dtype; several --alpha loop -- except --result-dir
+and --slice-wise: there are no stacked TGV forms.  --L2 is not used, as for the other PDL
+types: the steps come from tgv_numpy.norm_bound_linear.
+
 With --reference, the measures are evaluated through an Observer on the flat
 iterates against the flat reference (as run_denoising does and as the
 reference's tool does) and printed as first -> last value.
@@ -63,6 +72,14 @@ from ..proximal_operators import ProximalOperators as prox
 from ..similarity_measures import SimilarityMeasures
 from .run_denoising import (classify_slices, last_observed, member_result_path,
                             print_stop, read_weights)
+
+
+def _regulariser(reconstruction_type):
+    """The solver's keyword arguments that name the regulariser: reg_type for TVL2 /
+    HuberL2 (PrimalDualLinearSolver); none for TGVL2, whose solver takes beta."""
+    if reconstruction_type == "TGVL2":
+        return {}
+    return dict(reg_type="TV" if reconstruction_type == "TVL2" else "huber")
 
 
 def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.01,
@@ -98,7 +115,7 @@ def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.
     return dict(
         A=A_1D, A_adj=A_adj_1D, b=b, x0=x0, dimension=dimension, spacing=spacing,
         alpha=alpha, iterations=iterations,
-        reg_type="TV" if reconstruction_type == "TVL2" else "huber",
+        **_regulariser(reconstruction_type),
         isotropic=isotropic, data_loss=pdl_data_loss, weights=weights,
         bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
         verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every)
@@ -154,7 +171,7 @@ def sampled_pdl_wiring(observed_nda, spacing, blur, factors, offsets=None,
     return dict(
         A=A_1D, A_adj=A_adj_1D, b=b, x0=x0, dimension=dimension, spacing=fine_spacing,
         alpha=alpha, iterations=iterations,
-        reg_type="TV" if reconstruction_type == "TVL2" else "huber",
+        **_regulariser(reconstruction_type),
         isotropic=isotropic, data_loss=pdl_data_loss, weights=weights,
         bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
         verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every,
@@ -166,10 +183,27 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  rho=0.1, minimizer="lsmr", data_loss="linear",
                  data_loss_scale=1., L2=8, verbose=0, dtype=None,
                  tolerance=None, check_every=10, weights=None, pdl_data_loss="ell2",
-                 nonnegative=False, upsample=None, sample_offset=None, isotropic=False):
+                 nonnegative=False, upsample=None, sample_offset=None, beta=2.0,
+                 isotropic=False):
     """weights, pdl_data_loss ("ell2" | "ell1") and nonnegative belong to
     tv_solver="PDL" (PrimalDualLinearSolver), and so do upsample / sample_offset (one
-    integer per array axis: the observation is the coarse data, sampled_pdl_wiring)."""
+    integer per array axis: the observation is the coarse data, sampled_pdl_wiring).
+    reconstruction_type "TGVL2" with tv_solver "PDL" is TGVPrimalDualLinearSolver on the
+    same wiring, with beta in the place of the regulariser's type."""
+    if reconstruction_type == "TGVL2":
+        if tv_solver != "PDL":
+            raise ValueError("reconstruction_type 'TGVL2' belongs to tv_solver='PDL'")
+        from ..tgv_solver import TGVPrimalDualLinearSolver
+        if upsample is not None:
+            kw = sampled_pdl_wiring(
+                observed_nda, spacing, blur, upsample, sample_offset, "TGVL2", alpha,
+                iterations, verbose, dtype, tolerance, check_every, weights,
+                pdl_data_loss, nonnegative, isotropic)
+        else:
+            kw = pdl_wiring(
+                observed_nda, spacing, blur, "TGVL2", alpha, iterations, verbose, dtype,
+                tolerance, check_every, weights, pdl_data_loss, nonnegative, isotropic)
+        return TGVPrimalDualLinearSolver(beta=beta, **kw)
     if upsample is not None:
         if not (reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL"):
             raise ValueError("upsample belongs to tv_solver='PDL'")
@@ -334,9 +368,9 @@ def run_slice_wise(args, observed_nda, spacing, x_ref, info, weights=None):
     return 0
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(
-        description="Run TK0L2/TK1L2/TVL2/HuberL2 deconvolution on an MI355X")
+        description="Run TK0L2/TK1L2/TVL2/HuberL2/TGVL2 deconvolution on an MI355X")
     ap.add_argument("--observation", required=True)
     ap.add_argument("--result", required=True)
     ap.add_argument("--reference", required=False)
@@ -345,7 +379,10 @@ def main(argv=None):
                     choices=sorted(SimilarityMeasures.similarity_measures))
     ap.add_argument("--blur", type=float, default=1.2)
     ap.add_argument("--reconstruction-type", default="TVL2",
-                    choices=["TK0L2", "TK1L2", "TVL2", "HuberL2"])
+                    choices=["TK0L2", "TK1L2", "TVL2", "HuberL2", "TGVL2"])
+    ap.add_argument("--beta", type=float, default=None, metavar="B",
+                    help="--solver PDL --reconstruction-type TGVL2: the weight of the "
+                         "second-order term |E w|_1 against |grad x - w|_1 (default 2)")
     ap.add_argument("--solver", default="PD", choices=["PD", "ADMM", "PDL"])
     ap.add_argument("--alpha", type=float, nargs="+", default=[0.01])
     ap.add_argument("--rho", type=float, default=0.1)
@@ -354,7 +391,10 @@ def main(argv=None):
     ap.add_argument("--minimizer", default="lsmr")
     ap.add_argument("--data-loss", default="linear")
     ap.add_argument("--data-loss-scale", type=float, default=1.)
-    ap.add_argument("--L2", type=float, default=8)
+    ap.add_argument("--L2", type=float, default=8,
+                    help="--solver PD: the bound of the operator norm its steps come "
+                         "from.  Not used by --solver PDL, TGVL2 included: there the steps "
+                         "come from the bound of the operator norms")
     ap.add_argument("--dtype", default="float32",
                     choices=["float32", "float64"])
     ap.add_argument("--verbose", type=int, default=0)
@@ -401,12 +441,33 @@ def main(argv=None):
     ap.add_argument("--check-every", type=int, default=10, metavar="K",
                     help="with --tolerance: evaluate the change every K iterations "
                          "and at the last")
+    return ap
+
+
+def parse_args(argv=None, ap=None):
+    """The checked arguments; a combination that is not taken is a parser error."""
+    ap = ap or build_parser()
     args = ap.parse_args(argv)
+    tgv = args.reconstruction_type == "TGVL2"
+    if tgv:
+        if args.solver != "PDL":
+            ap.error("--reconstruction-type TGVL2 is a form of --solver PDL "
+                     "(TGVPrimalDualLinearSolver), not of --solver %s" % args.solver)
+        if args.result_dir is not None or args.slice_wise:
+            ap.error("--reconstruction-type TGVL2 does not take %s: there are no "
+                     "stacked TGV forms; several --alpha loop" %
+                     ("--result-dir" if args.result_dir is not None else "--slice-wise"))
+        if args.beta is None:
+            args.beta = 2.0
+        if not (np.isfinite(args.beta) and args.beta > 0):
+            ap.error("--beta must be positive")
+    elif args.beta is not None:
+        ap.error("--beta goes with --reconstruction-type TGVL2")
     primal_dual = args.solver in ("PD", "PDL") and \
-        args.reconstruction_type in ("TVL2", "HuberL2")
+        args.reconstruction_type in ("TVL2", "HuberL2", "TGVL2")
     linear = args.solver == "PDL"
     if linear and not primal_dual:
-        ap.error("--solver PDL applies to --reconstruction-type TVL2 or HuberL2")
+        ap.error("--solver PDL applies to --reconstruction-type TVL2, HuberL2 or TGVL2")
     if linear and args.data_loss not in ("linear", "ell2", "ell1"):
         ap.error("--solver PDL takes --data-loss linear (the l2 data term) or ell1, "
                  "not '%s'" % args.data_loss)
@@ -459,6 +520,13 @@ def main(argv=None):
                 any(not 0 <= o < f for o, f in zip(offs, args.upsample)):
             ap.error("--sample-offset takes one offset per --upsample factor with "
                      "0 <= O < F")
+    return args
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = parse_args(argv, ap)
+    linear = args.solver == "PDL"
 
     reader = dr.DataReader(args.observation)
     reader.read_data()
@@ -498,8 +566,10 @@ def main(argv=None):
     if args.result_dir is not None:
         return run_sweep(args, observed_nda, spacing, x_ref, info, weights)
     # (without --upsample the call is what it was)
-    sampled = {} if args.upsample is None else dict(upsample=args.upsample,
-                                                    sample_offset=args.sample_offset)
+    extra = {} if args.upsample is None else dict(upsample=args.upsample,
+                                                  sample_offset=args.sample_offset)
+    if args.reconstruction_type == "TGVL2":
+        extra["beta"] = args.beta
     for alpha in args.alpha:
         solver = build_solver(
             observed_nda, spacing, args.blur, args.reconstruction_type,
@@ -508,7 +578,7 @@ def main(argv=None):
             args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic,
             tolerance=args.tolerance, check_every=args.check_every, weights=weights,
             pdl_data_loss="ell1" if args.data_loss == "ell1" else "ell2",
-            nonnegative=args.nonnegative, **sampled)
+            nonnegative=args.nonnegative, **extra)
         obs = None
         if x_ref is not None:
             obs = Observer.Observer() if args.observe_every is None else \

@@ -6,6 +6,7 @@
 
 #include "nsol_common.hpp"
 #include "nsol_pd_common.hpp"
+#include "nsol_pd_lin_step.hpp"
 #include "nsol_pd_weighted.hpp"
 
 namespace nsol {
@@ -32,16 +33,6 @@ __device__ __forceinline__ bool pd_fused_block_tile(int bid, int ntx, int nty, i
     zc = bid / nty;
   }
   return true;
-}
-
-// LIN: the explicit primal step of the iteration whose data term sits behind a linear
-// operator A (k_pd_lin, nsol_pdl.hip): kt = grad^T p as the tile formed it, g = A^T q,
-// their sum before the one multiplication by tau, then the projection onto [lo, hi].
-template <typename T>
-__device__ __forceinline__ T lin_step(T x, T kt, T g, T tau, T lo, T hi) {
-  const T u = x - tau * (kt + g);
-  const T c = u < lo ? lo : u;
-  return c > hi ? hi : c;
 }
 
 // One iteration on tile (tx, ty), z-chunk zc of one volume: each wave owns a

@@ -17,6 +17,9 @@
 //                 xbar = x+ + theta (x+ - x), wbar likewise
 //                 reads p, q and their backward neighbours, x, w, b~ at their own index;
 //                 writes x, w, xbar, wbar in place.
+//   k_tgv_primal_w, k_tgv_primal_lin: the same body with the weighted prox (one more
+//                 read-only stream wt) or, for a data term behind a linear operator A, the
+//                 explicit clipped step on g = A^T r in b~'s place (TgvForm below).
 //
 // No array is read at a neighbour and written in the same launch: no ping-pong buffers,
 // no dependency between workgroups.  The thread mapping is nsol_stencil.hpp's (k_grad /
@@ -33,6 +36,9 @@
 
 #include "nsol_common.hpp"
 #include "nsol_pd_iso_body.hpp"
+#include "nsol_pd_launch.hpp"
+#include "nsol_pd_lin_step.hpp"
+#include "nsol_pd_weighted.hpp"
 #include "nsol_stencil.hpp"
 
 using namespace nsol;
@@ -183,12 +189,19 @@ __global__ __launch_bounds__(kBlock) void k_tgv_dual(const T *__restrict__ xbar,
   }
 }
 
-template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO, bool L1>
-__global__ __launch_bounds__(kBlock) void k_tgv_primal(
+// The x step of k_tgv_primal comes in three forms that share everything else:
+//   kPlain  prox_data(u, b~): the denoising prox, all weights 1
+//   kWgt    prox_data_w(u, b~, wt) of nsol_pd_weighted.hpp: per-voxel weights, one more
+//           read-only stream (23 words per voxel in 3-D); wt == 0 keeps u
+//   kLin    lin_step(x, sum_a D_a^T p_a, g) of nsol_pd_lin_step.hpp: the array in b~'s
+//           place holds g = A^T r and the step is explicit, clipped to [lo, hi] (22 words)
+enum TgvForm { kPlain = 0, kWgt = 1, kLin = 2 };
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool L1, int FORM>
+__device__ __forceinline__ void tgv_primal_body(
     const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
-    const T *__restrict__ bt, Geom<T> G, T tau, T tl, T den, T theta) {
-  // (ISO does not change the primal step; it is a template parameter so that both
-  // kernels of one iteration are named by the same list)
+    const T *__restrict__ bt, const T *__restrict__ wt, const Geom<T> &G, T tau, T tl,
+    T den, T theta, T lo, T hi) {
   const int64_t nrg = row_groups<T, VEC, ROWS>(G);
   for (int64_t rg = blockIdx.y; rg < nrg; rg += gridDim.y) {
     const Voxel c = voxel_at<T, VEC, ROWS>(G, rg);
@@ -204,9 +217,16 @@ __global__ __launch_bounds__(kBlock) void k_tgv_primal(
     }
     vlc<RAG, T, VEC>(c, x + c.i, v);
     vlc<RAG, T, VEC>(c, bt + c.i, t);
+    if constexpr (FORM == kWgt) vlc<RAG, T, VEC>(c, wt + c.i, own);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      const T xn = prox_data<T>(v[k] - tau * acc[k], t[k], tl, den, L1);
+      T xn;
+      if constexpr (FORM == kLin)
+        xn = lin_step<T>(v[k], acc[k], t[k], tau, lo, hi);
+      else if constexpr (FORM == kWgt)
+        xn = prox_data_w<T>(v[k] - tau * acc[k], t[k], own[k], tl, L1);
+      else
+        xn = prox_data<T>(v[k] - tau * acc[k], t[k], tl, den, L1);
       o[k] = xn + theta * (xn - v[k]);
       v[k] = xn;
     }
@@ -237,6 +257,32 @@ __global__ __launch_bounds__(kBlock) void k_tgv_primal(
       vs<RAG, T, VEC>(c.nval, wbar + a * G.n + c.i, o);
     }
   }
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO, bool L1>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ bt, Geom<T> G, T tau, T tl, T den, T theta) {
+  // (ISO does not change the primal step; it is a template parameter so that both
+  // kernels of one iteration are named by the same list)
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, L1, kPlain>(p, q, x, xbar, w, wbar, bt, nullptr,
+                                                       G, tau, tl, den, theta, T(0), T(0));
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool L1>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal_w(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ bt, const T *__restrict__ wt, Geom<T> G, T tau, T tl, T theta) {
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, L1, kWgt>(p, q, x, xbar, w, wbar, bt, wt, G, tau,
+                                                     tl, T(0), theta, T(0), T(0));
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal_lin(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ g, Geom<T> G, T tau, T theta, T lo, T hi) {
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, false, kLin>(p, q, x, xbar, w, wbar, g, nullptr,
+                                                        G, tau, T(0), T(0), theta, lo, hi);
 }
 
 // ---------------------------------------------------------------------------
@@ -356,6 +402,69 @@ int tgv_primal_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, const 
   });
 }
 
+template <typename T>
+int tgv_primal_w_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, const T *bt,
+                      const T *wt, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,
+                      double wy, double wz, double tau, double tl, double theta, int flags,
+                      void *stream) {
+  if (flags & ~NSOL_PD_DATA_L1) return NSOL_EINVAL;
+  const int gr = tgv_geometry(ndim, nz, ny, nx, flags);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t nb = nz * ny * nx * (int64_t)sizeof(T), M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{p, ndim * nb}, {q, M * nb},       {x, nb},  {xbar, nb},
+                        {w, ndim * nb}, {wbar, ndim * nb}, {bt, nb}, {wt, nb}};
+  if (spans_bad(spans) || !positive(tau) || !(isfinite(tl) && tl >= 0.0) ||
+      !isfinite(theta))
+    return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(p) && aligned16(q) && aligned16(x) && aligned16(xbar) &&
+                  aligned16(w) && aligned16(wbar) && aligned16(bt) && aligned16(wt);
+  const hipStream_t st = as_stream(stream);
+  const bool l1 = (flags & NSOL_PD_DATA_L1) != 0;
+  return tgv_dispatch<T>(ndim, nz, ny, nx, al, [&](auto vec, auto rows, auto rag, auto nd) {
+    constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+    constexpr int D = decltype(nd)::value;
+    constexpr bool RG = decltype(rag)::value;
+    const dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+    if (l1)
+      hipLaunchKernelGGL((k_tgv_primal_w<T, V, R, D, RG, true>), grid, dim3(kBlock), 0, st,
+                         p, q, x, xbar, w, wbar, bt, wt, G, (T)tau, (T)tl, (T)theta);
+    else
+      hipLaunchKernelGGL((k_tgv_primal_w<T, V, R, D, RG, false>), grid, dim3(kBlock), 0, st,
+                         p, q, x, xbar, w, wbar, bt, wt, G, (T)tau, (T)tl, (T)theta);
+    return launch_status();
+  });
+}
+
+template <typename T>
+int tgv_primal_lin_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, const T *g,
+                        int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+                        double wz, double tau, double theta, double lo, double hi,
+                        void *stream) {
+  const int gr = tgv_geometry(ndim, nz, ny, nx, 0);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t nb = nz * ny * nx * (int64_t)sizeof(T), M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{p, ndim * nb}, {q, M * nb},       {x, nb}, {xbar, nb},
+                        {w, ndim * nb}, {wbar, ndim * nb}, {g, nb}};
+  if (spans_bad(spans) || !positive(tau) || !isfinite(theta) || !(lo <= hi))
+    return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(p) && aligned16(q) && aligned16(x) && aligned16(xbar) &&
+                  aligned16(w) && aligned16(wbar) && aligned16(g);
+  const hipStream_t st = as_stream(stream);
+  T l, h;
+  box_in<T>(lo, hi, l, h);
+  return tgv_dispatch<T>(ndim, nz, ny, nx, al, [&](auto vec, auto rows, auto rag, auto nd) {
+    constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+    constexpr int D = decltype(nd)::value;
+    constexpr bool RG = decltype(rag)::value;
+    const dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+    hipLaunchKernelGGL((k_tgv_primal_lin<T, V, R, D, RG>), grid, dim3(kBlock), 0, st, p, q,
+                       x, xbar, w, wbar, g, G, (T)tau, (T)theta, l, h);
+    return launch_status();
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -375,6 +484,20 @@ int nsol_tgv_launches(void) { return g_tgv_launches.load(std::memory_order_relax
                             double theta, int flags, void *s) {                           \
     return tgv_primal_impl<T>(p, q, x, xbar, w, wbar, bt, ndim, nz, ny, nx, wx, wy, wz,   \
                               tau, tl, theta, flags, s);                                  \
+  }                                                                                       \
+  int nsol_tgv_primal_w_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,       \
+                              const T *bt, const T *wt, int ndim, int64_t nz, int64_t ny, \
+                              int64_t nx, double wx, double wy, double wz, double tau,    \
+                              double tl, double theta, int flags, void *s) {              \
+    return tgv_primal_w_impl<T>(p, q, x, xbar, w, wbar, bt, wt, ndim, nz, ny, nx, wx, wy, \
+                                wz, tau, tl, theta, flags, s);                            \
+  }                                                                                       \
+  int nsol_tgv_primal_lin_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,     \
+                                const T *g, int ndim, int64_t nz, int64_t ny, int64_t nx, \
+                                double wx, double wy, double wz, double tau,              \
+                                double theta, double lo, double hi, void *s) {            \
+    return tgv_primal_lin_impl<T>(p, q, x, xbar, w, wbar, g, ndim, nz, ny, nx, wx, wy,    \
+                                  wz, tau, theta, lo, hi, s);                             \
   }
 
 NSOL_TGV_DEF(float, f32)

@@ -1893,6 +1893,43 @@ def tgv_primal(p, q, x, xbar, w_field, wbar, bt, shape, w, tau, tl, theta=1., fl
     return True
 
 
+def tgv_primal_w(p, q, x, xbar, w_field, wbar, bt, wt, shape, w, tau, tl, theta=1.,
+                 flags=0):
+    """tgv_primal with per-voxel weights wt >= 0 on the data term: x <- prox_data_w(x -
+    tau grad^T p, bt, wt, tl); a voxel with wt == 0 keeps its u, whatever bt holds there.
+    flags: PD_DATA_L1.  Returns False when the library declined the geometry (nothing was
+    launched).  Does not synchronise."""
+    _same(x, xbar, bt, wt)
+    ndim, nz, ny, nx = _tgv_operands(shape, x, (p, w_field, wbar), (q,))
+    rc = _fn("tgv_primal_w", x)(
+        _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(bt), _p(wt), ndim, nz, ny,
+        nx, w[0], w[1], w[2], float(tau), float(tl), float(theta), int(flags),
+        stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_primal_w")
+    _wrote(x, xbar, w_field, wbar)
+    return True
+
+
+def tgv_primal_lin(p, q, x, xbar, w_field, wbar, g, shape, w, tau, theta=1., lo=-np.inf,
+                   hi=np.inf):
+    """The primal half behind a linear operator: x <- clip(x - tau (grad^T p + g), lo, hi)
+    with g = A^T r in bt's place (pdl_iter's step), w_field and the bars as in tgv_primal.
+    Returns False when the library declined the geometry (nothing was launched).  Does
+    not synchronise."""
+    _same(x, xbar, g)
+    ndim, nz, ny, nx = _tgv_operands(shape, x, (p, w_field, wbar), (q,))
+    rc = _fn("tgv_primal_lin", x)(
+        _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(g), ndim, nz, ny, nx,
+        w[0], w[1], w[2], float(tau), float(theta), float(lo), float(hi), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_primal_lin")
+    _wrote(x, xbar, w_field, wbar)
+    return True
+
+
 # ------------------------------ the same, member-stacked (nsol_pdls.hip) ----
 # An alpha sweep on one observation or a stack of images of one shape
 # (nsol_amd/linear_stack.py).  A member's state is x, two xbar, q, g = A^T q and two p

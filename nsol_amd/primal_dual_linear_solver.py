@@ -116,16 +116,65 @@ class _LinearStopRule(_StopRule):
         return criterion_met(r_x, r_d, self.tolerance)
 
 
-class PrimalDualLinearSolver(Stopping, Solver):
+class _DataSide:
+    """The data term's side of one run of a _LinearDataTermSolver: A and A^T in the run's execution form, and
+    the dual step q <- prox(q + sigma (A xbar - b~)) followed by g = A^T q."""
+
+    def __init__(self, solver, x):
+        import torch
+        s = self._solver = solver
+        self._fused = s._op is not None
+        if self._fused:
+            self._A = lambda t: s._op._apply(t, s._op_shape)
+            self._At = lambda t: s._op_adj._apply(t, s._op_adj_shape)
+        else:
+            self._A = BridgedCallable(s._A, s._dtype)
+            self._At = BridgedCallable(s._A_adj, s._dtype)
+        # q <- sigma A xbar + q as the epilogue of the one-pass blur, while it applies
+        self._epilogue = self._fused and isinstance(s._op, ConvolutionOperator) and \
+            s._m == s._n and linear_operators.USE_BLUR_EPILOGUE
+        self._slot = torch.empty(1, dtype=torch.float64, device=x.device) \
+            if self._epilogue else None
+
+    def dual_step(self, xbar, q, bt, wt, sigma, lmbda, l1):
+        """q in place; returns g = A^T q (n values)."""
+        s = self._solver
+        if self._epilogue and s._op.apply_axpby(xbar, q, s._op_shape, sigma, 1.,
+                                                result=self._slot) is None:
+            self._epilogue = False     # the kernel declined: nothing ran, q is intact
+        if self._epilogue:
+            ops.pdl_dual_data(q, None, bt, wt, sigma, lmbda, l1)
+        else:
+            t = self._A(xbar)
+            if t.numel() != s._m:
+                raise ValueError("A returned %d values, b holds %d" %
+                                 (t.numel(), s._m))
+            ops.pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1)
+        g = self._At(q)
+        if g.numel() != s._n:
+            raise ValueError("A_adj returned %d values, x holds %d" % (g.numel(), s._n))
+        return g
+
+    def finish(self):
+        """Records 'device' or 'host' for callables that are not this package's."""
+        if not self._fused:
+            A, At = self._A, self._At
+            self._solver._execution = "device" if (
+                A.on_device in (True, None) and At.on_device in (True, None)) else "host"
+
+
+class _LinearDataTermSolver(Stopping, Solver):
+    """What the solvers with a data term behind a linear operator A share, whatever
+    their regulariser (PrimalDualLinearSolver below, tgv_solver.TGVPrimalDualLinearSolver):
+    the checked arguments, the operators behind the caller's lambdas, the volume's shape,
+    weights, the box, A_norm2 and the step sizes.  A subclass supplies _default_L2 (its
+    bound of |K|^2) and _run, which takes the data side of an iteration from _DataSide."""
 
     def __init__(self, A, A_adj, b, x0, dimension, spacing=None, alpha=0.01,
-                 iterations=10, reg_type="TV", huber_gamma=0.05, isotropic=False,
-                 data_loss="ell2", weights=None, bounds=None, A_norm2=None, L2=None,
-                 tau=None, sigma=None, x_scale=1., verbose=0, dtype=None,
-                 tolerance=None, check_every=10, shape=None):
+                 iterations=10, isotropic=False, data_loss="ell2", weights=None,
+                 bounds=None, A_norm2=None, L2=None, tau=None, sigma=None, x_scale=1.,
+                 verbose=0, dtype=None, tolerance=None, check_every=10, shape=None):
         Solver.__init__(self, x0=x0, verbose=verbose, x_scale=x_scale, dtype=dtype)
-        if reg_type not in REG_TYPES:
-            raise ValueError("reg_type must be one of %r" % (REG_TYPES,))
         if data_loss not in DATA_LOSSES:
             raise ValueError("data_loss must be one of %r" % (DATA_LOSSES,))
         dimension = int(dimension)
@@ -141,7 +190,6 @@ class PrimalDualLinearSolver(Stopping, Solver):
         if not self._alpha > 0:
             raise ValueError("alpha must be positive")
         self._iterations = iterations
-        self._reg_type, self._huber_gamma = reg_type, float(huber_gamma)
         self._isotropic = bool(isotropic)
         self._data_loss = data_loss
         self._bounds = checked_bounds(bounds)
@@ -175,11 +223,14 @@ class PrimalDualLinearSolver(Stopping, Solver):
         if not (np.isfinite(self._A_norm2) and self._A_norm2 >= 0):
             raise ValueError("A_norm2 must be a finite number >= 0")
         if L2 is None:
-            L2 = float(np.sum(4. / self._spacing ** 2)) + self._A_norm2
+            L2 = self._default_L2()
         self._L2 = float(L2)
         self._tau, self._sigma = step_sizes(self._L2, tau, sigma)
         self._theta = 1.
         self._execution = "fused" if self._op is not None else None
+
+    def _default_L2(self):
+        raise NotImplementedError
 
     @staticmethod
     def _is_own(desc, n_in, n_out, dimension):
@@ -218,6 +269,28 @@ class PrimalDualLinearSolver(Stopping, Solver):
     def print_statistics(self, fmt="%.3e"):
         pass
 
+
+class PrimalDualLinearSolver(_LinearDataTermSolver):
+
+    def __init__(self, A, A_adj, b, x0, dimension, spacing=None, alpha=0.01,
+                 iterations=10, reg_type="TV", huber_gamma=0.05, isotropic=False,
+                 data_loss="ell2", weights=None, bounds=None, A_norm2=None, L2=None,
+                 tau=None, sigma=None, x_scale=1., verbose=0, dtype=None,
+                 tolerance=None, check_every=10, shape=None):
+        if reg_type not in REG_TYPES:
+            raise ValueError("reg_type must be one of %r" % (REG_TYPES,))
+        self._reg_type, self._huber_gamma = reg_type, float(huber_gamma)
+        _LinearDataTermSolver.__init__(
+            self, A, A_adj, b, x0, dimension, spacing=spacing, alpha=alpha,
+            iterations=iterations, isotropic=isotropic, data_loss=data_loss,
+            weights=weights, bounds=bounds, A_norm2=A_norm2, L2=L2, tau=tau, sigma=sigma,
+            x_scale=x_scale, verbose=verbose, dtype=dtype, tolerance=tolerance,
+            check_every=check_every, shape=shape)
+
+    def _default_L2(self):
+        """|grad|^2 + |A|^2 bounds |(grad, A)|^2."""
+        return float(np.sum(4. / self._spacing ** 2)) + self._A_norm2
+
     # ------------------------------------------------------------------
     def _flags(self):
         flags = ops.PD_REG_HUBER if self._reg_type == "huber" else ops.PD_REG_TV
@@ -244,17 +317,7 @@ class PrimalDualLinearSolver(Stopping, Solver):
         if rule is not None:
             rule.allocate(x)
 
-        fused = self._op is not None
-        if fused:
-            A = lambda t: self._op._apply(t, self._op_shape)
-            At = lambda t: self._op_adj._apply(t, self._op_adj_shape)
-        else:
-            A = BridgedCallable(self._A, self._dtype)
-            At = BridgedCallable(self._A_adj, self._dtype)
-        # q <- sigma A xbar + q as the epilogue of the one-pass blur, while it applies
-        epilogue = fused and isinstance(self._op, ConvolutionOperator) and m == n and \
-            linear_operators.USE_BLUR_EPILOGUE
-        slot = torch.empty(1, dtype=torch.float64, device=x.device) if epilogue else None
+        data = _DataSide(self, x)
 
         shape, w = self._shape, ops.inv_spacing(self._spacing, self._dimension)
         flags = self._flags()
@@ -271,20 +334,7 @@ class PrimalDualLinearSolver(Stopping, Solver):
             check = rule is not None and rule.is_point(i + 1)
             if check:
                 x_old, q_old = x.clone(), q.clone()
-            if epilogue and self._op.apply_axpby(xbar[k], q, self._op_shape, sigma, 1.,
-                                                 result=slot) is None:
-                epilogue = False       # the kernel declined: nothing ran, q is intact
-            if epilogue:
-                ops.pdl_dual_data(q, None, bt, wt, sigma, lmbda, l1)
-            else:
-                t = A(xbar[k])
-                if t.numel() != m:
-                    raise ValueError("A returned %d values, b holds %d" %
-                                     (t.numel(), m))
-                ops.pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1)
-            g = At(q)
-            if g.numel() != n:
-                raise ValueError("A_adj returned %d values, x holds %d" % (g.numel(), n))
+            g = data.dual_step(xbar[k], q, bt, wt, sigma, lmbda, l1)
             if not ops.pdl_iter(xbar[k], xbar[1 - k], x, g, p[k], p[1 - k], shape, w,
                                 sigma, hden, tau, theta, lo, hi, flags, has_p=i > 0):
                 raise ValueError("nsol_pdl_iter does not take a volume of shape %r" %
@@ -302,14 +352,12 @@ class PrimalDualLinearSolver(Stopping, Solver):
         self._x = x
         if rule is None:
             self._iterations_done = iters
-        if not fused:
-            self._execution = "device" if (A.on_device in (True, None) and
-                                           At.on_device in (True, None)) else "host"
+        data.finish()
 
 
-add_accessors(PrimalDualLinearSolver,
-              ["alpha", "iterations", "huber_gamma", "reg_type", "data_loss"])
-add_accessors(PrimalDualLinearSolver,
+add_accessors(_LinearDataTermSolver, ["alpha", "iterations", "data_loss"])
+add_accessors(PrimalDualLinearSolver, ["huber_gamma", "reg_type"])
+add_accessors(_LinearDataTermSolver,
               ["A", "A_adj", "dimension", "spacing", "isotropic", "bounds", "A_norm2",
                "L2", "tau", "sigma", "theta", "shape"],
               setters=False)

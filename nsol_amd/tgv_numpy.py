@@ -20,6 +20,8 @@ Arrays: x `shape`, w and p (d,) + shape, q (M,) + shape.
 """
 import numpy as np
 
+from . import vector_numpy
+
 DATA_LOSSES = ("ell2", "ell1")
 
 
@@ -186,6 +188,60 @@ def primal_step(p, q, x, w, b, tau, tl, theta=1., spacing=None, data_loss="ell2"
     return xn, xn + theta * (xn - x), wn, wn + theta * (wn - w)
 
 
+def primal_step_weighted(p, q, x, w, b, wt, tau, tl, theta=1., spacing=None,
+                         data_loss="ell2"):
+    """primal_step with per-voxel weights wt >= 0 on the data term (k_tgv_primal's WGT
+    form): the data prox is vector_numpy.prox_data_w, which keeps u where wt == 0,
+    whatever b holds there."""
+    dt = x.dtype.type
+    tau, theta = dt(tau), dt(theta)
+    kx, kw = K_adj(p, q, spacing)
+    xn = vector_numpy.prox_data_w(x - tau * kx, b, wt, tl, data_loss == "ell1",
+                                  x.dtype).astype(dt)
+    wn = w - tau * kw
+    return xn, xn + theta * (xn - x), wn, wn + theta * (wn - w)
+
+
+def primal_step_lin(p, q, x, w, g, tau, theta=1., lo=-np.inf, hi=np.inf, spacing=None,
+                    dtype=None):
+    """The primal half behind a linear operator (k_tgv_primal's LIN form): g = A^T r and
+    x+ = vector_numpy.pd_lin_step(x, sum_a D_a^T p_a, g): the explicit step, clipped to
+    box_in(lo, hi) as the kernel of element type `dtype` (default: x's) sees the box."""
+    dt = x.dtype.type
+    kx, kw = K_adj(p, q, spacing)
+    xn = vector_numpy.pd_lin_step(x, kx, g, tau, lo, hi, dtype or x.dtype).astype(dt)
+    tau, theta = dt(tau), dt(theta)
+    wn = w - tau * kw
+    return xn, xn + theta * (xn - x), wn, wn + theta * (wn - w)
+
+
+def norm_bound_linear(dimension, spacing=None, A_norm2=0.):
+    """An upper bound of |K|^2 for K(x, w) = (grad x - w, E w, A x) with |A|^2 <= a =
+    A_norm2: |K(x, w)|^2 <= (g + a) |x|^2 + 2 sqrt(g) |x| |w| + (1 + g) |w|^2, so the
+    largest eigenvalue of [[g + a, sqrt g], [sqrt g, 1 + g]],
+    ((2 g + a + 1) + sqrt((a - 1)^2 + 4 g)) / 2 with g = 4 sum 1/h_a^2.  a = 0 is
+    norm_bound, bit for bit."""
+    sp = np.ones(dimension) if spacing is None else np.atleast_1d(spacing).astype(float)
+    g = 4. * float(np.sum(1. / sp ** 2))
+    a = float(A_norm2)
+    return ((2. * g + a + 1.) + np.sqrt((a - 1.) ** 2 + 4. * g)) / 2.
+
+
+def energy_linear(x, w, Ax, b, lmbda, beta, spacing=None, data_loss="ell2",
+                  isotropic=False, weights=None):
+    """lmbda D_wt(A x, b) + |grad x - w|_1 + beta |E w|_1 (float64); Ax is A applied to x.
+    Samples of weight 0 do not enter, whatever b holds there.  (The box is a constraint:
+    it is not part of the value.)"""
+    x, w = (np.asarray(t, dtype=np.float64) for t in (x, w))
+    reg = energy(x, w, x, 1., beta, spacing, "ell2", isotropic)    # x - x: no data term
+    r = np.asarray(Ax, dtype=np.float64).ravel() - np.asarray(b, dtype=np.float64).ravel()
+    wt = np.ones_like(r) if weights is None else \
+        np.asarray(weights, dtype=np.float64).ravel()
+    r = np.where(wt == 0, 0., r)
+    data = np.sum(wt * np.abs(r)) if data_loss == "ell1" else 0.5 * np.sum(wt * r * r)
+    return float(lmbda * data + reg)
+
+
 def _ratio(num, den):
     if num == 0.:
         return 0.
@@ -194,19 +250,88 @@ def _ratio(num, den):
     return float(np.sqrt(num / den))
 
 
+def _sq(*arrs):
+    return float(sum(np.sum(np.asarray(t, dtype=np.float64) ** 2) for t in arrs))
+
+
+def iterate_linear(A, A_adj, b, x0, iterations, alpha, beta=2., spacing=None,
+                   data_loss="ell2", isotropic=False, tau=None, sigma=None, theta=1.,
+                   L2=None, dtype=None, keep=False, weights=None, bounds=None,
+                   A_norm2=None):
+    """`iterations` iterations of the TGV iteration whose data term sits behind a linear
+    operator, lmbda D_wt(A x, b) + |grad x - w|_1 + beta |E w|_1 + indicator_[lo, hi](x),
+    from x = xbar = x0, w = wbar = p = q = r = 0.  A and A_adj are callables on arrays: A
+    takes an array of x0's shape and returns the m values of b (any shape), A_adj the
+    reverse.  weights: m values >= 0 or None (all 1); bounds: (lo, hi) or None; A_norm2:
+    an upper bound of |A|^2, required unless L2 is given.  One iteration:
+
+        (p, q) <- dual_step(xbar, wbar, p, q)
+        r      <- vector_numpy.pdl_dual_data(r, A xbar, b, weights, sigma, lmbda, l1)
+        (x, xbar, w, wbar) <- primal_step_lin(p, q, x, w, A_adj r, tau, theta, lo, hi)
+
+    Returns what iterate returns plus r; the primal ratio runs over (x, w), the dual one
+    over (p, q, r)."""
+    if data_loss not in DATA_LOSSES:
+        raise ValueError("data_loss must be one of %r" % (DATA_LOSSES,))
+    dt = np.dtype(dtype or np.asarray(b).dtype).type
+    b = np.asarray(b, dtype=dt)
+    x = np.array(x0, dtype=dt)
+    d = x.ndim
+    if L2 is None:
+        if A_norm2 is None:
+            raise ValueError("A_norm2 (an upper bound of |A|^2) or L2 is required")
+        L2 = norm_bound_linear(d, spacing, A_norm2)
+    if tau is None and sigma is None:
+        tau = sigma = 1. / np.sqrt(L2)
+    elif tau is None:
+        tau = 1. / (L2 * sigma)
+    elif sigma is None:
+        sigma = 1. / (L2 * tau)
+    lmbda = 1. / alpha
+    lo, hi = (-np.inf, np.inf) if bounds is None else (float(bounds[0]), float(bounds[1]))
+    wt = None if weights is None else np.asarray(weights, dtype=dt).reshape(b.shape)
+    w = np.zeros((d,) + x.shape, dtype=dt)
+    p = np.zeros((d,) + x.shape, dtype=dt)
+    q = np.zeros((components(d),) + x.shape, dtype=dt)
+    r = np.zeros(b.shape, dtype=dt)
+    xbar, wbar = x.copy(), w.copy()
+    ratios, iterates = [], [x.copy()]
+    for k in range(1, int(iterations) + 1):
+        pn, qn = dual_step(xbar, wbar, p, q, sigma, beta, spacing, isotropic)
+        t = np.asarray(A(xbar), dtype=dt).reshape(b.shape)
+        rn = vector_numpy.pdl_dual_data(r, t, b, wt, sigma, lmbda, data_loss == "ell1",
+                                        dt).astype(dt)
+        g = np.asarray(A_adj(rn), dtype=dt).reshape(x.shape)
+        xn, xbar, wn, wbar = primal_step_lin(pn, qn, x, w, g, tau, theta, lo, hi, spacing,
+                                             dt)
+        ratios.append((float(k),
+                       _ratio(_sq(xn - x, wn - w), _sq(xn, wn)),
+                       _ratio(_sq(pn - p, qn - q, rn - r), _sq(pn, qn, rn))))
+        x, w, p, q, r = xn, wn, pn, qn, rn
+        if keep:
+            iterates.append(x.copy())
+    out = dict(x=x, w=w, p=p, q=q, r=r, tau=float(tau), sigma=float(sigma),
+               ratios=np.array(ratios, dtype=np.float64).reshape(-1, 3))
+    if keep:
+        out["iterates"] = iterates
+    return out
+
+
 def iterate(b, x0, iterations, alpha, beta=2., spacing=None, data_loss="ell2",
             isotropic=False, tau=None, sigma=None, theta=1., L2=None, dtype=None,
-            keep=False):
+            keep=False, weights=None):
     """`iterations` iterations from x = xbar = x0, w = wbar = p = q = 0 on arrays in the
     scaled units (b and x0 of the volume's shape).  Returns a dict: x, w, p, q (the last
     iterate), ratios (one row (k, r_primal, r_dual) per iteration: the stopping rule's
     r = sqrt(sum (v_k - v_{k-1})^2 / sum v_k^2) over (x, w) and over (p, q)), tau, sigma,
-    and with keep the list `iterates` of every x, the start included."""
+    and with keep the list `iterates` of every x, the start included.  weights: per-voxel
+    weights >= 0 of the data term (primal_step_weighted) or None, the unweighted step."""
     if data_loss not in DATA_LOSSES:
         raise ValueError("data_loss must be one of %r" % (DATA_LOSSES,))
     dt = np.dtype(dtype or np.asarray(b).dtype).type
     b = np.asarray(b, dtype=dt)
     x = np.array(x0, dtype=dt).reshape(b.shape)
+    wt = None if weights is None else np.asarray(weights, dtype=dt).reshape(b.shape)
     d = b.ndim
     if L2 is None:
         L2 = norm_bound(d, spacing)
@@ -223,13 +348,16 @@ def iterate(b, x0, iterations, alpha, beta=2., spacing=None, data_loss="ell2",
     xbar, wbar = x.copy(), w.copy()
     ratios, iterates = [], [x.copy()]
 
-    def sq(*arrs):
-        return float(sum(np.sum(np.asarray(t, dtype=np.float64) ** 2) for t in arrs))
-
+    sq = _sq
     for k in range(1, int(iterations) + 1):
         pn, qn = dual_step(xbar, wbar, p, q, sigma, beta, spacing, isotropic)
-        xn, xbar, wn, wbar = primal_step(pn, qn, x, w, b, tau, tau * lmbda, theta,
-                                         spacing, data_loss)
+        if wt is None:
+            xn, xbar, wn, wbar = primal_step(pn, qn, x, w, b, tau, tau * lmbda, theta,
+                                             spacing, data_loss)
+        else:
+            xn, xbar, wn, wbar = primal_step_weighted(pn, qn, x, w, b, wt, tau,
+                                                      tau * lmbda, theta, spacing,
+                                                      data_loss)
         ratios.append((float(k),
                        _ratio(sq(xn - x, wn - w), sq(xn, wn)),
                        _ratio(sq(pn - p, qn - q), sq(pn, qn))))

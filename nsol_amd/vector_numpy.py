@@ -353,7 +353,7 @@ def box_in(lo, hi, dtype=np.float64):
 
 
 def pd_lin_step(x, kt, g, tau, lo, hi, dtype=np.float64):
-    """lin_step of csrc/nsol_pd_fused_body.hpp: u = x - tau * (kt + g), then
+    """lin_step of csrc/nsol_pd_lin_step.hpp: u = x - tau * (kt + g), then
     c = u < lo ? lo : u and c > hi ? hi : c on the box box_in(lo, hi): the selects as the
     kernel makes them (u == lo keeps u, so -0.0 stays -0.0 on lo = 0)."""
     lo, hi = box_in(lo, hi, dtype)
