@@ -1476,7 +1476,9 @@ int nsol_observe_widen_f64(double *out, const double *x, double x_scale, int64_t
  * vectors in ONE pass over them -- the Y'ZZ'Y, S'ZZ'S and S'ZZ'Y blocks of the
  * subspace matrix (2c^2 + c masked dots for c stored pairs).  vecs is a HOST
  * array of nvec device pointers (16-byte aligned); ws holds at least
- * nsol_lb_gram_ws_doubles() doubles. */
+ * nsol_lb_gram_ws_doubles() doubles.  A variable that is not free contributes
+ * nothing, whatever is stored there (NaN and Inf included), in every kernel that
+ * forms the sum and in the products and the gradient of nsol_lb_masked_gram_rgrad_*. */
 /* mdots: result[k] = sum over the free variables of vecs[k] * y, k < nvec, with y
  * and the mask read once (W^T v of the compact L-BFGS representation).  vecs is
  * a HOST array of device pointers; ws: nsol_lb_gram_ws_doubles() doubles. */
@@ -1535,6 +1537,12 @@ int nsol_lb_subspace_step_r_f64(const double *const *w_host, const double *wcoef
                                 double hi, double *xn, double *d, double *result, double *ws,
                                 void *stream);
 int64_t nsol_lb_gram_ws_doubles(void);
+/* Three kernels form the masked_gram sum, and a launcher that declines hands the call
+ * to the next one without a word: launches this process has made of form 0 (k_masked_gram,
+ * staged through registers), 1 (k_masked_gram_dma, staged by LDS-DMA) or 2
+ * (k_masked_gram_mfma, the products on the matrix cores); -1 for another form.
+ * For tests and tools that must know which kernel a call went through. */
+int nsol_lb_gram_launches(int form);
 int nsol_lb_masked_gram_f32(const float *const *vecs, int nvec, const int8_t *iwhere,
                             int64_t n, double *result, double *ws, void *stream);
 int nsol_lb_masked_gram_f64(const double *const *vecs, int nvec, const int8_t *iwhere,

@@ -11,6 +11,8 @@
 
 #include <string.h>
 
+#include <atomic>
+
 #include "nsol_common.hpp"
 
 using namespace nsol;
@@ -310,6 +312,9 @@ template <typename T> constexpr int gram_tile() { return 4096 / (int)sizeof(T); 
 constexpr int kGramBlocks = 512;
 constexpr int kGramMaxVec = 24;                 // 8 x 8 blocks of 3 x 3 pairs
 constexpr int kGramEnt = 36 * 9;                // block entries one workgroup writes
+// launches of k_masked_gram / k_masked_gram_dma / k_masked_gram_mfma by this process
+// (nsol_lb_gram_launches: a launcher that declines hands the call on silently)
+std::atomic<int> g_gram_launches[3];
 
 template <typename T>
 struct GramPtrs {
@@ -458,7 +463,8 @@ __global__ __launch_bounds__(kBlock) void k_gram_final(const double *ws, int nbl
 // s_waitcnt vmcnt(N) leaves the newer one in flight across the barrier) while step
 // t is multiplied; a thread owns a 4 x 4 block of pairs for a share of the tile, so
 // eight LDS reads feed sixteen double FMAs per element; the free-variable mask is
-// staged the same way and applied to one side of the products.  Same sums in a
+// staged the same way and applied to both sides of the products (selected, not
+// multiplied: what is stored at a variable that is not free may be NaN).  Same sums in a
 // different order as k_masked_gram (both fixed; double accumulation).
 constexpr int kGram2B = 4;                       // pair block edge
 constexpr int kGram2Threads = 1024;
@@ -661,14 +667,17 @@ __global__ __launch_bounds__(kGram2Threads) void k_masked_gram_dma(
           double ad[kGram2B], bd[kGram2B];
 #pragma unroll
           for (int u = 0; u < kGram2B; ++u) {
-            ad[u] = (double)(keep[k] ? av[u][k] : T(0));   // (select before widening)
-            bd[u] = (double)bv[u][k];
+            // (select before widening) on BOTH sides, like k_mdot and the other two forms:
+            // a NaN or Inf stored at a variable that is not free must not meet the zero
+            // of the other side as fma(0, NaN)
+            ad[u] = (double)(keep[k] ? av[u][k] : T(0));
+            bd[u] = (double)(keep[k] ? bv[u][k] : T(0));
           }
           // one fused multiply-add per product (the library is built without
           // contraction): for float data the product of two widened values is exact
           // in double, so this is bit for bit the multiply and add of k_masked_gram
           if (RG && diag) {
-            const double bb = (double)bq[k];
+            const double bb = (double)(keep[k] ? bq[k] : T(0));
 #pragma unroll
             for (int u = 0; u < kGram2B; ++u)
 #pragma unroll
@@ -997,6 +1006,7 @@ int masked_gram_mfma_launch(const GramPtrs<T> &P, int nvec, const int8_t *iwhere
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return -2; }
   }
+  g_gram_launches[2].fetch_add(1, std::memory_order_relaxed);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kGram2Threads), lds, st, P, nvec,
                      iwhere, n, ws, R);
   hipLaunchKernelGGL(k_gram2_final, dim3(nvec * (nvec + 1) / 2 + (RG ? nvec : 0)),
@@ -1048,6 +1058,7 @@ int masked_gram_dma_launch_tb(const GramPtrs<T> &P, int nvec, const int8_t *iwhe
                                        (int)lds);
     if (e != hipSuccess) { (void)hipGetLastError(); return -2; }
   }
+  g_gram_launches[1].fetch_add(1, std::memory_order_relaxed);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kGram2Threads), lds, st, P, nvec,
                      iwhere, n, nb, splits, ws, R);
   hipLaunchKernelGGL(k_gram2_final, dim3(nvec * (nvec + 1) / 2 + (RG ? nvec : 0)),
@@ -1121,6 +1132,7 @@ int masked_gram_impl(const T *const *vecs, int nvec, const int8_t *iwhere, int64
                                        (int)lds);
     if (e != hipSuccess) return (int)e;
   }
+  g_gram_launches[0].fetch_add(1, std::memory_order_relaxed);
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), lds, as_stream(stream), P, nvec,
                      iwhere, n, nb, splits, ws);
   hipLaunchKernelGGL(k_gram_final, dim3(nvec * (nvec + 1) / 2), dim3(kBlock), 0,
@@ -1750,6 +1762,10 @@ int nsol_hip_set_param_lb(const char *name, int value) {
 }
 int64_t nsol_lb_gram_ws_doubles(void) {
   return (int64_t)kGramBlocks * (kGramEnt > kGram2Ent ? kGramEnt : kGram2Ent);
+}
+int nsol_lb_gram_launches(int form) {
+  if (form < 0 || form > 2) return -1;
+  return g_gram_launches[form].load(std::memory_order_relaxed);
 }
 int nsol_lb_mdots_f32(const float *const *vecs, int nvec, const float *y,
                       const int8_t *iwhere, int64_t n, double *result, double *ws,

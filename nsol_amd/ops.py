@@ -1174,6 +1174,12 @@ def pd_shift_launches():
     return int(_lib.load().nsol_pd_shift_launches())
 
 
+def lb_gram_launches(form):
+    """Launches of one form of the masked Gram pass by this process so far (0:
+    k_masked_gram, 1: k_masked_gram_dma, 2: k_masked_gram_mfma; -1 for another form)."""
+    return int(_lib.load().nsol_lb_gram_launches(int(form)))
+
+
 def pd_run_parts(iterations, min_iters):
     """(taken, lead, launches): how nsol_pd_run_* cuts a run of `iterations` when the
     shifted block starts at `min_iters` iterations (0: never)."""

@@ -2561,10 +2561,13 @@ def test_two_iterations_per_pass_large_shapes(nsol, shape):
                                  (2, 16), (9, 512 * 700 + 256)])
 def test_masked_gram_matches_masked_dots(nsol, dtype, c, n):
     """nsol_lb_masked_gram_* (all Y'ZZ'Y, S'ZZ'S, S'ZZ'Y entries from one pass)
-    against one nsol_lb_mdot_* per entry and against NumPy in float64; lengths
-    that are a multiple of 16 take the LDS-DMA staged kernel (partial last
-    tiles, fewer tiles than workgroups), the others the register-staged one,
-    and the two agree where both apply."""
+    against one nsol_lb_mdot_* per entry and against NumPy in float64.  With a
+    mask, lengths that are a multiple of 16 take k_masked_gram_mfma by default
+    (tiles staged by LDS-DMA, products on the matrix cores; partial last tiles,
+    fewer tiles than workgroups) and k_masked_gram_dma with lb_gram_mfma = 0;
+    the other lengths, and every length with lb_gram_dma = 0, take the
+    register-staged k_masked_gram.  All three meet the same references, and
+    nsol_lb_gram_launches says which kernel each leg ran."""
     import torch
     from nsol_amd.lbfgsb_device import DeviceBackend
     td = torch.float32 if dtype == np.float32 else torch.float64
@@ -2574,16 +2577,30 @@ def test_masked_gram_matches_masked_dots(nsol, dtype, c, n):
     free = (torch.rand(n, device="cuda", generator=gen) < 0.3).to(torch.int8)
     free = free * 2 - 1 * (torch.rand(n, device="cuda", generator=gen) < 0.1).to(
         torch.int8)                                   # values in {-1, 0, 1, 2}
-    from nsol_amd import _lib
+    from nsol_amd import _lib, ops
     be = DeviceBackend()
-    one = be.masked_grams(ws, wy, free)
+
+    def leg(form, run):
+        """run() must launch exactly one Gram kernel: the given form."""
+        before = [ops.lb_gram_launches(f) for f in range(3)]
+        out = run()
+        after = [ops.lb_gram_launches(f) for f in range(3)]
+        assert [x - y for x, y in zip(after, before)] == \
+            [int(f == form) for f in range(3)], (form, n)
+        return out
+    staged = n % 16 == 0
+    one = leg(2 if staged else 0, lambda: be.masked_grams(ws, wy, free))
     _lib.set_param("lb_gram_dma", 0)
-    old = be.masked_grams(ws, wy, free)
+    old = leg(0, lambda: be.masked_grams(ws, wy, free))
     _lib.set_param("lb_gram_dma", 1)
-    for a, b in zip(one, old):
+    _lib.set_param("lb_gram_mfma", 0)
+    dma = leg(1 if staged else 0, lambda: be.masked_grams(ws, wy, free))
+    _lib.set_param("lb_gram_mfma", 1)
+    for a, d, b in zip(one, dma, old):
         assert np.abs(a - b).max() <= 1e-12 * (np.abs(b).max() + 1e-300)
+        assert np.abs(d - b).max() <= 1e-12 * (np.abs(b).max() + 1e-300)
     be.USE_GRAM_KERNEL = False
-    many = be.masked_grams(ws, wy, free)
+    many = leg(-1, lambda: be.masked_grams(ws, wy, free))      # one masked dot per entry
     m = (free.cpu().numpy() <= 0).astype(np.float64)
     S = np.stack([w.cpu().numpy().astype(np.float64) * m for w in ws])
     Y = np.stack([w.cpu().numpy().astype(np.float64) * m for w in wy])
@@ -2592,7 +2609,11 @@ def test_masked_gram_matches_masked_dots(nsol, dtype, c, n):
         scale = np.abs(r).max() + 1e-300
         assert np.abs(a - r).max() / scale < 1e-12
         assert np.abs(a - b).max() / scale < 1e-12
-    none = be._masked_grams_one_pass(ws, wy, None)   # no mask: all variables
+    for d, r in zip(dma, ref):
+        assert np.abs(d - r).max() / (np.abs(r).max() + 1e-300) < 1e-12
+    # no mask: all variables (a whole number of 16-byte vectors is enough to be staged)
+    vec = 16 // np.dtype(dtype).itemsize
+    none = leg(2 if n % vec == 0 else 0, lambda: be._masked_grams_one_pass(ws, wy, None))
     assert np.abs(none[0] - np.stack([w.cpu().numpy().astype(np.float64)
                                       for w in wy]).dot(
         np.stack([w.cpu().numpy().astype(np.float64) for w in wy]).T)).max() \
@@ -2606,7 +2627,9 @@ def test_gram_pass_also_forms_the_reduced_gradient(nsol, dtype, c, n):
     """nsol_lb_masked_gram_rgrad_*: the subspace matrix and scipy cmprlb's reduced
     gradient from one pass over the 2c stored vectors -- the gradient bit for
     bit what nsol_lb_wcomb_* computes from a pass of its own, the matrix as from
-    nsol_lb_masked_gram_*."""
+    nsol_lb_masked_gram_*.  By default k_masked_gram_mfma forms them, with
+    lb_gram_mfma = 0 k_masked_gram_dma (nsol_lb_gram_launches tells which); the
+    register-staged kernel has no such form, so other lengths are declined."""
     import torch
     from nsol_amd.lbfgsb_device import DeviceBackend
     td = torch.float32 if dtype == np.float32 else torch.float64
@@ -2619,19 +2642,27 @@ def test_gram_pass_also_forms_the_reduced_gradient(nsol, dtype, c, n):
         (torch.rand(n, device="cuda", generator=gen) < 0.1).to(torch.int8)
     coef_s = list(np.linspace(-0.7, 0.9, c))
     coef_y = list(np.linspace(0.3, -1.1, c))
+    from nsol_amd import _lib, ops
     be = DeviceBackend()
     grams = be.masked_grams(ws, wy, free)
     r_ref = be.reduced_gradient(z, x, g, 0.83, ws, wy, coef_s, coef_y, free)
-    fused = be.masked_grams_rgrad(ws, wy, free, z, x, g, 0.83, coef_s, coef_y)
-    assert fused is not None, "the fused kernel did not run"
-    for a, b in zip(fused[:3], grams):
-        assert np.abs(a - b).max() <= 1e-12 * (np.abs(b).max() + 1e-300)
-    assert torch.equal(fused[3], r_ref)
     # [Y S]'Z r from the matrix and the products with the base part of r, against the
     # pass of its own (which sees r rounded to the working precision)
     wtzr_ref = np.asarray(be.dots(wy + ws, r_ref, free))
     tol = 1e-12 if dtype == np.float64 else 2e-6
-    assert np.abs(fused[4] - wtzr_ref).max() <= tol * (np.abs(wtzr_ref).max() + 1e-300)
+    for form in (2, 1):                               # the default, then lb_gram_mfma = 0
+        _lib.set_param("lb_gram_mfma", 1 if form == 2 else 0)
+        before = [ops.lb_gram_launches(f) for f in range(3)]
+        fused = be.masked_grams_rgrad(ws, wy, free, z, x, g, 0.83, coef_s, coef_y)
+        after = [ops.lb_gram_launches(f) for f in range(3)]
+        assert fused is not None, "the fused kernel did not run"
+        assert [x1 - x0 for x1, x0 in zip(after, before)] == \
+            [int(f == form) for f in range(3)], form
+        for a, b in zip(fused[:3], grams):
+            assert np.abs(a - b).max() <= 1e-12 * (np.abs(b).max() + 1e-300)
+        assert torch.equal(fused[3], r_ref)
+        assert np.abs(fused[4] - wtzr_ref).max() <= tol * (np.abs(wtzr_ref).max() + 1e-300)
+    _lib.set_param("lb_gram_mfma", 1)
     # lengths the LDS-DMA staged kernel does not take: the caller's two-step path
     if n % 16 == 0:
         m = n - 3
@@ -2640,6 +2671,7 @@ def test_gram_pass_also_forms_the_reduced_gradient(nsol, dtype, c, n):
                                       z[:m].clone(), x[:m].clone(), g[:m].clone(),
                                       0.83, coef_s, coef_y)
         assert short is None
+        assert [ops.lb_gram_launches(f) for f in range(3)] == after    # nothing launched
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
