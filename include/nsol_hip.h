@@ -1128,6 +1128,59 @@ int nsol_tgv_primal_lin_f64(const double *p, const double *q, double *x, double 
     int64_t nx, double wx, double wy, double wz, double tau, double theta, double lo,
     double hi, void *stream);
 
+/* The same two kernels on `members` (1 ... 65535) independent problems of one shape in
+ * ONE launch each, member m at blockIdx.z = m: a stack of images, or an (alpha, beta)
+ * sweep on one image.  Every array of the single entries holds the members one after
+ * the other: xbar and x at m * n, wbar, w and p at m * ndim * n, q at m * M * n, the
+ * components at stride n inside a member as before.  bt and wt (n values per member)
+ * sit at a member stride of 0 (shared by all members) or n; any other stride is
+ * NSOL_EINVAL.  sigma, tau and theta are shared; what differs per member comes from a
+ * device table:
+ * nsol_tgv_stack_table_*: beta_host[members] and tl_host[members] (tl = tau / alpha),
+ *   checked as the single entries check them (NSOL_EINVAL for a beta that is not
+ *   positive and finite, a tl that is not finite or < 0) and rounded as they round
+ *   them, 4 values of the element type per member (beta, tl, the prox denominator, 0),
+ *   written to the page-locked tab_host and copied to tab (tab_bytes >= 4 * members
+ *   elements) asynchronously on `stream`: tab_host must live until that copy is done.
+ *   The steps are constant, so one table serves all iterations.  -2 for members outside
+ *   1 ... 65535.
+ * nsol_tgv_stack_dual_*, nsol_tgv_stack_primal_*, nsol_tgv_stack_primal_w_*: every
+ *   member's result has the bits of the single entry on that member's arrays.  Vector
+ *   width and access form follow the alignment of every base and of the member strides
+ *   in bytes.  Returns as the single entries', the spans `members` times as long; -2,
+ *   nothing launched, also for members outside 1 ... 65535.
+ * nsol_tgv_stack_launches: successful launches of the stacked kernels by this process
+ *   (nsol_tgv_launches does not count them). */
+int nsol_tgv_stack_launches(void);
+int nsol_tgv_stack_table_f32(int members, const double *beta_host, const double *tl_host,
+    void *tab_host, void *tab, int64_t tab_bytes, void *stream);
+int nsol_tgv_stack_table_f64(int members, const double *beta_host, const double *tl_host,
+    void *tab_host, void *tab, int64_t tab_bytes, void *stream);
+int nsol_tgv_stack_dual_f32(const float *xbar, const float *wbar, float *p, float *q,
+    int members, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+    double wz, double sigma, const void *tab, int flags, void *stream);
+int nsol_tgv_stack_dual_f64(const double *xbar, const double *wbar, double *p, double *q,
+    int members, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx, double wy,
+    double wz, double sigma, const void *tab, int flags, void *stream);
+int nsol_tgv_stack_primal_f32(const float *p, const float *q, float *x, float *xbar,
+    float *w, float *wbar, const float *bt, int64_t bt_stride, int members, int ndim,
+    int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz, double tau,
+    double theta, const void *tab, int flags, void *stream);
+int nsol_tgv_stack_primal_f64(const double *p, const double *q, double *x, double *xbar,
+    double *w, double *wbar, const double *bt, int64_t bt_stride, int members, int ndim,
+    int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz, double tau,
+    double theta, const void *tab, int flags, void *stream);
+int nsol_tgv_stack_primal_w_f32(const float *p, const float *q, float *x, float *xbar,
+    float *w, float *wbar, const float *bt, int64_t bt_stride, const float *wt,
+    int64_t wt_stride, int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+    double wx, double wy, double wz, double tau, double theta, const void *tab,
+    int flags, void *stream);
+int nsol_tgv_stack_primal_w_f64(const double *p, const double *q, double *x, double *xbar,
+    double *w, double *wbar, const double *bt, int64_t bt_stride, const double *wt,
+    int64_t wt_stride, int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+    double wx, double wy, double wz, double tau, double theta, const void *tab,
+    int flags, void *stream);
+
 /* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */

@@ -30,4 +30,7 @@ def __getattr__(name):
     if name in ("PrimalDualLinearBatch", "PrimalDualLinearSweep"):
         from . import linear_stack
         return getattr(linear_stack, name)
+    if name in ("TGVPrimalDualBatch", "TGVPrimalDualSweep"):
+        from . import tgv_stack
+        return getattr(tgv_stack, name)
     raise AttributeError("module 'nsol_amd' has no attribute '%s'" % name)

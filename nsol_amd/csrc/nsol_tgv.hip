@@ -20,6 +20,13 @@
 //   k_tgv_primal_w, k_tgv_primal_lin: the same body with the weighted prox (one more
 //                 read-only stream wt) or, for a data term behind a linear operator A, the
 //                 explicit clipped step on g = A^T r in b~'s place (TgvForm below).
+//   k_tgv_dual_stack, k_tgv_primal_stack, k_tgv_primal_w_stack: the same device functions
+//                 on member blockIdx.z of a stack of independent problems of one shape (a
+//                 stack of images, an (alpha, beta) sweep): the member's arrays at
+//                 member-major 64-bit offsets, its beta, tl and prox denominator from a
+//                 device table (TgvMember).  The thread mapping uses blockIdx.x and
+//                 blockIdx.y only, so blockIdx.z adds a constant to a member's linear
+//                 workgroup ids and the slab grouping of voxel_at is kept within a member.
 //
 // No array is read at a neighbour and written in the same launch: no ping-pong buffers,
 // no dependency between workgroups.  The thread mapping is nsol_stencil.hpp's (k_grad /
@@ -46,6 +53,7 @@ using namespace nsol;
 namespace {
 
 std::atomic<int> g_tgv_launches{0};
+std::atomic<int> g_tgv_stack_launches{0};   // the member-stacked kernels'
 
 // stored component of the off-diagonal (a, b), a < b
 template <int NDIM>
@@ -105,10 +113,12 @@ __device__ __forceinline__ T clamp_beta(T v, T beta) {
   return v > beta ? beta : v;
 }
 
+// One member's dual step.  The single kernel passes its arguments on as they are; the
+// stacked one passes member blockIdx.z's arrays and its beta (k_tgv_dual_stack below).
 template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO>
-__global__ __launch_bounds__(kBlock) void k_tgv_dual(const T *__restrict__ xbar,
-                                                      const T *__restrict__ wbar, T *p,
-                                                      T *q, Geom<T> G, T sigma, T beta) {
+__device__ __forceinline__ void tgv_dual_body(const T *__restrict__ xbar,
+                                              const T *__restrict__ wbar, T *p, T *q,
+                                              const Geom<T> &G, T sigma, T beta) {
   constexpr int M = NDIM * (NDIM + 1) / 2;
   const int64_t nrg = row_groups<T, VEC, ROWS>(G);
   for (int64_t rg = blockIdx.y; rg < nrg; rg += gridDim.y) {
@@ -187,6 +197,36 @@ __global__ __launch_bounds__(kBlock) void k_tgv_dual(const T *__restrict__ xbar,
 #pragma unroll
     for (int m = 0; m < M; ++m) vs<RAG, T, VEC>(c.nval, q + m * G.n + c.i, e[m]);
   }
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO>
+__global__ __launch_bounds__(kBlock) void k_tgv_dual(const T *__restrict__ xbar,
+                                                      const T *__restrict__ wbar, T *p,
+                                                      T *q, Geom<T> G, T sigma, T beta) {
+  tgv_dual_body<T, VEC, ROWS, NDIM, RAG, ISO>(xbar, wbar, p, q, G, sigma, beta);
+}
+
+// What differs from member to member of a stack, in the kernels' type: beta (dual
+// kernel), tl = tau / alpha and prox_den<T>(tl) (primal kernels).  4 values of T per
+// member; nsol_tgv_stack_table_* fills the table.
+template <typename T>
+struct TgvMember {
+  T beta, tl, den, pad;
+};
+
+// k_tgv_dual on member m = blockIdx.z of a stack: xbar at m n, wbar and p at m d n, q
+// at m M n (64-bit offsets), beta from the table.  Components stay at stride n inside a
+// member, so Voxel::wide -- computed against one n-element array -- holds for every
+// member as it does for one.
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool ISO>
+__global__ __launch_bounds__(kBlock) void k_tgv_dual_stack(
+    const T *__restrict__ xbar, const T *__restrict__ wbar, T *p, T *q, Geom<T> G, T sigma,
+    const TgvMember<T> *__restrict__ tab) {
+  constexpr int M = NDIM * (NDIM + 1) / 2;
+  const int64_t m = blockIdx.z;
+  tgv_dual_body<T, VEC, ROWS, NDIM, RAG, ISO>(xbar + m * G.n, wbar + m * NDIM * G.n,
+                                              p + m * NDIM * G.n, q + m * M * G.n, G, sigma,
+                                              tab[m].beta);
 }
 
 // The x step of k_tgv_primal comes in three forms that share everything else:
@@ -285,6 +325,36 @@ __global__ __launch_bounds__(kBlock) void k_tgv_primal_lin(
                                                         G, tau, T(0), T(0), theta, lo, hi);
 }
 
+// tgv_primal_body (kPlain, kWgt) on member m = blockIdx.z: the state at member-major
+// offsets as in k_tgv_dual_stack, bt and wt at a member stride of 0 (a sweep shares them)
+// or n (a batch brings one per member), tl and den from the table.
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool L1>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal_stack(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ bt, int64_t bt_stride, Geom<T> G, T tau, T theta,
+    const TgvMember<T> *__restrict__ tab) {
+  constexpr int M = NDIM * (NDIM + 1) / 2;
+  const int64_t m = blockIdx.z;
+  const TgvMember<T> s = tab[m];
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, L1, kPlain>(
+      p + m * NDIM * G.n, q + m * M * G.n, x + m * G.n, xbar + m * G.n, w + m * NDIM * G.n,
+      wbar + m * NDIM * G.n, bt + m * bt_stride, nullptr, G, tau, s.tl, s.den, theta, T(0),
+      T(0));
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool L1>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal_w_stack(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ bt, int64_t bt_stride, const T *__restrict__ wt,
+    int64_t wt_stride, Geom<T> G, T tau, T theta, const TgvMember<T> *__restrict__ tab) {
+  constexpr int M = NDIM * (NDIM + 1) / 2;
+  const int64_t m = blockIdx.z;
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, L1, kWgt>(
+      p + m * NDIM * G.n, q + m * M * G.n, x + m * G.n, xbar + m * G.n, w + m * NDIM * G.n,
+      wbar + m * NDIM * G.n, bt + m * bt_stride, wt + m * wt_stride, G, tau, tab[m].tl,
+      T(0), theta, T(0), T(0));
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -325,7 +395,8 @@ inline int tgv_geometry(int ndim, int64_t nz, int64_t ny, int64_t nx, int flags)
 }
 
 template <typename T, typename F>
-int tgv_dispatch(int ndim, int64_t nz, int64_t ny, int64_t nx, bool aligned, F f) {
+int tgv_dispatch(int ndim, int64_t nz, int64_t ny, int64_t nx, bool aligned, F f,
+                 std::atomic<int> &launches = g_tgv_launches) {
   return dispatch_stencil<T>(nz, ny, nx, aligned, [&](auto vec, auto rows, auto rag) {
     int rc;
     switch (ndim) {
@@ -333,7 +404,7 @@ int tgv_dispatch(int ndim, int64_t nz, int64_t ny, int64_t nx, bool aligned, F f
       case 2: rc = f(vec, rows, rag, std::integral_constant<int, 2>()); break;
       default: rc = f(vec, rows, rag, std::integral_constant<int, 3>()); break;
     }
-    if (rc == 0) g_tgv_launches.fetch_add(1, std::memory_order_relaxed);
+    if (rc == 0) launches.fetch_add(1, std::memory_order_relaxed);
     return rc;
   });
 }
@@ -465,11 +536,150 @@ int tgv_primal_lin_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, co
   });
 }
 
+// ---------------------------------------------------------------------------
+// the member-stacked entries
+// ---------------------------------------------------------------------------
+// The table of a stack, TgvMember<T>[members], from the host's beta[m] and tl[m]: checked
+// as tgv_dual_impl and tgv_primal_impl check their scalars and rounded as they round
+// them, written to the pinned tab_host and uploaded in one copy on the stream.  The
+// steps are constant, so one table serves every iteration of a run.
+template <typename T>
+int tgv_stack_table_impl(int members, const double *beta, const double *tl, void *tab_host,
+                         void *tab, int64_t tab_bytes, void *stream) {
+  if (!pd_members_ok(members)) return -2;
+  if (!beta || !tl || !tab_host || !tab ||
+      tab_bytes < (int64_t)sizeof(TgvMember<T>) * members)
+    return NSOL_EINVAL;
+  for (int m = 0; m < members; ++m)
+    if (!positive(beta[m]) || !(isfinite(tl[m]) && tl[m] >= 0.0)) return NSOL_EINVAL;
+  TgvMember<T> *h = static_cast<TgvMember<T> *>(tab_host);
+  for (int m = 0; m < members; ++m) {
+    h[m].beta = (T)beta[m];
+    h[m].tl = (T)tl[m];
+    h[m].den = prox_den<T>(tl[m]);
+    h[m].pad = T(0);
+  }
+  const hipError_t e = hipMemcpyAsync(tab, tab_host, sizeof(TgvMember<T>) * (size_t)members,
+                                      hipMemcpyHostToDevice, as_stream(stream));
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+// What every stacked launch checks first.  0: go on; 1: an empty volume, return 0; else
+// the value to return.
+inline int tgv_stack_geometry(int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                              int flags) {
+  if (!pd_members_ok(members)) return -2;
+  return tgv_geometry(ndim, nz, ny, nx, flags);
+}
+
+// whole 16-byte vectors need every member to start on a 16-byte boundary: the bases (the
+// caller's check) and the member strides in bytes.  Every stride is a multiple of n
+// elements; a stride of 0 elements is aligned.
+template <typename T>
+inline bool stack_strides_aligned(int members, int64_t n) {
+  return members == 1 || (n * (int64_t)sizeof(T)) % 16 == 0;
+}
+
+template <typename T>
+int tgv_stack_dual_impl(const T *xbar, const T *wbar, T *p, T *q, int members, int ndim,
+                        int64_t nz, int64_t ny, int64_t nx, double wx, double wy, double wz,
+                        double sigma, const void *tab, int flags, void *stream) {
+  const int gr = tgv_stack_geometry(members, ndim, nz, ny, nx, flags);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t n = nz * ny * nx, nb = members * n * (int64_t)sizeof(T);
+  const int64_t M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{xbar, nb}, {wbar, ndim * nb}, {p, ndim * nb}, {q, M * nb}};
+  if (spans_bad(spans) || !tab || !positive(sigma)) return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(xbar) && aligned16(wbar) && aligned16(p) && aligned16(q) &&
+                  stack_strides_aligned<T>(members, n);
+  const hipStream_t st = as_stream(stream);
+  const TgvMember<T> *tb = static_cast<const TgvMember<T> *>(tab);
+  return tgv_dispatch<T>(
+      ndim, nz, ny, nx, al,
+      [&](auto vec, auto rows, auto rag, auto nd) {
+        constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+        constexpr int D = decltype(nd)::value;
+        constexpr bool RG = decltype(rag)::value;
+        dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+        grid.z = (unsigned)members;
+        if (flags & NSOL_PD_REG_ISOTROPIC)
+          hipLaunchKernelGGL((k_tgv_dual_stack<T, V, R, D, RG, true>), grid, dim3(kBlock), 0,
+                             st, xbar, wbar, p, q, G, (T)sigma, tb);
+        else
+          hipLaunchKernelGGL((k_tgv_dual_stack<T, V, R, D, RG, false>), grid, dim3(kBlock), 0,
+                             st, xbar, wbar, p, q, G, (T)sigma, tb);
+        return launch_status();
+      },
+      g_tgv_stack_launches);
+}
+
+// wt == nullptr with weighted == false: the plain prox
+template <typename T>
+int tgv_stack_primal_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, const T *bt,
+                          int64_t bt_stride, const T *wt, int64_t wt_stride, bool weighted,
+                          int members, int ndim, int64_t nz, int64_t ny, int64_t nx,
+                          double wx, double wy, double wz, double tau, double theta,
+                          const void *tab, int flags, void *stream) {
+  if (weighted && (flags & ~NSOL_PD_DATA_L1)) return NSOL_EINVAL;
+  const int gr = tgv_stack_geometry(members, ndim, nz, ny, nx, flags);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t n = nz * ny * nx, n1 = n * (int64_t)sizeof(T), nb = members * n1;
+  const int64_t M = ndim * (ndim + 1) / 2;
+  if (!pd_stride_ok(bt_stride, n) || (weighted && !pd_stride_ok(wt_stride, n)))
+    return NSOL_EINVAL;
+  const Span spans[] = {{p, ndim * nb}, {q, M * nb}, {x, nb}, {xbar, nb}, {w, ndim * nb},
+                        {wbar, ndim * nb}, {bt, bt_stride ? nb : n1},
+                        // (unweighted: an empty span, which overlaps nothing)
+                        {weighted ? wt : bt, weighted ? (wt_stride ? nb : n1) : 0}};
+  if (spans_bad(spans) || !tab || !positive(tau) || !isfinite(theta)) return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(p) && aligned16(q) && aligned16(x) && aligned16(xbar) &&
+                  aligned16(w) && aligned16(wbar) && aligned16(bt) &&
+                  (!weighted || aligned16(wt)) && stack_strides_aligned<T>(members, n);
+  const hipStream_t st = as_stream(stream);
+  const TgvMember<T> *tb = static_cast<const TgvMember<T> *>(tab);
+  const bool l1 = (flags & NSOL_PD_DATA_L1) != 0;
+  return tgv_dispatch<T>(
+      ndim, nz, ny, nx, al,
+      [&](auto vec, auto rows, auto rag, auto nd) {
+        constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+        constexpr int D = decltype(nd)::value;
+        constexpr bool RG = decltype(rag)::value;
+        dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+        grid.z = (unsigned)members;
+        if (weighted) {
+          if (l1)
+            hipLaunchKernelGGL((k_tgv_primal_w_stack<T, V, R, D, RG, true>), grid,
+                               dim3(kBlock), 0, st, p, q, x, xbar, w, wbar, bt, bt_stride, wt,
+                               wt_stride, G, (T)tau, (T)theta, tb);
+          else
+            hipLaunchKernelGGL((k_tgv_primal_w_stack<T, V, R, D, RG, false>), grid,
+                               dim3(kBlock), 0, st, p, q, x, xbar, w, wbar, bt, bt_stride, wt,
+                               wt_stride, G, (T)tau, (T)theta, tb);
+        } else {
+          if (l1)
+            hipLaunchKernelGGL((k_tgv_primal_stack<T, V, R, D, RG, true>), grid,
+                               dim3(kBlock), 0, st, p, q, x, xbar, w, wbar, bt, bt_stride, G,
+                               (T)tau, (T)theta, tb);
+          else
+            hipLaunchKernelGGL((k_tgv_primal_stack<T, V, R, D, RG, false>), grid,
+                               dim3(kBlock), 0, st, p, q, x, xbar, w, wbar, bt, bt_stride, G,
+                               (T)tau, (T)theta, tb);
+        }
+        return launch_status();
+      },
+      g_tgv_stack_launches);
+}
+
 }  // namespace
 
 extern "C" {
 
 int nsol_tgv_launches(void) { return g_tgv_launches.load(std::memory_order_relaxed); }
+int nsol_tgv_stack_launches(void) {
+  return g_tgv_stack_launches.load(std::memory_order_relaxed);
+}
 
 #define NSOL_TGV_DEF(T, SUF)                                                              \
   int nsol_tgv_dual_##SUF(const T *xbar, const T *wbar, T *p, T *q, int ndim, int64_t nz, \
@@ -500,8 +710,43 @@ int nsol_tgv_launches(void) { return g_tgv_launches.load(std::memory_order_relax
                                   wz, tau, theta, lo, hi, s);                             \
   }
 
+#define NSOL_TGV_STACK_DEF(T, SUF)                                                        \
+  int nsol_tgv_stack_table_##SUF(int members, const double *beta, const double *tl,       \
+                                 void *tab_host, void *tab, int64_t tab_bytes, void *s) { \
+    return tgv_stack_table_impl<T>(members, beta, tl, tab_host, tab, tab_bytes, s);       \
+  }                                                                                       \
+  int nsol_tgv_stack_dual_##SUF(const T *xbar, const T *wbar, T *p, T *q, int members,    \
+                                int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,  \
+                                double wy, double wz, double sigma, const void *tab,      \
+                                int flags, void *s) {                                     \
+    return tgv_stack_dual_impl<T>(xbar, wbar, p, q, members, ndim, nz, ny, nx, wx, wy, wz, \
+                                  sigma, tab, flags, s);                                  \
+  }                                                                                       \
+  int nsol_tgv_stack_primal_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,   \
+                                  const T *bt, int64_t bt_stride, int members, int ndim,  \
+                                  int64_t nz, int64_t ny, int64_t nx, double wx,          \
+                                  double wy, double wz, double tau, double theta,         \
+                                  const void *tab, int flags, void *s) {                  \
+    return tgv_stack_primal_impl<T>(p, q, x, xbar, w, wbar, bt, bt_stride, nullptr, 0,    \
+                                    false, members, ndim, nz, ny, nx, wx, wy, wz, tau,    \
+                                    theta, tab, flags, s);                                \
+  }                                                                                       \
+  int nsol_tgv_stack_primal_w_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, \
+                                    const T *bt, int64_t bt_stride, const T *wt,          \
+                                    int64_t wt_stride, int members, int ndim, int64_t nz, \
+                                    int64_t ny, int64_t nx, double wx, double wy,         \
+                                    double wz, double tau, double theta, const void *tab, \
+                                    int flags, void *s) {                                 \
+    return tgv_stack_primal_impl<T>(p, q, x, xbar, w, wbar, bt, bt_stride, wt, wt_stride, \
+                                    true, members, ndim, nz, ny, nx, wx, wy, wz, tau,     \
+                                    theta, tab, flags, s);                                \
+  }
+
 NSOL_TGV_DEF(float, f32)
 NSOL_TGV_DEF(double, f64)
 #undef NSOL_TGV_DEF
+NSOL_TGV_STACK_DEF(float, f32)
+NSOL_TGV_STACK_DEF(double, f64)
+#undef NSOL_TGV_STACK_DEF
 
 }  // extern "C"

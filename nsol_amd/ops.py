@@ -1936,6 +1936,133 @@ def tgv_primal_lin(p, q, x, xbar, w_field, wbar, g, shape, w, tau, theta=1., lo=
     return True
 
 
+# ----------------- TGV, member-stacked (k_tgv_*_stack in nsol_tgv.hip; tgv_stack.py) ----
+# A stack of images of one shape or an (alpha, beta) sweep on one image: two launches per
+# iteration for all members of a group.  A member's state is x, xbar, w, wbar, p and q:
+# (2 + 3 dim + M) n words, M = dim (dim + 1) / 2, plus its own scaled observation and
+# weights where the members do not share them.  The value is PD_BATCH_GROUP_BYTES',
+# borrowed, not measured for TGV; it decides speed only.
+TGV_STACK_GROUP_BYTES = 256 << 20
+TGV_STACK_MAX_MEMBERS = 65535
+
+
+def tgv_stack_launches():
+    """Successful launches of the member-stacked TGV kernels so far (tgv_launches() does
+    not count them)."""
+    return int(_lib.load().nsol_tgv_stack_launches())
+
+
+def tgv_stack_group_size(members, n, dim, itemsize, weighted, own_data=True):
+    """Members per stacked group of TGV runs: as many as keep a group's state ((2 + 3 dim
+    + M) n words per member, and with own_data -- a batch -- the member's own observation
+    and, weighted, its own weights; a sweep shares both) under TGV_STACK_GROUP_BYTES, at
+    most TGV_STACK_MAX_MEMBERS, at least one."""
+    dim, n = int(dim), int(n)
+    words = 2 + 3 * dim + dim * (dim + 1) // 2
+    if own_data:
+        words += 2 if weighted else 1
+    g = min(TGV_STACK_GROUP_BYTES // (words * n * int(itemsize)), TGV_STACK_MAX_MEMBERS)
+    return int(max(1, min(int(members), g)))
+
+
+def tgv_stack_table(like, beta, tl):
+    """The device table of a stack's per-member scalars (beta[m], tl[m] = tau / alpha_m
+    and the prox denominator, in the element type of `like`) for tgv_stack_dual and
+    tgv_stack_primal: one table for all iterations of a run.  Returns None when the
+    library declined the member count."""
+    beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+    tl = np.ascontiguousarray(tl, dtype=np.float64).reshape(-1)
+    if beta.size != tl.size:
+        raise ValueError("%d values of beta, %d of tl" % (beta.size, tl.size))
+    _chk(like)
+    _sweep_staging[:] = [s for s in _sweep_staging if not s[0].query()]
+    nbytes = max(16, 4 * like.element_size() * beta.size)
+    tab_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    tab = torch.empty(nbytes, dtype=torch.uint8, device=like.device)
+    rc = _fn("tgv_stack_table", like)(
+        int(beta.size), beta.ctypes.data, tl.ctypes.data, tab_host.data_ptr(), _p(tab),
+        nbytes, stream_ptr())
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_tgv_stack_table")
+    _table_keep(tab_host)
+    return tab
+
+
+def _tgv_stack_operands(members, shape, x_like, scalars, vectors, tensors, tab):
+    """Checks the stacks of a member-stacked TGV call: members * n values in every tensor
+    of `scalars`, members * ndim * n in `vectors`, members * M * n in `tensors`, all in the
+    element type of x_like, and a table with a row for every member."""
+    ndim, nz, ny, nx = dims3(shape)
+    n = nz * ny * nx
+    members = int(members)
+    if members < 1:
+        return ndim, nz, ny, nx, n          # (the library declines it)
+    for group, size in ((scalars, n), (vectors, ndim * n),
+                        (tensors, ndim * (ndim + 1) // 2 * n)):
+        for t in group:
+            if _chk(t).dtype != x_like.dtype or t.numel() != members * size:
+                raise ValueError("operand mismatch: %s[%d] where %s[%d] is expected for "
+                                 "%d members of shape %r" % (
+                                     str(t.dtype), t.numel(), str(x_like.dtype),
+                                     members * size, members, tuple(shape)))
+    if _chk(tab).numel() < 4 * x_like.element_size() * members:
+        raise ValueError("the table has no row for %d members" % members)
+    return ndim, nz, ny, nx, n
+
+
+def _tgv_member_stride(t, x_like, members, n, what):
+    """0 (one array shared by the members) or n (every member its own)."""
+    if _chk(t).dtype != x_like.dtype or t.numel() not in (n, members * n):
+        raise ValueError("operand mismatch: %s holds %s[%d], neither %d nor %d x %d "
+                         "values" % (what, str(t.dtype), t.numel(), n, members, n))
+    return 0 if t.numel() == n else n
+
+
+def tgv_stack_dual(xbar, wbar, p, q, members, shape, w, sigma, tab, flags=0):
+    """tgv_dual on `members` stacked problems in one launch: every array holds the
+    members one after the other, beta comes from tgv_stack_table's table.  Returns False
+    when the library declined (nothing was launched).  Does not synchronise."""
+    ndim, nz, ny, nx, _ = _tgv_stack_operands(members, shape, xbar, (xbar,), (wbar, p),
+                                              (q,), tab)
+    rc = _fn("tgv_stack_dual", xbar)(
+        _p(xbar), _p(wbar), _p(p), _p(q), int(members), ndim, nz, ny, nx, w[0], w[1], w[2],
+        float(sigma), _p(tab), int(flags), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_stack_dual")
+    _wrote(p, q)
+    return True
+
+
+def tgv_stack_primal(p, q, x, xbar, w_field, wbar, bt, members, shape, w, tau, tab,
+                     theta=1., flags=0, wt=None):
+    """tgv_primal (wt None) or tgv_primal_w on `members` stacked problems in one launch;
+    bt and wt hold n values shared by the members or members * n, each on its own; tl
+    comes from tgv_stack_table's table.  Returns False when the library declined (nothing
+    was launched).  Does not synchronise."""
+    ndim, nz, ny, nx, n = _tgv_stack_operands(members, shape, x, (x, xbar),
+                                              (p, w_field, wbar), (q,), tab)
+    members = int(members)
+    bts = _tgv_member_stride(bt, x, members, n, "bt") if members >= 1 else 0
+    if wt is None:
+        rc = _fn("tgv_stack_primal", x)(
+            _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(bt), bts, members,
+            ndim, nz, ny, nx, w[0], w[1], w[2], float(tau), float(theta), _p(tab),
+            int(flags), stream_ptr())
+    else:
+        wts = _tgv_member_stride(wt, x, members, n, "wt") if members >= 1 else 0
+        rc = _fn("tgv_stack_primal_w", x)(
+            _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(bt), bts, _p(wt), wts,
+            members, ndim, nz, ny, nx, w[0], w[1], w[2], float(tau), float(theta), _p(tab),
+            int(flags), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_stack_primal" + ("" if wt is None else "_w"))
+    _wrote(x, xbar, w_field, wbar)
+    return True
+
+
 # ------------------------------ the same, member-stacked (nsol_pdls.hip) ----
 # An alpha sweep on one observation or a stack of images of one shape
 # (nsol_amd/linear_stack.py).  A member's state is x, two xbar, q, g = A^T q and two p

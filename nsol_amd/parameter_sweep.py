@@ -45,14 +45,16 @@ from .stopping import checked_check_every, checked_tolerance
 PARAMETER_KEYS = ("alpha", "alg_type", "L2")
 
 
-def member_parameters(parameters):
+def member_parameters(parameters, keys=PARAMETER_KEYS):
     """The members of a sweep: one dict per element of itertools.product over the
-    value lists, in the dictionary's own key order."""
+    value lists, in the dictionary's own key order.  keys: the parameters the kind of
+    sweep knows (tgv_stack.TGVPrimalDualSweep: alpha and beta)."""
+    known = tuple(keys)
     keys = list(parameters.keys())
     for k in keys:
-        if k not in PARAMETER_KEYS:
+        if k not in known:
             raise ValueError("unknown sweep parameter '%s' (known: %s)" %
-                             (k, ", ".join(PARAMETER_KEYS)))
+                             (k, ", ".join(known)))
     values = []
     for k in keys:
         v = parameters[k]
