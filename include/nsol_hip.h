@@ -1181,6 +1181,9 @@ int nsol_tgv_stack_primal_w_f64(const double *p, const double *q, double *x, dou
     double wx, double wy, double wz, double tau, double theta, const void *tab,
     int flags, void *stream);
 
+/* The member-stacked form of nsol_tgv_primal_lin_*, nsol_tgv_stack_primal_lin_*, is declared
+ * in nsol_hip_tgv_lin_stack.h, which this header includes at its end. */
+
 /* ---------------------------------------------------------------------- *
  * ADMM outer update, admm_linear_solver.py:202-218, 239-253
  * ---------------------------------------------------------------------- */
@@ -1748,4 +1751,7 @@ int nsol_lb_cauchy_walk_f64(const double *tbk, const double *d, const double *x,
 #ifdef __cplusplus
 }
 #endif
+
+#include "nsol_hip_tgv_lin_stack.h"
+
 #endif /* NSOL_HIP_H */

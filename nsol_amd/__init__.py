@@ -33,4 +33,7 @@ def __getattr__(name):
     if name in ("TGVPrimalDualBatch", "TGVPrimalDualSweep"):
         from . import tgv_stack
         return getattr(tgv_stack, name)
+    if name in ("TGVPrimalDualLinearBatch", "TGVPrimalDualLinearSweep"):
+        from . import tgv_linear_stack
+        return getattr(tgv_linear_stack, name)
     raise AttributeError("module 'nsol_amd' has no attribute '%s'" % name)

@@ -10,6 +10,9 @@ import re
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libnsol_hip.so")
 HEADER = os.path.join(HERE, "..", "include", "nsol_hip.h")
+# entries declared in headers of their own, which nsol_hip.h includes: bound beside
+# HEADER's, by the same parser (declared_symbols(header=...))
+MORE_HEADERS = (os.path.join(HERE, "..", "include", "nsol_hip_tgv_lin_stack.h"),)
 
 _lib = None
 
@@ -26,7 +29,8 @@ class NsolHipError(RuntimeError):
 
 
 def declared_symbols(header=HEADER):
-    """Parse include/nsol_hip.h: {name: (restype, [argtypes])}."""
+    """Parse include/nsol_hip.h (or `header`, one of MORE_HEADERS): {name: (restype,
+    [argtypes])} of what that file itself declares."""
     text = open(header).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     out = {}
@@ -55,7 +59,10 @@ def load():
             "libnsol_hip.so not found at %s -- build it with "
             "`python -m nsol_amd.build` (there is no CPU fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, argtypes) in declared_symbols().items():
+    declared = declared_symbols()
+    for header in MORE_HEADERS:
+        declared.update(declared_symbols(header))
+    for name, (res, argtypes) in declared.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -47,8 +47,9 @@ keeps the smooth ramps TV turns into terraces; B (default 2) weighs |E w|_1 agai
 |grad x - w|_1.  It takes what the other PDL types take -- --data-loss ell1, --mask /
 --weights, --nonnegative, --isotropic, --tolerance / --check-every, --upsample /
 --sample-offset, --observe-every, --dtype; several --alpha loop -- except --result-dir
-and --slice-wise: there are no stacked TGV forms.  --L2 is not used, as for the other PDL
-types: the steps come from tgv_numpy.norm_bound_linear.
+and --slice-wise: the stacked TGV forms (nsol_amd/tgv_linear_stack.py) are reachable
+through the API only.  --L2 is not used, as for the other PDL types: the steps come from
+tgv_numpy.norm_bound_linear.
 
 With --reference, the measures are evaluated through an Observer on the flat
 iterates against the flat reference (as run_denoising does and as the
@@ -454,8 +455,9 @@ def parse_args(argv=None, ap=None):
             ap.error("--reconstruction-type TGVL2 is a form of --solver PDL "
                      "(TGVPrimalDualLinearSolver), not of --solver %s" % args.solver)
         if args.result_dir is not None or args.slice_wise:
-            ap.error("--reconstruction-type TGVL2 does not take %s: there are no "
-                     "stacked TGV forms; several --alpha loop" %
+            ap.error("--reconstruction-type TGVL2 does not take %s yet: the stacked "
+                     "TGV forms (nsol_amd/tgv_linear_stack.py) are reachable through "
+                     "the API only; several --alpha loop" %
                      ("--result-dir" if args.result_dir is not None else "--slice-wise"))
         if args.beta is None:
             args.beta = 2.0

@@ -26,7 +26,7 @@ def _stale():
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
             if f.endswith((".hip", ".hpp"))]
-    deps.append(os.path.join(INCLUDE, "nsol_hip.h"))
+    deps += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

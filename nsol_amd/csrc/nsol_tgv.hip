@@ -20,11 +20,13 @@
 //   k_tgv_primal_w, k_tgv_primal_lin: the same body with the weighted prox (one more
 //                 read-only stream wt) or, for a data term behind a linear operator A, the
 //                 explicit clipped step on g = A^T r in b~'s place (TgvForm below).
-//   k_tgv_dual_stack, k_tgv_primal_stack, k_tgv_primal_w_stack: the same device functions
+//   k_tgv_dual_stack, k_tgv_primal_stack, k_tgv_primal_w_stack, k_tgv_primal_lin_stack:
+//                 the same device functions
 //                 on member blockIdx.z of a stack of independent problems of one shape (a
 //                 stack of images, an (alpha, beta) sweep): the member's arrays at
 //                 member-major 64-bit offsets, its beta, tl and prox denominator from a
-//                 device table (TgvMember).  The thread mapping uses blockIdx.x and
+//                 device table (TgvMember; the kLin form reads none: its step takes tau,
+//                 theta and the box only).  The thread mapping uses blockIdx.x and
 //                 blockIdx.y only, so blockIdx.z adds a constant to a member's linear
 //                 workgroup ids and the slab grouping of voxel_at is kept within a member.
 //
@@ -355,6 +357,21 @@ __global__ __launch_bounds__(kBlock) void k_tgv_primal_w_stack(
       T(0), theta, T(0), T(0));
 }
 
+// tgv_primal_body (kLin) on member m = blockIdx.z: the state at member-major offsets as
+// in k_tgv_dual_stack, g = A^T r at m n (every member has its own).  tau, theta and the
+// box are shared by value; a member's lambda sits in the data side's r update and its
+// beta in the dual kernel, so this kernel reads no table.
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal_lin_stack(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ g, Geom<T> G, T tau, T theta, T lo, T hi) {
+  constexpr int M = NDIM * (NDIM + 1) / 2;
+  const int64_t m = blockIdx.z;
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, false, kLin>(
+      p + m * NDIM * G.n, q + m * M * G.n, x + m * G.n, xbar + m * G.n, w + m * NDIM * G.n,
+      wbar + m * NDIM * G.n, g + m * G.n, nullptr, G, tau, T(0), T(0), theta, lo, hi);
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -672,6 +689,42 @@ int tgv_stack_primal_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, 
       g_tgv_stack_launches);
 }
 
+// tgv_primal_lin_impl's checks and rounding of the box on spans `members` times as long
+template <typename T>
+int tgv_stack_primal_lin_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,
+                              const T *g, int members, int ndim, int64_t nz, int64_t ny,
+                              int64_t nx, double wx, double wy, double wz, double tau,
+                              double theta, double lo, double hi, void *stream) {
+  const int gr = tgv_stack_geometry(members, ndim, nz, ny, nx, 0);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t n = nz * ny * nx, nb = members * n * (int64_t)sizeof(T);
+  const int64_t M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{p, ndim * nb}, {q, M * nb},       {x, nb}, {xbar, nb},
+                        {w, ndim * nb}, {wbar, ndim * nb}, {g, nb}};
+  if (spans_bad(spans) || !positive(tau) || !isfinite(theta) || !(lo <= hi))
+    return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(p) && aligned16(q) && aligned16(x) && aligned16(xbar) &&
+                  aligned16(w) && aligned16(wbar) && aligned16(g) &&
+                  stack_strides_aligned<T>(members, n);
+  const hipStream_t st = as_stream(stream);
+  T l, h;
+  box_in<T>(lo, hi, l, h);
+  return tgv_dispatch<T>(
+      ndim, nz, ny, nx, al,
+      [&](auto vec, auto rows, auto rag, auto nd) {
+        constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+        constexpr int D = decltype(nd)::value;
+        constexpr bool RG = decltype(rag)::value;
+        dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+        grid.z = (unsigned)members;
+        hipLaunchKernelGGL((k_tgv_primal_lin_stack<T, V, R, D, RG>), grid, dim3(kBlock), 0,
+                           st, p, q, x, xbar, w, wbar, g, G, (T)tau, (T)theta, l, h);
+        return launch_status();
+      },
+      g_tgv_stack_launches);
+}
+
 }  // namespace
 
 extern "C" {
@@ -740,6 +793,14 @@ int nsol_tgv_stack_launches(void) {
     return tgv_stack_primal_impl<T>(p, q, x, xbar, w, wbar, bt, bt_stride, wt, wt_stride, \
                                     true, members, ndim, nz, ny, nx, wx, wy, wz, tau,     \
                                     theta, tab, flags, s);                                \
+  }                                                                                       \
+  int nsol_tgv_stack_primal_lin_##SUF(const T *p, const T *q, T *x, T *xbar, T *w,        \
+                                      T *wbar, const T *g, int members, int ndim,         \
+                                      int64_t nz, int64_t ny, int64_t nx, double wx,      \
+                                      double wy, double wz, double tau, double theta,     \
+                                      double lo, double hi, void *s) {                    \
+    return tgv_stack_primal_lin_impl<T>(p, q, x, xbar, w, wbar, g, members, ndim, nz, ny, \
+                                        nx, wx, wy, wz, tau, theta, lo, hi, s);           \
   }
 
 NSOL_TGV_DEF(float, f32)

@@ -116,6 +116,45 @@ def launches_per_iteration(solver, members):
             adj.stacked_launches(solver._op_adj_shape, P) + 2, P * one)
 
 
+class StackedDataSide(object):
+    """The data term's side of one stacked run (run_linear_stack below,
+    tgv_linear_stack.run_tgv_linear_stack): the blur over the stack -- as the epilogue
+    q <- sigma A xbar + q of the one-pass blur while it applies, else into t = A xbar,
+    allocated when first needed -- every member's update of q and g = A^T q.  The
+    template supplies the operators; `like` the element type, the device and, with
+    `group`, the size of t and of the epilogue's slots."""
+
+    def __init__(self, template, like, group, n):
+        import torch
+        s = template
+        self._op, self._op_shape = s._op, s._op_shape
+        self._adj, self._adj_shape = s._op_adj, s._op_adj_shape
+        self._like, self._size = like, group * n
+        self._t_all = None
+        # q <- sigma A xbar + q as the epilogue of the one-pass blur, while it applies
+        self._epilogue = bool(linear_operators.USE_BLUR_EPILOGUE)
+        self._slots = torch.empty(group, dtype=torch.float64, device=like.device) \
+            if self._epilogue else None
+
+    def dual_step(self, xbar, q, bt, wt, sigma, lm, g, l1, out):
+        """q (g members) in place, then out <- A^T q.  False when the library declined
+        the update of q: the adjoint has not run then."""
+        n = q.numel() // g
+        if self._epilogue and self._op.apply_axpby_stacked(
+                xbar, q, self._op_shape, g, sigma, 1., results=self._slots[:g]) is None:
+            self._epilogue = False     # the kernel declined: nothing ran, q is intact
+        if self._epilogue:
+            ok = ops.pdl_stack_dual_data(q, None, bt, wt, sigma, lm, g, l1)
+        else:
+            if self._t_all is None:
+                self._t_all = self._like.new_empty(self._size)
+            t = self._op._apply_stacked(xbar, self._op_shape, g, out=self._t_all[:g * n])
+            ok = ops.pdl_stack_dual_data(q, t, bt, wt, sigma, lm, g, l1)
+        if ok:
+            self._adj._apply_stacked(q, self._adj_shape, g, out=out)
+        return ok
+
+
 def run_linear_stack(x_all, bt, wt, strided, template, lmbda, group, points,
                      observe=None, taken=None, start=None):
     """Advance the P = len(lmbda) stacked runs whose start vectors x_all (P * n,
@@ -132,12 +171,10 @@ def run_linear_stack(x_all, bt, wt, strided, template, lmbda, group, points,
     Returns True, or None when the library declined the tile kernel's very first
     launch: x_all is as it was and nothing has been called.  A decline on any later
     launch raises RuntimeError."""
-    import torch
     s = template
     P = len(lmbda)
     n, dim = x_all.numel() // P, s._dimension
     iters = int(s._iterations)
-    op, op_shape, adj, adj_shape = s._op, s._op_shape, s._op_adj, s._op_adj_shape
     shape, w, flags = s._shape, ops.inv_spacing(s._spacing, dim), s._flags()
     tau, sigma, theta = s._tau, s._sigma, s._theta
     hden = 1. + sigma * s._huber_gamma if s._reg_type == "huber" else 1.
@@ -145,14 +182,10 @@ def run_linear_stack(x_all, bt, wt, strided, template, lmbda, group, points,
     lo, hi = s._bounds
     lm_all = ops.pdl_lambdas(lmbda, x_all)
     points = set(points or ())
-    # a group's q, g = A^T q and t = A xbar (where the epilogue does not spare it),
-    # allocated once beside stack_groups' xbar and p
+    # a group's q and g = A^T q, allocated once beside stack_groups' xbar and p (t = A
+    # xbar, where the epilogue does not spare it, is the data side's)
     q_all, g_all = x_all.new_empty(group * n), x_all.new_empty(group * n)
-    t_all = None
-    # q <- sigma A xbar + q as the epilogue of the one-pass blur, while it applies
-    epilogue = bool(linear_operators.USE_BLUR_EPILOGUE)
-    slots = torch.empty(group, dtype=torch.float64, device=x_all.device) \
-        if epilogue else None
+    data = StackedDataSide(s, x_all, group, n)
     launches = Launches(taken)
     for a, b, x, xb, pp, bt_g, wt_g in stack_groups(x_all, bt, wt, strided, P, dim,
                                                     group, start):
@@ -162,22 +195,10 @@ def run_linear_stack(x_all, bt, wt, strided, template, lmbda, group, points,
         lm = lm_all[a:b]
         for i in range(iters):
             k = i & 1
-            if epilogue and op.apply_axpby_stacked(xb[k], q, op_shape, g, sigma, 1.,
-                                                   results=slots[:g]) is None:
-                epilogue = False       # the kernel declined: nothing ran, q is intact
-            if epilogue:
-                ok = ops.pdl_stack_dual_data(q, None, bt_g, wt_g, sigma, lm, g, l1)
-            else:
-                if t_all is None:
-                    t_all = x_all.new_empty(group * n)
-                t = op._apply_stacked(xb[k], op_shape, g, out=t_all[:g * n])
-                ok = ops.pdl_stack_dual_data(q, t, bt_g, wt_g, sigma, lm, g, l1)
-            if ok:
-                adj._apply_stacked(q, adj_shape, g, out=gq)
-                ok = ops.pdl_stack_iter(xb[k], xb[1 - k], x, gq, pp[k], pp[1 - k], g,
-                                        shape, w, sigma, hden, tau, theta, lo, hi, flags,
-                                        has_p=i > 0)
-            if not ok:
+            if not (data.dual_step(xb[k], q, bt_g, wt_g, sigma, lm, g, l1, gq) and
+                    ops.pdl_stack_iter(xb[k], xb[1 - k], x, gq, pp[k], pp[1 - k], g,
+                                       shape, w, sigma, hden, tau, theta, lo, hi, flags,
+                                       has_p=i > 0)):
                 return launches.declined("pdl_stack")
             launches.accepted()
             if observe is not None and (i + 1) in points:

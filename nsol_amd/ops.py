@@ -1941,7 +1941,8 @@ def tgv_primal_lin(p, q, x, xbar, w_field, wbar, g, shape, w, tau, theta=1., lo=
 # iteration for all members of a group.  A member's state is x, xbar, w, wbar, p and q:
 # (2 + 3 dim + M) n words, M = dim (dim + 1) / 2, plus its own scaled observation and
 # weights where the members do not share them.  The value is PD_BATCH_GROUP_BYTES',
-# borrowed, not measured for TGV; it decides speed only.
+# borrowed, not measured for TGV; it decides speed only.  The stacked linear form
+# (tgv_linear_stack.py, tgv_lin_stack_group_size below) counts its groups against it too.
 TGV_STACK_GROUP_BYTES = 256 << 20
 TGV_STACK_MAX_MEMBERS = 65535
 
@@ -2061,6 +2062,48 @@ def tgv_stack_primal(p, q, x, xbar, w_field, wbar, bt, members, shape, w, tau, t
     _lib.check(rc, "nsol_tgv_stack_primal" + ("" if wt is None else "_w"))
     _wrote(x, xbar, w_field, wbar)
     return True
+
+
+def tgv_stack_primal_lin(p, q, x, xbar, w_field, wbar, g, members, shape, w, tau,
+                         theta=1., lo=-np.inf, hi=np.inf):
+    """tgv_primal_lin on `members` stacked problems in one launch: every array holds the
+    members one after the other, g = A^T r included (every member has its own); tau,
+    theta and the box are common to the stack, so there is no table.  Returns False when
+    the library declined (nothing was launched).  Does not synchronise."""
+    members = int(members)
+    ndim, nz, ny, nx = dims3(shape)
+    if members >= 1:
+        n = nz * ny * nx
+        for group, size in (((x, xbar, g), n), ((p, w_field, wbar), ndim * n),
+                            ((q,), ndim * (ndim + 1) // 2 * n)):
+            for t in group:
+                if _chk(t).dtype != x.dtype or t.numel() != members * size:
+                    raise ValueError("operand mismatch: %s[%d] where %s[%d] is expected "
+                                     "for %d members of shape %r" % (
+                                         str(t.dtype), t.numel(), str(x.dtype),
+                                         members * size, members, tuple(shape)))
+    rc = _fn("tgv_stack_primal_lin", x)(
+        _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(g), members, ndim, nz, ny,
+        nx, w[0], w[1], w[2], float(tau), float(theta), float(lo), float(hi), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_stack_primal_lin")
+    _wrote(x, xbar, w_field, wbar)
+    return True
+
+
+def tgv_lin_stack_group_size(members, n, dim, itemsize, own_data=True, own_weights=False,
+                             with_t=False):
+    """Members per stacked group of TGVPrimalDualLinearSolver runs: (2 + 3 dim + M + 2) n
+    words per member -- x and xbar; w, wbar and p; q; r and g = A^T r -- and one more
+    each for t = A xbar (with_t: the blur runs without its epilogue), the member's own
+    observation (own_data) and its own weights (own_weights), under
+    TGV_STACK_GROUP_BYTES, at most TGV_STACK_MAX_MEMBERS, at least one."""
+    dim, n = int(dim), int(n)
+    words = 2 + 3 * dim + dim * (dim + 1) // 2 + 2 + int(bool(with_t)) + \
+        int(bool(own_data)) + int(bool(own_weights))
+    g = min(TGV_STACK_GROUP_BYTES // (words * n * int(itemsize)), TGV_STACK_MAX_MEMBERS)
+    return int(max(1, min(int(members), g)))
 
 
 # ------------------------------ the same, member-stacked (nsol_pdls.hip) ----

@@ -1,81 +1,107 @@
-"""Stacked forms of TGVPrimalDualSolver -- second-order TGV denoising -- for the two jobs
-that are otherwise a Python loop of solvers:
+"""Stacked forms of TGVPrimalDualLinearSolver -- TGV for blurred, thick-sliced, partly
+missing data -- for the two jobs that are otherwise a Python loop of solvers:
 
-    batch = TGVPrimalDualBatch([TGVPrimalDualSolver(...), ...])
+    batch = TGVPrimalDualLinearBatch([TGVPrimalDualLinearSolver(...), ...])
     batch.run()                                  # the slices of a stack, small volumes
     x = batch.get_solvers()[3].get_x()           # as if that solver's run() had run
     w = batch.get_solvers()[3].get_w()
 
-    sweep = TGVPrimalDualSweep(b, x0, dimension,
-                               parameters={"alpha": [...], "beta": [...]}, iterations=200)
+    sweep = TGVPrimalDualLinearSweep(A, A_adj, b, x0, dimension,
+                                     parameters={"alpha": [...], "beta": [...]},
+                                     iterations=200)
     sweep.set_measures({"PSNR": ...}, every=50)
     sweep.run()
     m, best = sweep.best("PSNR")
 
-P members of one shape advance together, TWO launches per iteration for a whole group
-(ops.tgv_stack_dual, ops.tgv_stack_primal; k_tgv_*_stack in nsol_tgv.hip, member m at
-blockIdx.z = m), in groups that keep the state under ops.TGV_STACK_GROUP_BYTES, without a
-read-back or a synchronisation inside the loop.  tau, sigma and theta depend on shape and
-spacing only and are shared by value; beta and tl = tau / alpha differ per member and come
-from one device table per group (ops.tgv_stack_table).  A sweep shares one scaled
-observation, one set of weights and one start among its members; a batch uploads every
-member's own together (one page-locked (P, n) array each, scaled by every member's
-x_scale in one launch).  Every member's x and w are bit-identical to its own run().
+P members of one shape advance together in a host-driven loop of, per iteration,
 
-Solvers form a stack when they agree in what member_key() lists; alpha, beta, b, x0,
-x_scale and the weights may differ.  Everything else runs `solver.run()`, one after the
-other ("sequential"): a tolerance (members do not stop one by one here), an observer that
-keeps iterates on the host, a verbose solver, a stack of one, a geometry the library
-declines on its first launch.
+    ops.tgv_stack_dual               every member's p and q, its own beta from a table
+    the blur over the stack          ConvolutionOperator._apply_stacked, or the one-pass
+                                     blur's epilogue r <- sigma A xbar + r per member
+    ops.pdl_stack_dual_data          every member's r, its own lambda = 1 / alpha
+    the adjoint blur over the stack
+    ops.tgv_stack_primal_lin         every member's x, w and the bars; tau, theta and the
+                                     box shared by value
+
+in groups that keep the state under ops.TGV_STACK_GROUP_BYTES, without a read-back or a
+synchronisation inside the loop.  The regulariser's side is tgv_stack.py's (k_tgv_dual_stack
+and its table), the data term's linear_stack.py's (StackedDataSide); what joins them is
+k_tgv_primal_lin_stack in nsol_tgv.hip.  A separable 1-D / 2-D blur runs in one launch per
+pass over the whole stack: 7 launches per iteration for a stack of 2-D images instead of
+7 P.  A 3-D blur runs member by member (2 P + 3 launches).  A sweep shares one scaled
+observation, one set of weights and one start among its members; a batch uploads every
+member's own together.  Every member's x and w are bit-identical to its own run().
+
+Solvers form a stack when their A and A_adj are ConvolutionOperators and they agree in
+what member_key() lists; alpha, beta, b, x0, x_scale and the weights may differ.
+Everything else runs `solver.run()`, one after the other ("sequential"): a tolerance
+(members do not stop one by one here), an observer that keeps iterates on the host, a
+verbose solver, foreign or NumPy-only callables, a SampledConvolutionOperator pair (m != n,
+which the stacked state does not hold), a stack of one, a geometry the library declines on
+its first launch.
 
 The two classes hold no front end of their own: they are solver_batch.PrimalDualBatch and
 parameter_sweep.PrimalDualSweep with this solver's key, operands, group size and runner
-(run_tgv_stack, on stacked_run's decline contract).  TGVPrimalDualLinearSolver's stacked
-forms are tgv_linear_stack.py's.
+(run_tgv_linear_stack, on stacked_run's decline contract).
 """
 import numpy as np
 
 from . import ops, tgv_numpy
 from .device import device_index, is_device_tensor, to_numpy
+from .linear_operators import ConvolutionOperator
+from .linear_stack import StackedDataSide, expects_epilogue, operator_key
 from .parameter_sweep import PrimalDualSweep, member_parameters
 from .solver_batch import PrimalDualBatch, plan_stacks, solver_key
 from .stacked_run import Launches
-from .tgv_solver import TGVPrimalDualSolver
+from .tgv_stack import member_table_values
+from .tgv_solver import TGVPrimalDualLinearSolver
 
 SWEEP_KEYS = ("alpha", "beta")
 
 
 def member_key(solver):
     """What the members of one stack share, or None for a solver that runs on its own:
-    shape, spacing, dimension, data_loss, isotropic, tau, sigma, theta, dtype, iteration
+    the operators (by value) and the shapes they are applied to, the volume's shape,
+    spacing, dimension, isotropic, data_loss, bounds, tau, sigma, theta, dtype, iteration
     count, a device-mode observer's points, whether the data term is weighted, and the
     devices of b, x0 and the weights."""
-    if not isinstance(solver, TGVPrimalDualSolver):
+    if not isinstance(solver, TGVPrimalDualLinearSolver):
         return None
+    op, op_adj = solver._op, solver._op_adj
+    if not (isinstance(op, ConvolutionOperator) and
+            isinstance(op_adj, ConvolutionOperator)):
+        return None             # foreign or NumPy-only callables, other operators
     own = solver_key(solver)
     if own is None:
         return None             # (a tolerance, its own stopping iteration, among them)
-    if solver._x0_ndim != 1:
+    if solver._m != solver._n or solver._x0_ndim != 1:
         return None
     b = solver._b
-    if int(b.numel() if is_device_tensor(b) else np.size(b)) != solver._n:
+    if int(b.numel() if is_device_tensor(b) else np.size(b)) != solver._m:
         return None             # (run() says what is wrong with it)
     w = solver._weights
-    return (tuple(solver._shape), tuple(float(v) for v in solver._spacing),
-            int(solver._dimension), solver._data_loss, bool(solver._isotropic),
-            float(solver._tau), float(solver._sigma), float(solver._theta)) + own[:3] + \
+    return (operator_key(op), tuple(solver._op_shape), operator_key(op_adj),
+            tuple(solver._op_adj_shape), tuple(solver._shape),
+            tuple(float(v) for v in solver._spacing), int(solver._dimension),
+            bool(solver._isotropic), solver._data_loss,
+            tuple(float(v) for v in solver._bounds), float(solver._tau),
+            float(solver._sigma), float(solver._theta)) + own[:3] + \
         (w is not None, ("b", device_index(b)), own[3], ("weights", device_index(w)))
 
 
-def member_table_values(tau, alphas, betas):
-    """(beta[m], tl[m] = tau / alpha[m]) in float64, as TGVPrimalDualSolver._run forms
-    them for its own launches; ops.tgv_stack_table rounds them to the working type."""
-    return (np.asarray([float(b) for b in betas], dtype=np.float64),
-            np.asarray([tau / float(a) for a in alphas], dtype=np.float64))
+def launches_per_iteration(solver, members):
+    """(stacked, loop of solvers): kernel launches per iteration of `members` runs like
+    `solver` -- the TGV dual step, the blur, the update of r, the adjoint blur, the
+    primal step."""
+    op, adj, P = solver._op, solver._op_adj, int(members)
+    one = max(op._launches(solver._op_shape), 1) + \
+        max(adj._launches(solver._op_adj_shape), 1) + 3
+    return (op.stacked_launches(solver._op_shape, P) +
+            adj.stacked_launches(solver._op_adj_shape, P) + 3, P * one)
 
 
-def run_tgv_stack(x_all, bt, wt, strided, template, alphas, betas, group, points,
-                  observe=None, taken=None):
+def run_tgv_linear_stack(x_all, bt, wt, strided, template, alphas, betas, group, points,
+                         observe=None, taken=None):
     """Advance the P = len(alphas) stacked runs whose start vectors x_all (P * n,
     member-major, solver units) holds; x_all holds the results afterwards.
 
@@ -98,34 +124,43 @@ def run_tgv_stack(x_all, bt, wt, strided, template, alphas, betas, group, points
     shape, iw = s._shape, ops.inv_spacing(s._spacing, d)
     tau, sigma, theta = s._tau, s._sigma, s._theta
     dflags = ops.PD_REG_ISOTROPIC if s._isotropic else 0
-    pflags = ops.PD_DATA_L1 if s._data_loss == "ell1" else 0
+    l1 = s._data_loss == "ell1"
+    lo, hi = s._bounds
+    # (tl is unused by the kLin step; the table checks it as it checks beta)
     beta_all, tl_all = member_table_values(tau, alphas, betas)
+    lm_all = ops.pdl_lambdas([1. / float(a) for a in alphas], x_all)
     points = set(points or ())
     w_all = x_all.new_zeros(P * d * n)
-    # a group's xbar, wbar, p and q, allocated once
+    # a group's xbar, wbar, p, q, r and g = A^T r, allocated once
     xbar_g, wbar_g = x_all.new_empty(group * n), x_all.new_empty(group * d * n)
     p_g, q_g = x_all.new_empty(group * d * n), x_all.new_empty(group * M * n)
+    r_g, g_g = x_all.new_empty(group * n), x_all.new_empty(group * n)
+    data = StackedDataSide(s, x_all, group, n)
     launches = Launches(taken)
     for a, b in ops.sweep_groups(P, group):
         g = b - a
         x, w = x_all[a * n:b * n], w_all[a * d * n:b * d * n]
         xbar, wbar = xbar_g[:g * n], wbar_g[:g * d * n]
         p, q = p_g[:g * d * n], q_g[:g * M * n]
+        r, gq = r_g[:g * n], g_g[:g * n]
         bt_m, wt_m = bt, wt
         if strided:
             bt_m, wt_m = bt[a * n:b * n], None if wt is None else wt[a * n:b * n]
         tab = ops.tgv_stack_table(x_all, beta_all[a:b], tl_all[a:b])
         if tab is None:
             return launches.declined("tgv_stack_table")
+        lm = lm_all[a:b]
         xbar.copy_(x)
         wbar.zero_()
         p.zero_()
         q.zero_()
+        r.zero_()
         for i in range(iters):
             if not (ops.tgv_stack_dual(xbar, wbar, p, q, g, shape, iw, sigma, tab, dflags)
-                    and ops.tgv_stack_primal(p, q, x, xbar, w, wbar, bt_m, g, shape, iw,
-                                             tau, tab, theta, pflags, wt=wt_m)):
-                return launches.declined("tgv_stack")
+                    and data.dual_step(xbar, r, bt_m, wt_m, sigma, lm, g, l1, gq)
+                    and ops.tgv_stack_primal_lin(p, q, x, xbar, w, wbar, gq, g, shape, iw,
+                                                 tau, theta, lo, hi)):
+                return launches.declined("tgv_stack_primal_lin")
             launches.accepted()
             if observe is not None and (i + 1) in points:
                 for m in range(a, b):
@@ -134,12 +169,19 @@ def run_tgv_stack(x_all, bt, wt, strided, template, alphas, betas, group, points
     return w_all
 
 
-class TGVPrimalDualBatch(PrimalDualBatch):
-    """PrimalDualBatch's interface for TGVPrimalDualSolver objects: its __init__, run()
-    and upload, with this solver's key, operands and runner.  Every stacked member also
-    answers get_w() as after its own run().  The members never stop one by one."""
+def _group_size(template, members, n, itemsize, own_data, own_weights):
+    return ops.tgv_lin_stack_group_size(
+        members, n, template._dimension, itemsize, own_data=own_data,
+        own_weights=own_weights,
+        with_t=not expects_epilogue(template._op, template._op_shape))
 
-    _solver_type = TGVPrimalDualSolver
+
+class TGVPrimalDualLinearBatch(PrimalDualBatch):
+    """PrimalDualBatch's interface for TGVPrimalDualLinearSolver objects: its __init__,
+    run() and upload, with this solver's key, operands and runner.  Every stacked member
+    also answers get_w() as after its own run().  The members never stop one by one."""
+
+    _solver_type = TGVPrimalDualLinearSolver
     _stops_members = False
 
     def _stacks_to_try(self):
@@ -162,10 +204,11 @@ class TGVPrimalDualBatch(PrimalDualBatch):
         solvers = [self._solvers[i] for i in idx]
         s0, P = solvers[0], len(solvers)
         n, d = x_all.numel() // P, s0._dimension
-        G = ops.tgv_stack_group_size(P, n, d, x_all.element_size(), wt is not None)
-        w_all = run_tgv_stack(x_all, bt, wt, True, s0, [s._alpha for s in solvers],
-                              [s._beta for s in solvers], G, points, observe=observe,
-                              taken=taken)
+        G = _group_size(s0, P, n, x_all.element_size(), True, wt is not None)
+        w_all = run_tgv_linear_stack(x_all, bt, wt, True, s0,
+                                     [s._alpha for s in solvers],
+                                     [s._beta for s in solvers], G, points,
+                                     observe=observe, taken=taken)
         if w_all is None:
             return None
         for m, s in enumerate(solvers):
@@ -173,20 +216,21 @@ class TGVPrimalDualBatch(PrimalDualBatch):
         return G, None
 
 
-class TGVPrimalDualSweep(PrimalDualSweep):
-    """PrimalDualSweep's interface for an (alpha, beta) sweep of TGVPrimalDualSolver on one
-    observation: TGVPrimalDualSweep(b, x0, dimension, parameters={"alpha": [...],
-    "beta": [...]}, **solver_kwargs) with TGVPrimalDualSolver's keyword arguments; the
-    members are itertools.product over the lists in the dictionary's key order, and a
-    parameter that is not swept keeps its keyword's value.  get_w(m) is member m's second
-    primal variable.  A sweep with a `tolerance`, or one the library declines, runs its
-    members one after the other through plain solvers."""
+class TGVPrimalDualLinearSweep(PrimalDualSweep):
+    """PrimalDualSweep's interface for an (alpha, beta) sweep of TGVPrimalDualLinearSolver
+    on one observation: TGVPrimalDualLinearSweep(A, A_adj, b, x0, dimension,
+    parameters={"alpha": [...], "beta": [...]}, **solver_kwargs) with
+    TGVPrimalDualLinearSolver's keyword arguments; the members are itertools.product over
+    the lists in the dictionary's key order, and a parameter that is not swept keeps its
+    keyword's value.  get_w(m) is member m's second primal variable.  A sweep with a
+    `tolerance`, or one the library declines, runs its members one after the other
+    through plain solvers."""
 
-    def __init__(self, b, x0, dimension, parameters, **solver_kwargs):
+    def __init__(self, A, A_adj, b, x0, dimension, parameters, **solver_kwargs):
         members = member_parameters(parameters, keys=SWEEP_KEYS)
         kw = dict(solver_kwargs)
         self._defaults = dict(alpha=kw.pop("alpha", 0.01), beta=kw.pop("beta", 2.0))
-        self._args = dict(b=b, x0=x0, dimension=dimension)
+        self._args = dict(A=A, A_adj=A_adj, b=b, x0=x0, dimension=dimension)
         self._kwargs = kw
         template = self._solver(members[0])          # the arguments' own refusals
         self._init_state(x0, members, template._iterations, template._tolerance,
@@ -197,8 +241,8 @@ class TGVPrimalDualSweep(PrimalDualSweep):
     def _solver(self, member=None):
         kw = dict(self._defaults)
         kw.update(member or {})
-        return TGVPrimalDualSolver(alpha=kw["alpha"], beta=kw["beta"], **self._args,
-                                   **self._kwargs)
+        return TGVPrimalDualLinearSolver(alpha=kw["alpha"], beta=kw["beta"],
+                                         **self._args, **self._kwargs)
 
     def run(self):
         self._w_all = self._w_list = None
@@ -232,15 +276,15 @@ class TGVPrimalDualSweep(PrimalDualSweep):
         bt = scaled_data_on_device(template._b, template._x_scale, x0)
         wt = None if template._weights is None else \
             weights_on_device(template._weights, x0)
-        return bt, wt, ops.tgv_stack_group_size(
-            len(self._members), x0.numel(), template._dimension, x0.element_size(),
-            wt is not None, own_data=False)
+        return bt, wt, _group_size(template, len(self._members), x0.numel(),
+                                   x0.element_size(), False, False)
 
     def _advance(self, template, form, x_all, bt, wt, group, points, observe, x0):
         kws = [dict(self._defaults, **member) for member in self._members]
-        w_all = run_tgv_stack(x_all, bt, wt, False, template,
-                              [kw["alpha"] for kw in kws], [kw["beta"] for kw in kws],
-                              group, points, observe=observe)
+        w_all = run_tgv_linear_stack(x_all, bt, wt, False, template,
+                                     [kw["alpha"] for kw in kws],
+                                     [kw["beta"] for kw in kws], group, points,
+                                     observe=observe)
         if w_all is None:
             return None
         self._w_all = w_all
@@ -248,7 +292,7 @@ class TGVPrimalDualSweep(PrimalDualSweep):
 
     def get_w(self, m):
         """Member m's second primal variable times x_scale, dimension * n values, as
-        TGVPrimalDualSolver.get_w() gives it."""
+        TGVPrimalDualLinearSolver.get_w() gives it."""
         if self._w_all is not None:
             dn = self._w_all.numel() // len(self._members)
             return to_numpy(ops.scale(self._w_all[m * dn:(m + 1) * dn], self._x_scale))
