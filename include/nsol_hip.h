@@ -1056,6 +1056,56 @@ int nsol_pdl_stack_iter_f64(const double *xbar_in, double *xbar_out, double *x,
     double tau, double theta, double lo, double hi, int flags, int has_p, void *stream);
 
 /* ---------------------------------------------------------------------- *
+ * The Poisson (Kullback-Leibler) data term (csrc/nsol_kl.hpp holds both proxes; the
+ * arithmetic is restated in nsol_amd/vector_numpy.py, kl_dual_prox and prox_kl):
+ *   D(u; bt) = sum_i w_i ((u_i + bg) - bt_i log(u_i + bg)),   bt_i >= 0 where w_i > 0,
+ * the negative Poisson log-likelihood up to a constant, bg >= 0 a constant background.
+ *
+ * nsol_pdl_dual_data_kl_*: nsol_pdl_dual_data_* for lambda D(A x; bt), q in place:
+ *   t != NULL: v = q + sigma * (t + bg);   t == NULL: v = q + sigma * bg;
+ *   c = lmbda * w (w = 1 where wt == NULL), d = v - c, s = sqrt(d * d + 4 * sigma * c * bt);
+ *   q = d > 0 ? c - (2 * sigma * c * bt) / (d + s) : c + 0.5 * (d - s)
+ *   (one number in two forms, each free of the other's cancellation; q <= c);
+ *   w_i == 0: q = 0 exactly, whatever bt holds there (NaN included).
+ * NSOL_EINVAL: as nsol_pdl_dual_data_*, and a bg that is negative or not finite.
+ * nsol_pdl_stack_dual_data_kl_*: the same on every member in one launch, with the
+ * contract of nsol_pdl_stack_dual_data_* (grid y = member, lmbda a device array, strides
+ * 0 or n, -2 declines); member m is bit-identical to nsol_pdl_dual_data_kl_* on it.
+ *
+ * nsol_prox_kl_*: the prox of tl * w * D (no background), out may be x, wt may be NULL
+ * (all 1):  t = tl * w, e = x - t, s = sqrt(e * e + 4 * t * bt);
+ *   out = e >= 0 ? 0.5 * (e + s) : (2 * t * bt) / (s - e)         (always >= 0);
+ *   w_i == 0: out = x exactly, whatever bt holds there.
+ * NSOL_EINVAL: a missing out, x or bt, tl negative or not finite, n < 0.
+ *
+ * nsol_tgv_primal_kl_*: nsol_tgv_primal_w_* with that prox as the x step (wt may be
+ * NULL); w and wbar come out with the bits nsol_tgv_primal_* gives them.  Returns as
+ * nsol_tgv_primal_w_*; counted by nsol_tgv_launches.
+ * Divisions and square roots are IEEE ones in both element types. */
+int nsol_pdl_dual_data_kl_f32(float *q, const float *t, const float *bt, const float *wt,
+    double sigma, double lmbda, double bg, int64_t n, void *stream);
+int nsol_pdl_dual_data_kl_f64(double *q, const double *t, const double *bt,
+    const double *wt, double sigma, double lmbda, double bg, int64_t n, void *stream);
+int nsol_pdl_stack_dual_data_kl_f32(float *q, const float *t, const float *bt,
+    int64_t bt_stride, const float *wt, int64_t wt_stride, double sigma,
+    const float *lmbda, double bg, int members, int64_t n, void *stream);
+int nsol_pdl_stack_dual_data_kl_f64(double *q, const double *t, const double *bt,
+    int64_t bt_stride, const double *wt, int64_t wt_stride, double sigma,
+    const double *lmbda, double bg, int members, int64_t n, void *stream);
+int nsol_prox_kl_f32(float *out, const float *x, const float *bt, const float *wt,
+    double tl, int64_t n, void *stream);
+int nsol_prox_kl_f64(double *out, const double *x, const double *bt, const double *wt,
+    double tl, int64_t n, void *stream);
+int nsol_tgv_primal_kl_f32(const float *p, const float *q, float *x, float *xbar,
+    float *w, float *wbar, const float *bt, const float *wt, int ndim, int64_t nz,
+    int64_t ny, int64_t nx, double wx, double wy, double wz, double tau, double tl,
+    double theta, void *stream);
+int nsol_tgv_primal_kl_f64(const double *p, const double *q, double *x, double *xbar,
+    double *w, double *wbar, const double *bt, const double *wt, int ndim, int64_t nz,
+    int64_t ny, int64_t nx, double wx, double wy, double wz, double tau, double tl,
+    double theta, void *stream);
+
+/* ---------------------------------------------------------------------- *
  * Second-order total generalised variation, TGV^2 (nsol_tgv.hip; the arithmetic is
  * restated in nsol_amd/tgv_numpy.py):
  *   min over x (n values), w (ndim * n)

@@ -16,7 +16,9 @@ saddle-point problem's linear map instead of the primal prox, so no iteration so
 linear system (one blur, one adjoint blur and two element-wise / stencil passes per
 iteration).  It takes --isotropic, --tolerance / --check-every, --observe-every,
 --mask FILE (voxels > 0 count) or --weights FILE (per-voxel weights of the data term,
-as in run_denoising), --data-loss ell1 for sum w_i |(A x - b)_i| ("linear" is the l2
+as in run_denoising), --data-loss kl [--background B] for Poisson counts, the
+Kullback-Leibler term sum w_i ((A x + B)_i - b_i log (A x + B)_i) with the options ell1
+takes, --data-loss ell1 for sum w_i |(A x - b)_i| ("linear" is the l2
 data term) and --nonnegative for the exact projection onto x >= 0.  --L2 is not used:
 the step sizes come from the operator norms.  PDL needs more iterations than PD, each
 of them far cheaper.
@@ -85,9 +87,11 @@ def _regulariser(reconstruction_type):
 
 def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.01,
                iterations=10, verbose=0, dtype=None, tolerance=None, check_every=10,
-               weights=None, pdl_data_loss="ell2", nonnegative=False, isotropic=False):
+               weights=None, pdl_data_loss="ell2", nonnegative=False, isotropic=False,
+               background=0.):
     """The keyword arguments PrimalDualLinearSolver (tv_solver="PDL") and
-    PrimalDualLinearSweep are built from."""
+    PrimalDualLinearSweep are built from.  background (in the observation's units) goes
+    with pdl_data_loss="kl"."""
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -119,7 +123,13 @@ def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.
         **_regulariser(reconstruction_type),
         isotropic=isotropic, data_loss=pdl_data_loss, weights=weights,
         bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
-        verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every)
+        verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every,
+        **_background(background))
+
+
+def _background(background):
+    """The solvers' background= where there is one (their default otherwise)."""
+    return dict(background=background) if background else {}
 
 
 def fine_grid(shape, spacing, factors):
@@ -137,7 +147,8 @@ def fine_grid(shape, spacing, factors):
 def sampled_pdl_wiring(observed_nda, spacing, blur, factors, offsets=None,
                        reconstruction_type="TVL2", alpha=0.01, iterations=10, verbose=0,
                        dtype=None, tolerance=None, check_every=10, weights=None,
-                       pdl_data_loss="ell2", nonnegative=False, isotropic=False):
+                       pdl_data_loss="ell2", nonnegative=False, isotropic=False,
+                       background=0.):
     """PrimalDualLinearSolver's keyword arguments for --upsample: the observation is
     the coarse data of a SampledConvolutionOperator on the fine grid."""
     dimension = observed_nda.ndim
@@ -176,7 +187,7 @@ def sampled_pdl_wiring(observed_nda, spacing, blur, factors, offsets=None,
         isotropic=isotropic, data_loss=pdl_data_loss, weights=weights,
         bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
         verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every,
-        shape=fine_shape)
+        shape=fine_shape, **_background(background))
 
 
 def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
@@ -185,8 +196,9 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  data_loss_scale=1., L2=8, verbose=0, dtype=None,
                  tolerance=None, check_every=10, weights=None, pdl_data_loss="ell2",
                  nonnegative=False, upsample=None, sample_offset=None, beta=2.0,
-                 isotropic=False):
-    """weights, pdl_data_loss ("ell2" | "ell1") and nonnegative belong to
+                 background=0., isotropic=False):
+    """weights, pdl_data_loss ("ell2" | "ell1" | "kl", the last with background, a
+    constant in the observation's units) and nonnegative belong to
     tv_solver="PDL" (PrimalDualLinearSolver), and so do upsample / sample_offset (one
     integer per array axis: the observation is the coarse data, sampled_pdl_wiring).
     reconstruction_type "TGVL2" with tv_solver "PDL" is TGVPrimalDualLinearSolver on the
@@ -199,11 +211,12 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
             kw = sampled_pdl_wiring(
                 observed_nda, spacing, blur, upsample, sample_offset, "TGVL2", alpha,
                 iterations, verbose, dtype, tolerance, check_every, weights,
-                pdl_data_loss, nonnegative, isotropic)
+                pdl_data_loss, nonnegative, isotropic, background)
         else:
             kw = pdl_wiring(
                 observed_nda, spacing, blur, "TGVL2", alpha, iterations, verbose, dtype,
-                tolerance, check_every, weights, pdl_data_loss, nonnegative, isotropic)
+                tolerance, check_every, weights, pdl_data_loss, nonnegative, isotropic,
+                background)
         return TGVPrimalDualLinearSolver(beta=beta, **kw)
     if upsample is not None:
         if not (reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL"):
@@ -211,12 +224,12 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
         return pdl.PrimalDualLinearSolver(**sampled_pdl_wiring(
             observed_nda, spacing, blur, upsample, sample_offset, reconstruction_type,
             alpha, iterations, verbose, dtype, tolerance, check_every, weights,
-            pdl_data_loss, nonnegative, isotropic))
+            pdl_data_loss, nonnegative, isotropic, background))
     if reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL":
         return pdl.PrimalDualLinearSolver(**pdl_wiring(
             observed_nda, spacing, blur, reconstruction_type, alpha, iterations,
             verbose, dtype, tolerance, check_every, weights, pdl_data_loss,
-            nonnegative, isotropic))
+            nonnegative, isotropic, background))
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -240,8 +253,8 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                   x_scale=x_scale, data_loss=data_loss,
                   data_loss_scale=data_loss_scale, iter_max=iter_max,
                   verbose=verbose, dtype=dtype)
-    if weights is not None or nonnegative:
-        raise ValueError("weights and nonnegative belong to tv_solver='PDL'")
+    if weights is not None or nonnegative or background:
+        raise ValueError("weights, nonnegative and background belong to tv_solver='PDL'")
     if reconstruction_type == "TK0L2":
         return tk.TikhonovLinearSolver(B=I_1D, B_adj=I_1D,
                                        minimizer=minimizer, **common)
@@ -280,8 +293,13 @@ def _pdl_arguments(args):
     the command line."""
     return dict(dtype=np.dtype(args.dtype).type, isotropic=args.isotropic,
                 tolerance=args.tolerance, check_every=args.check_every,
-                pdl_data_loss="ell1" if args.data_loss == "ell1" else "ell2",
-                nonnegative=args.nonnegative)
+                pdl_data_loss=_pdl_data_loss(args),
+                nonnegative=args.nonnegative, **_background(args.background))
+
+
+def _pdl_data_loss(args):
+    """--data-loss as the PDL solvers name it ("linear" is their l2 data term)."""
+    return args.data_loss if args.data_loss in ("ell1", "kl") else "ell2"
 
 
 def run_sweep(args, observed_nda, spacing, x_ref, info, weights=None):
@@ -392,6 +410,10 @@ def build_parser():
     ap.add_argument("--minimizer", default="lsmr")
     ap.add_argument("--data-loss", default="linear")
     ap.add_argument("--data-loss-scale", type=float, default=1.)
+    ap.add_argument("--background", type=float, default=None, metavar="B",
+                    help="--solver PDL --data-loss kl: a known constant background "
+                         ">= 0 in the observation's units (dark current, scatter): "
+                         "the counts are Poisson with mean A x + B")
     ap.add_argument("--L2", type=float, default=8,
                     help="--solver PD: the bound of the operator norm its steps come "
                          "from.  Not used by --solver PDL, TGVL2 included: there the steps "
@@ -470,9 +492,16 @@ def parse_args(argv=None, ap=None):
     linear = args.solver == "PDL"
     if linear and not primal_dual:
         ap.error("--solver PDL applies to --reconstruction-type TVL2, HuberL2 or TGVL2")
-    if linear and args.data_loss not in ("linear", "ell2", "ell1"):
-        ap.error("--solver PDL takes --data-loss linear (the l2 data term) or ell1, "
-                 "not '%s'" % args.data_loss)
+    if linear and args.data_loss not in ("linear", "ell2", "ell1", "kl"):
+        ap.error("--solver PDL takes --data-loss linear (the l2 data term), ell1 or kl "
+                 "(Poisson counts), not '%s'" % args.data_loss)
+    if args.background is not None:
+        if not (linear and args.data_loss == "kl"):
+            ap.error("--background goes with --solver PDL --data-loss kl")
+        if not (np.isfinite(args.background) and args.background >= 0):
+            ap.error("--background must be a finite number >= 0")
+    else:
+        args.background = 0.
     if args.nonnegative and not linear:
         ap.error("--nonnegative is an option of --solver PDL")
     if args.tolerance is not None and not primal_dual:
@@ -572,6 +601,7 @@ def main(argv=None):
                                                   sample_offset=args.sample_offset)
     if args.reconstruction_type == "TGVL2":
         extra["beta"] = args.beta
+    extra.update(_background(args.background))
     for alpha in args.alpha:
         solver = build_solver(
             observed_nda, spacing, args.blur, args.reconstruction_type,
@@ -579,7 +609,7 @@ def main(argv=None):
             args.minimizer, args.data_loss, args.data_loss_scale, args.L2,
             args.verbose, np.dtype(args.dtype).type, isotropic=args.isotropic,
             tolerance=args.tolerance, check_every=args.check_every, weights=weights,
-            pdl_data_loss="ell1" if args.data_loss == "ell1" else "ell2",
+            pdl_data_loss=_pdl_data_loss(args),
             nonnegative=args.nonnegative, **extra)
         obs = None
         if x_ref is not None:

@@ -11,7 +11,7 @@
 // A and A^T are the caller's (the one-pass blur of nsol_blur3_*.hip where it applies);
 // this unit holds the two kernels around them:
 //   * k_pdl_dual_data: the element-wise update of q, weights, masks and the l1 data
-//     term included;
+//     term included; k_pdl_dual_data_kl: the same for the Poisson (KL) data term;
 //   * k_pd_lin / k_pd_lin_iso: the regulariser's dual update and the explicit primal
 //     step in ONE pass -- the tile bodies pd_fused_tile / pd_fused_iso_tile with LIN
 //     on: the array in bt's place holds g = A^T q, the data prox is the step and the
@@ -26,6 +26,7 @@
 #include <atomic>
 
 #include "nsol_common.hpp"
+#include "nsol_kl.hpp"
 #include "nsol_pd_common.hpp"
 #include "nsol_pd_fused_body.hpp"
 #include "nsol_pd_iso_body.hpp"
@@ -155,6 +156,34 @@ int dual_data_impl(T *q, const T *t, const T *bt, const T *wt, double sigma, dou
   return launch_status();
 }
 
+// The same pass for the Poisson (Kullback-Leibler) data term with a constant background
+// bg >= 0, lambda sum w ((A x + bg) - bt log(A x + bg)): v = q + sigma * (t + bg), or, t
+// null, v = q + sigma * bg; then kl_dual_prox of nsol_kl.hpp (0 where w == 0).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pdl_dual_data_kl(
+    T *q, const T *__restrict__ t, const T *__restrict__ bt, const T *__restrict__ wt,
+    T sigma, T lmbda, T bg, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const T w = wt ? wt[i] : T(1);
+    const T v = t ? q[i] + sigma * (t[i] + bg) : q[i] + sigma * bg;
+    q[i] = kl_dual_prox<T>(v, bt[i], w, sigma, lmbda);
+  }
+}
+
+template <typename T>
+int dual_data_kl_impl(T *q, const T *t, const T *bt, const T *wt, double sigma,
+                      double lmbda, double bg, int64_t n, void *stream) {
+  if (n < 0) return NSOL_EINVAL;
+  if (n == 0) return 0;
+  if (!q || !bt || q == t || !(sigma > 0.0) || !(lmbda >= 0.0) ||
+      !(isfinite(bg) && bg >= 0.0))
+    return NSOL_EINVAL;
+  hipLaunchKernelGGL((k_pdl_dual_data_kl<T>), dim3(grid_for(n)), dim3(kBlock), 0,
+                     as_stream(stream), q, t, bt, wt, (T)sigma, (T)lmbda, (T)bg, n);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -166,6 +195,11 @@ int nsol_pdl_launches(void) { return g_lin_launches.load(std::memory_order_relax
                                double sigma, double lmbda, int l1, int64_t n,          \
                                void *s) {                                              \
     return dual_data_impl<T>(q, t, bt, wt, sigma, lmbda, l1, n, s);                    \
+  }                                                                                    \
+  int nsol_pdl_dual_data_kl_##SUF(T *q, const T *t, const T *bt, const T *wt,          \
+                                  double sigma, double lmbda, double bg, int64_t n,    \
+                                  void *s) {                                           \
+    return dual_data_kl_impl<T>(q, t, bt, wt, sigma, lmbda, bg, n, s);                 \
   }                                                                                    \
   int nsol_pdl_iter_##SUF(const T *xi, T *xo, T *x, const T *g, const T *pi, T *po,    \
                           int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,     \

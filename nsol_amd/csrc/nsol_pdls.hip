@@ -19,6 +19,7 @@
 #include <atomic>
 
 #include "nsol_common.hpp"
+#include "nsol_kl.hpp"
 #include "nsol_pd_common.hpp"
 #include "nsol_pd_fused_body.hpp"
 #include "nsol_pd_iso_body.hpp"
@@ -167,6 +168,42 @@ int dual_data_stack_impl(T *q, const T *t, const T *bt, int64_t bt_stride, const
   return launch_status();
 }
 
+// k_pdl_dual_data_kl (nsol_pdl.hip) on member m = blockIdx.y, expression for expression.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pdl_dual_data_kl_stack(
+    T *q_all, const T *__restrict__ t_all, const T *__restrict__ bt_all,
+    int64_t bt_stride, const T *__restrict__ wt_all, int64_t wt_stride, T sigma,
+    const T *__restrict__ lmbda_all, T bg, int64_t n) {
+  const int64_t m = blockIdx.y;
+  T *q = q_all + m * n;
+  const T *t = t_all ? t_all + m * n : nullptr;
+  const T *bt = bt_all + m * bt_stride;
+  const T *wt = wt_all ? wt_all + m * wt_stride : nullptr;
+  const T lmbda = lmbda_all[m];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const T w = wt ? wt[i] : T(1);
+    const T v = t ? q[i] + sigma * (t[i] + bg) : q[i] + sigma * bg;
+    q[i] = kl_dual_prox<T>(v, bt[i], w, sigma, lmbda);
+  }
+}
+
+template <typename T>
+int dual_data_kl_stack_impl(T *q, const T *t, const T *bt, int64_t bt_stride, const T *wt,
+                            int64_t wt_stride, double sigma, const T *lmbda, double bg,
+                            int members, int64_t n, void *stream) {
+  if (n < 0) return NSOL_EINVAL;
+  if (!pd_members_ok(members) || n > (int64_t(1) << 31) / members) return -2;
+  if (n == 0) return 0;
+  if (!q || !bt || !lmbda || q == t || !(sigma > 0.0) || !pd_stride_ok(bt_stride, n) ||
+      (wt && !pd_stride_ok(wt_stride, n)) || !(isfinite(bg) && bg >= 0.0))
+    return NSOL_EINVAL;
+  const dim3 grid((unsigned)grid_for(n), (unsigned)members), block(kBlock);
+  hipLaunchKernelGGL((k_pdl_dual_data_kl_stack<T>), grid, block, 0, as_stream(stream), q,
+                     t, bt, bt_stride, wt, wt_stride, (T)sigma, lmbda, (T)bg, n);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,6 +219,14 @@ int nsol_pdl_stack_launches(void) {
                                      void *s) {                                        \
     return dual_data_stack_impl<T>(q, t, bt, bt_stride, wt, wt_stride, sigma, lmbda,   \
                                    l1, members, n, s);                                 \
+  }                                                                                    \
+  int nsol_pdl_stack_dual_data_kl_##SUF(T *q, const T *t, const T *bt,                 \
+                                        int64_t bt_stride, const T *wt,                \
+                                        int64_t wt_stride, double sigma,               \
+                                        const T *lmbda, double bg, int members,        \
+                                        int64_t n, void *s) {                          \
+    return dual_data_kl_stack_impl<T>(q, t, bt, bt_stride, wt, wt_stride, sigma,       \
+                                      lmbda, bg, members, n, s);                       \
   }                                                                                    \
   int nsol_pdl_stack_iter_##SUF(const T *xi, T *xo, T *x, const T *g, const T *pi,     \
                                 T *po, int members, int ndim, int64_t nz, int64_t ny,  \

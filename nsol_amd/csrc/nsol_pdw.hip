@@ -22,6 +22,7 @@
 #include <atomic>
 
 #include "nsol_common.hpp"
+#include "nsol_kl.hpp"
 #include "nsol_pd_common.hpp"
 #include "nsol_pd_fused_body.hpp"
 #include "nsol_pd_iso_body.hpp"
@@ -192,6 +193,29 @@ int prox_w_impl(T *out, const T *x, const T *bt, const T *wt, double tau, int64_
   return launch_status();
 }
 
+// The prox of the Poisson (Kullback-Leibler) data term, prox_kl of nsol_kl.hpp; wt may
+// be null (all 1), a uniform branch on the pointer.  out may be x, as above.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_prox_kl(T *out, const T *x,
+                                                    const T *__restrict__ bt,
+                                                    const T *__restrict__ wt, T tl,
+                                                    int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    out[i] = prox_kl<T>(x[i], bt[i], wt ? wt[i] : T(1), tl);
+}
+
+template <typename T>
+int prox_kl_impl(T *out, const T *x, const T *bt, const T *wt, double tl, int64_t n,
+                 void *stream) {
+  if (n < 0) return NSOL_EINVAL;
+  if (n == 0) return 0;
+  if (!out || !x || !bt || !(isfinite(tl) && tl >= 0.0)) return NSOL_EINVAL;
+  hipLaunchKernelGGL((k_prox_kl<T>), dim3(grid_for(n)), dim3(kBlock), 0,
+                     as_stream(stream), out, x, bt, wt, (T)tl, n);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -204,6 +228,10 @@ int nsol_pd_weighted_launches(void) {
   int nsol_prox_ell2_weighted_##SUF(T *out, const T *x, const T *bt, const T *wt,      \
                                     double tau, int64_t n, void *s) {                  \
     return prox_w_impl<T, false>(out, x, bt, wt, tau, n, s);                           \
+  }                                                                                    \
+  int nsol_prox_kl_##SUF(T *out, const T *x, const T *bt, const T *wt, double tl,      \
+                         int64_t n, void *s) {                                         \
+    return prox_kl_impl<T>(out, x, bt, wt, tl, n, s);                                  \
   }                                                                                    \
   int nsol_prox_ell1_weighted_##SUF(T *out, const T *x, const T *bt, const T *wt,      \
                                     double tau, int64_t n, void *s) {                  \

@@ -20,6 +20,8 @@
 //   k_tgv_primal_w, k_tgv_primal_lin: the same body with the weighted prox (one more
 //                 read-only stream wt) or, for a data term behind a linear operator A, the
 //                 explicit clipped step on g = A^T r in b~'s place (TgvForm below).
+//   k_tgv_primal_kl: the same body with the prox of the Poisson (Kullback-Leibler) data
+//                 term, prox_kl of nsol_kl.hpp; wt may be null.
 //   k_tgv_dual_stack, k_tgv_primal_stack, k_tgv_primal_w_stack, k_tgv_primal_lin_stack:
 //                 the same device functions
 //                 on member blockIdx.z of a stack of independent problems of one shape (a
@@ -44,6 +46,7 @@
 #include <type_traits>
 
 #include "nsol_common.hpp"
+#include "nsol_kl.hpp"
 #include "nsol_pd_iso_body.hpp"
 #include "nsol_pd_launch.hpp"
 #include "nsol_pd_lin_step.hpp"
@@ -237,7 +240,9 @@ __global__ __launch_bounds__(kBlock) void k_tgv_dual_stack(
 //           read-only stream (23 words per voxel in 3-D); wt == 0 keeps u
 //   kLin    lin_step(x, sum_a D_a^T p_a, g) of nsol_pd_lin_step.hpp: the array in b~'s
 //           place holds g = A^T r and the step is explicit, clipped to [lo, hi] (22 words)
-enum TgvForm { kPlain = 0, kWgt = 1, kLin = 2 };
+//   kKl     prox_kl(u, b~, wt) of nsol_kl.hpp: the Poisson (Kullback-Leibler) data term;
+//           wt may be null (all weights 1), a uniform branch on the pointer
+enum TgvForm { kPlain = 0, kWgt = 1, kLin = 2, kKl = 3 };
 
 template <typename T, int VEC, int ROWS, int NDIM, bool RAG, bool L1, int FORM>
 __device__ __forceinline__ void tgv_primal_body(
@@ -260,6 +265,14 @@ __device__ __forceinline__ void tgv_primal_body(
     vlc<RAG, T, VEC>(c, x + c.i, v);
     vlc<RAG, T, VEC>(c, bt + c.i, t);
     if constexpr (FORM == kWgt) vlc<RAG, T, VEC>(c, wt + c.i, own);
+    if constexpr (FORM == kKl) {
+      if (wt) {
+        vlc<RAG, T, VEC>(c, wt + c.i, own);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) own[k] = T(1);
+      }
+    }
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       T xn;
@@ -267,6 +280,8 @@ __device__ __forceinline__ void tgv_primal_body(
         xn = lin_step<T>(v[k], acc[k], t[k], tau, lo, hi);
       else if constexpr (FORM == kWgt)
         xn = prox_data_w<T>(v[k] - tau * acc[k], t[k], own[k], tl, L1);
+      else if constexpr (FORM == kKl)
+        xn = prox_kl<T>(v[k] - tau * acc[k], t[k], own[k], tl);
       else
         xn = prox_data<T>(v[k] - tau * acc[k], t[k], tl, den, L1);
       o[k] = xn + theta * (xn - v[k]);
@@ -325,6 +340,14 @@ __global__ __launch_bounds__(kBlock) void k_tgv_primal_lin(
     const T *__restrict__ g, Geom<T> G, T tau, T theta, T lo, T hi) {
   tgv_primal_body<T, VEC, ROWS, NDIM, RAG, false, kLin>(p, q, x, xbar, w, wbar, g, nullptr,
                                                         G, tau, T(0), T(0), theta, lo, hi);
+}
+
+template <typename T, int VEC, int ROWS, int NDIM, bool RAG>
+__global__ __launch_bounds__(kBlock) void k_tgv_primal_kl(
+    const T *__restrict__ p, const T *__restrict__ q, T *x, T *xbar, T *w, T *wbar,
+    const T *__restrict__ bt, const T *__restrict__ wt, Geom<T> G, T tau, T tl, T theta) {
+  tgv_primal_body<T, VEC, ROWS, NDIM, RAG, false, kKl>(p, q, x, xbar, w, wbar, bt, wt, G,
+                                                       tau, tl, T(0), theta, T(0), T(0));
 }
 
 // tgv_primal_body (kPlain, kWgt) on member m = blockIdx.z: the state at member-major
@@ -520,6 +543,38 @@ int tgv_primal_w_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, cons
     else
       hipLaunchKernelGGL((k_tgv_primal_w<T, V, R, D, RG, false>), grid, dim3(kBlock), 0, st,
                          p, q, x, xbar, w, wbar, bt, wt, G, (T)tau, (T)tl, (T)theta);
+    return launch_status();
+  });
+}
+
+// wt may be null: all weights 1
+template <typename T>
+int tgv_primal_kl_impl(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar, const T *bt,
+                       const T *wt, int ndim, int64_t nz, int64_t ny, int64_t nx, double wx,
+                       double wy, double wz, double tau, double tl, double theta,
+                       void *stream) {
+  const int gr = tgv_geometry(ndim, nz, ny, nx, 0);
+  if (gr) return gr == 1 ? 0 : gr;
+  const int64_t nb = nz * ny * nx * (int64_t)sizeof(T), M = ndim * (ndim + 1) / 2;
+  const Span spans[] = {{p, ndim * nb}, {q, M * nb},       {x, nb},  {xbar, nb},
+                        {w, ndim * nb}, {wbar, ndim * nb}, {bt, nb},
+                        // (no weights: an empty span, which overlaps nothing)
+                        {wt ? wt : bt, wt ? nb : 0}};
+  if (spans_bad(spans) || !positive(tau) || !(isfinite(tl) && tl >= 0.0) ||
+      !isfinite(theta))
+    return NSOL_EINVAL;
+  const Geom<T> G = make_geom<T>(ndim, nz, ny, nx, wx, wy, wz);
+  const bool al = aligned16(p) && aligned16(q) && aligned16(x) && aligned16(xbar) &&
+                  aligned16(w) && aligned16(wbar) && aligned16(bt) &&
+                  (!wt || aligned16(wt));
+  const hipStream_t st = as_stream(stream);
+  return tgv_dispatch<T>(ndim, nz, ny, nx, al, [&](auto vec, auto rows, auto rag, auto nd) {
+    constexpr int V = decltype(vec)::value, R = decltype(rows)::value;
+    constexpr int D = decltype(nd)::value;
+    constexpr bool RG = decltype(rag)::value;
+    const dim3 grid = stencil_grid<V, R>(nz, ny, nx);
+    hipLaunchKernelGGL((k_tgv_primal_kl<T, V, R, D, RG>), grid, dim3(kBlock), 0, st, p, q,
+                       x, xbar, w, wbar, bt, wt, G, (T)tau, (T)tl, (T)theta);
     return launch_status();
   });
 }
@@ -754,6 +809,13 @@ int nsol_tgv_stack_launches(void) {
                               double tl, double theta, int flags, void *s) {              \
     return tgv_primal_w_impl<T>(p, q, x, xbar, w, wbar, bt, wt, ndim, nz, ny, nx, wx, wy, \
                                 wz, tau, tl, theta, flags, s);                            \
+  }                                                                                       \
+  int nsol_tgv_primal_kl_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,      \
+                               const T *bt, const T *wt, int ndim, int64_t nz,            \
+                               int64_t ny, int64_t nx, double wx, double wy, double wz,   \
+                               double tau, double tl, double theta, void *s) {            \
+    return tgv_primal_kl_impl<T>(p, q, x, xbar, w, wbar, bt, wt, ndim, nz, ny, nx, wx,    \
+                                 wy, wz, tau, tl, theta, s);                              \
   }                                                                                       \
   int nsol_tgv_primal_lin_##SUF(const T *p, const T *q, T *x, T *xbar, T *w, T *wbar,     \
                                 const T *g, int ndim, int64_t nz, int64_t ny, int64_t nx, \

@@ -17,6 +17,7 @@ P members of one shape advance together in a host-driven loop of, per iteration,
     the blur over the stack          ConvolutionOperator._apply_stacked, or the one-pass
                                      blur's epilogue q <- sigma A xbar + q per member
     ops.pdl_stack_dual_data          every member's q, its own lambda = 1 / alpha
+                                     (data_loss="kl": ops.pdl_stack_dual_data_kl)
     the adjoint blur over the stack
     ops.pdl_stack_iter               the regulariser's dual update and the primal step
 
@@ -70,12 +71,22 @@ def operator_key(op):
     return (int(op.dimension), op.mode, tuple(op.kernel.shape), op.kernel.tobytes())
 
 
+def data_term_key(solver):
+    """The data term's entry of a member key: data_loss itself, and for the KL term the
+    pair of it and the background as the kernel sees it (background / x_scale, one value
+    for the whole stack)."""
+    if solver._data_loss == "kl":
+        return ("kl", float(solver._scaled_background()))
+    return solver._data_loss
+
+
 def member_key(solver):
     """What the members of one stack share, or None for a solver that runs on its own:
     the operators (by value) and the shapes they are applied to, the volume's shape,
-    spacing, dimension, reg_type, huber_gamma, isotropic, data_loss, bounds, tau,
-    sigma, dtype, iteration count, a device-mode observer's points, whether the data
-    term is weighted, and the devices of b, x0 and the weights."""
+    spacing, dimension, reg_type, huber_gamma, isotropic, the data term (data_term_key:
+    data_loss, with the KL term's scaled background), bounds, tau, sigma, dtype, iteration
+    count, a device-mode observer's points, whether the data term is weighted, and the
+    devices of b, x0 and the weights."""
     if not isinstance(solver, PrimalDualLinearSolver):
         return None
     op, op_adj = solver._op, solver._op_adj
@@ -95,7 +106,8 @@ def member_key(solver):
             tuple(solver._op_adj_shape), tuple(solver._shape),
             tuple(float(v) for v in solver._spacing), int(solver._dimension),
             solver._reg_type, float(solver._huber_gamma), bool(solver._isotropic),
-            solver._data_loss, tuple(float(v) for v in solver._bounds),
+            data_term_key(solver),
+            tuple(float(v) for v in solver._bounds),
             float(solver._tau), float(solver._sigma)) + own[:3] + \
         (w is not None, ("b", device_index(b)), own[3], ("weights", device_index(w)))
 
@@ -136,20 +148,29 @@ class StackedDataSide(object):
         self._slots = torch.empty(group, dtype=torch.float64, device=like.device) \
             if self._epilogue else None
 
-    def dual_step(self, xbar, q, bt, wt, sigma, lm, g, l1, out):
-        """q (g members) in place, then out <- A^T q.  False when the library declined
-        the update of q: the adjoint has not run then."""
+    def dual_step(self, xbar, q, bt, wt, sigma, lm, g, data_loss, background, out):
+        """q (g members) in place, then out <- A^T q; background: the scaled one of the
+        KL data term.  False when the library declined the update of q: the adjoint has
+        not run then."""
         n = q.numel() // g
+        if data_loss == "kl":
+            def update(t):
+                return ops.pdl_stack_dual_data_kl(q, t, bt, wt, sigma, lm, g, background)
+        else:
+            l1 = data_loss == "ell1"
+
+            def update(t):
+                return ops.pdl_stack_dual_data(q, t, bt, wt, sigma, lm, g, l1)
         if self._epilogue and self._op.apply_axpby_stacked(
                 xbar, q, self._op_shape, g, sigma, 1., results=self._slots[:g]) is None:
             self._epilogue = False     # the kernel declined: nothing ran, q is intact
         if self._epilogue:
-            ok = ops.pdl_stack_dual_data(q, None, bt, wt, sigma, lm, g, l1)
+            ok = update(None)
         else:
             if self._t_all is None:
                 self._t_all = self._like.new_empty(self._size)
             t = self._op._apply_stacked(xbar, self._op_shape, g, out=self._t_all[:g * n])
-            ok = ops.pdl_stack_dual_data(q, t, bt, wt, sigma, lm, g, l1)
+            ok = update(t)
         if ok:
             self._adj._apply_stacked(q, self._adj_shape, g, out=out)
         return ok
@@ -178,7 +199,7 @@ def run_linear_stack(x_all, bt, wt, strided, template, lmbda, group, points,
     shape, w, flags = s._shape, ops.inv_spacing(s._spacing, dim), s._flags()
     tau, sigma, theta = s._tau, s._sigma, s._theta
     hden = 1. + sigma * s._huber_gamma if s._reg_type == "huber" else 1.
-    l1 = s._data_loss == "ell1"
+    data_loss, bg = s._data_loss, s._scaled_background()
     lo, hi = s._bounds
     lm_all = ops.pdl_lambdas(lmbda, x_all)
     points = set(points or ())
@@ -195,7 +216,8 @@ def run_linear_stack(x_all, bt, wt, strided, template, lmbda, group, points,
         lm = lm_all[a:b]
         for i in range(iters):
             k = i & 1
-            if not (data.dual_step(xb[k], q, bt_g, wt_g, sigma, lm, g, l1, gq) and
+            if not (data.dual_step(xb[k], q, bt_g, wt_g, sigma, lm, g, data_loss, bg,
+                                   gq) and
                     ops.pdl_stack_iter(xb[k], xb[1 - k], x, gq, pp[k], pp[1 - k], g,
                                        shape, w, sigma, hden, tau, theta, lo, hi, flags,
                                        has_p=i > 0)):

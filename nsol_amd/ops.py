@@ -611,6 +611,21 @@ def prox_ell1_weighted(x, bt, wt, tau, out=None):
     return _wrote(out)
 
 
+def prox_kl(x, bt, wt, tau, out=None):
+    """The prox of the Poisson (Kullback-Leibler) term t (x - bt log x) with t = tau * wt
+    per element (wt None: all 1), csrc/nsol_kl.hpp: never negative; x where wt == 0."""
+    _same(x, bt)
+    if wt is not None:
+        _same(x, wt)
+    if out is None:
+        out = empty_like(x)
+    else:
+        _same(x, out)
+    _lib.check(_fn("prox_kl", x)(_p(out), _p(x), _p(bt), _p(wt), float(tau), x.numel(),
+                                 stream_ptr()), "nsol_prox_kl")
+    return _wrote(out)
+
+
 # ------------------------------------------------------------ reductions ----
 _ws = {}
 
@@ -1818,6 +1833,22 @@ def pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1=False):
     return _wrote(q)
 
 
+def pdl_dual_data_kl(q, t, bt, wt, sigma, lmbda, background=0.):
+    """pdl_dual_data for the Poisson (Kullback-Leibler) data term with a constant
+    background >= 0: v = q + sigma * (t + background), or, t None, q + sigma * background;
+    then kl_dual_prox of csrc/nsol_kl.hpp with c = lmbda * wt (never above c), and exactly
+    0 where wt is 0.  Does not synchronise."""
+    _same(q, bt)
+    if t is not None:
+        _same(q, t)
+    if wt is not None:
+        _same(q, wt)
+    _lib.check(_fn("pdl_dual_data_kl", q)(
+        _p(q), _p(t), _p(bt), _p(wt), float(sigma), float(lmbda), float(background),
+        q.numel(), stream_ptr()), "nsol_pdl_dual_data_kl")
+    return _wrote(q)
+
+
 def pdl_iter(xbar_in, xbar_out, x, g, p_in, p_out, shape, w, sigma, hden, tau, theta,
              lo, hi, flags, has_p=True):
     """One iteration's regulariser side and explicit primal step in one pass:
@@ -1914,6 +1945,25 @@ def tgv_primal_w(p, q, x, xbar, w_field, wbar, bt, wt, shape, w, tau, tl, theta=
     if rc == -2:
         return False
     _lib.check(rc, "nsol_tgv_primal_w")
+    _wrote(x, xbar, w_field, wbar)
+    return True
+
+
+def tgv_primal_kl(p, q, x, xbar, w_field, wbar, bt, wt, shape, w, tau, tl, theta=1.):
+    """tgv_primal with the Poisson (Kullback-Leibler) data term: x <- prox_kl(x - tau
+    grad^T p, bt, wt, tl) of csrc/nsol_kl.hpp, wt None: all weights 1; w_field and the
+    bars as in tgv_primal.  Returns False when the library declined the geometry (nothing
+    was launched).  Does not synchronise."""
+    _same(x, xbar, bt)
+    if wt is not None:
+        _same(x, wt)
+    ndim, nz, ny, nx = _tgv_operands(shape, x, (p, w_field, wbar), (q,))
+    rc = _fn("tgv_primal_kl", x)(
+        _p(p), _p(q), _p(x), _p(xbar), _p(w_field), _p(wbar), _p(bt), _p(wt), ndim, nz, ny,
+        nx, w[0], w[1], w[2], float(tau), float(tl), float(theta), stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_tgv_primal_kl")
     _wrote(x, xbar, w_field, wbar)
     return True
 
@@ -2147,6 +2197,35 @@ def pdl_stack_dual_data(q, t, bt, wt, sigma, lmbda, members, l1=False):
     pdl_lambdas' device array.  Every member's q has the bits pdl_dual_data gives it
     alone.  Returns False when the library declined (nothing was launched).  Does not
     synchronise."""
+    members, n, bts, wts = _pdl_stack_operands(q, t, bt, wt, lmbda, members)
+    rc = _fn("pdl_stack_dual_data", q)(
+        _p(q), _p(t), _p(bt), bts, _p(wt), wts, float(sigma), _p(lmbda), int(bool(l1)),
+        members, n, stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pdl_stack_dual_data")
+    _wrote(q)
+    return True
+
+
+def pdl_stack_dual_data_kl(q, t, bt, wt, sigma, lmbda, members, background=0.):
+    """pdl_dual_data_kl on `members` stacked runs in one launch, operands as
+    pdl_stack_dual_data's; the background is common to the stack.  Every member's q has
+    the bits pdl_dual_data_kl gives it alone.  Returns False when the library declined
+    (nothing was launched).  Does not synchronise."""
+    members, n, bts, wts = _pdl_stack_operands(q, t, bt, wt, lmbda, members)
+    rc = _fn("pdl_stack_dual_data_kl", q)(
+        _p(q), _p(t), _p(bt), bts, _p(wt), wts, float(sigma), _p(lmbda),
+        float(background), members, n, stream_ptr())
+    if rc == -2:
+        return False
+    _lib.check(rc, "nsol_pdl_stack_dual_data_kl")
+    _wrote(q)
+    return True
+
+
+def _pdl_stack_operands(q, t, bt, wt, lmbda, members):
+    """(members, n, bt's member stride, wt's) of a stacked update of q, checked."""
     members = int(members)
     _chk(q)
     _chk(bt)
@@ -2168,14 +2247,7 @@ def pdl_stack_dual_data(q, t, bt, wt, sigma, lmbda, members, l1=False):
                              "-" if wt is None else wt.numel(), lmbda.numel()))
     bts = 0 if bt.numel() == n else n
     wts = 0 if wt is None or wt.numel() == n else n
-    rc = _fn("pdl_stack_dual_data", q)(
-        _p(q), _p(t), _p(bt), bts, _p(wt), wts, float(sigma), _p(lmbda), int(bool(l1)),
-        members, n, stream_ptr())
-    if rc == -2:
-        return False
-    _lib.check(rc, "nsol_pdl_stack_dual_data")
-    _wrote(q)
-    return True
+    return members, n, bts, wts
 
 
 def pdl_stack_iter(xbar_in, xbar_out, x, g, p_in, p_out, members, shape, w, sigma, hden,

@@ -5,7 +5,10 @@ MI355X -- deconvolution without inner solves:
 
 in the scaled variable x / x_scale (b~ = b / x_scale; the box is the scaled
 variable's, as TikhonovLinearSolver's bounds are), with
-  D_w   1/2 sum w_i (.)^2 (data_loss="ell2") or sum w_i |.| ("ell1"), per-voxel
+  D_w   1/2 sum w_i (.)^2 (data_loss="ell2"), sum w_i |.| ("ell1") or the Poisson
+        (Kullback-Leibler) term sum w_i ((u_i + g) - b~_i log(u_i + g)) of u = A x
+        ("kl": photon counts b >= 0; g = background / x_scale >= 0 a known constant such
+        as a dark current, which keeps the log finite where A x reaches 0), per-voxel
         weights w_i >= 0 (a mask, a confidence map; None: all 1),
   R     TV or Huber(gamma), anisotropic or isotropic,
   grad  the zero-padded forward difference of GradientOperator.
@@ -19,11 +22,16 @@ indicator, so the accelerated schedules do not apply) is
     p <- prox_{sigma R*}(p + sigma grad xbar)
     v  = q + sigma (A xbar - b~)
     q <- l2: v c / (c + sigma), c = lambda w;   l1: clamp(v, -c, c);   w = 0: 0
+         kl: v = q + sigma (A xbar + g), d = v - c, s = sqrt(d^2 + 4 sigma c b~),
+             q <- d > 0 ? c - 2 sigma c b~ / (d + s) : c + (d - s) / 2   (csrc/nsol_kl.hpp)
     x+ = clip(x - tau (grad^T p + A^T q), lo, hi);  xbar <- x+ + theta (x+ - x);  x <- x+
 
 one application of A, one of A^T, one element-wise kernel (ops.pdl_dual_data) and one
 pass of the fused primal-dual tile (ops.pdl_iter, nsol_pdl.hip).  Weights, masks, the
-l1 data term and the box cost nothing extra.  A list of such solvers on volumes of one
+l1 data term and the box cost nothing extra; the KL term costs one square root and one
+division per value.  Like TV, the KL term is 1-homogeneous, so the minimiser of TV-KL does
+not depend on x_scale in exact arithmetic (a finite run does: the steps act on the scaled
+variable).  A list of such solvers on volumes of one
 shape, or one observation under several alphas, runs in stacked launches through
 PrimalDualLinearBatch / PrimalDualLinearSweep (nsol_amd/linear_stack.py, nsol_pdls.hip).
 
@@ -58,7 +66,7 @@ from .symbolic import trace_operator
 from ._accessors import add_accessors
 
 REG_TYPES = ("TV", "huber")
-DATA_LOSSES = ("ell2", "ell1")
+DATA_LOSSES = ("ell2", "ell1", "kl")
 
 
 def step_sizes(L2, tau=None, sigma=None):
@@ -82,6 +90,46 @@ def step_sizes(L2, tau=None, sigma=None):
         raise ValueError("tau * sigma * L2 = %g > 1: the iteration need not converge" %
                          (tau * sigma * L2))
     return tau, sigma
+
+
+def checked_background(background, data_loss):
+    """`background` as a float: finite, >= 0, and 0 unless data_loss is "kl"."""
+    try:
+        background = float(background)
+    except (TypeError, ValueError):
+        raise ValueError("background must be a number")
+    if not (np.isfinite(background) and background >= 0):
+        raise ValueError("background must be a finite number >= 0")
+    if background != 0 and data_loss != "kl":
+        raise ValueError("background belongs to data_loss=\"kl\", not to %r" %
+                         (data_loss,))
+    return background
+
+
+def check_counts(b, weights):
+    """ValueError unless the observation `b` is >= 0 wherever its weight is positive
+    (weights None: everywhere), NaN counting as negative: what the Poisson (KL) data term
+    needs.  One reduction when a solver is set up, on the host for NumPy arrays and on the
+    device (one read-back) for device tensors; what sits under weight 0 is not looked at."""
+    if is_device_tensor(b) or is_device_tensor(weights):
+        import torch
+        if not is_device_tensor(b):
+            b = torch.as_tensor(np.asarray(b), device=weights.device)
+        bad = ~(b.reshape(-1) >= 0)
+        if weights is not None:
+            if not is_device_tensor(weights):
+                weights = torch.as_tensor(np.asarray(weights), device=b.device)
+            bad = bad & (weights.reshape(-1) > 0)
+        found = bool(torch.any(bad))
+    else:
+        with np.errstate(invalid="ignore"):
+            bad = ~(np.asarray(b).reshape(-1) >= 0)
+            if weights is not None:
+                bad = bad & (np.asarray(weights).reshape(-1) > 0)
+        found = bool(np.any(bad))
+    if found:
+        raise ValueError("data_loss=\"kl\" needs observations >= 0 wherever the weight is "
+                         "positive (negative or NaN values found)")
 
 
 def checked_bounds(bounds):
@@ -136,20 +184,28 @@ class _DataSide:
         self._slot = torch.empty(1, dtype=torch.float64, device=x.device) \
             if self._epilogue else None
 
-    def dual_step(self, xbar, q, bt, wt, sigma, lmbda, l1):
-        """q in place; returns g = A^T q (n values)."""
+    def dual_step(self, xbar, q, bt, wt, sigma, lmbda, data_loss, background=0.):
+        """q in place; returns g = A^T q (n values).  background: the scaled one."""
         s = self._solver
+        if data_loss == "kl":
+            def update(t):
+                ops.pdl_dual_data_kl(q, t, bt, wt, sigma, lmbda, background)
+        else:
+            l1 = data_loss == "ell1"
+
+            def update(t):
+                ops.pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1)
         if self._epilogue and s._op.apply_axpby(xbar, q, s._op_shape, sigma, 1.,
                                                 result=self._slot) is None:
             self._epilogue = False     # the kernel declined: nothing ran, q is intact
         if self._epilogue:
-            ops.pdl_dual_data(q, None, bt, wt, sigma, lmbda, l1)
+            update(None)
         else:
             t = self._A(xbar)
             if t.numel() != s._m:
                 raise ValueError("A returned %d values, b holds %d" %
                                  (t.numel(), s._m))
-            ops.pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1)
+            update(t)
         g = self._At(q)
         if g.numel() != s._n:
             raise ValueError("A_adj returned %d values, x holds %d" % (g.numel(), s._n))
@@ -173,10 +229,12 @@ class _LinearDataTermSolver(Stopping, Solver):
     def __init__(self, A, A_adj, b, x0, dimension, spacing=None, alpha=0.01,
                  iterations=10, isotropic=False, data_loss="ell2", weights=None,
                  bounds=None, A_norm2=None, L2=None, tau=None, sigma=None, x_scale=1.,
-                 verbose=0, dtype=None, tolerance=None, check_every=10, shape=None):
+                 verbose=0, dtype=None, tolerance=None, check_every=10, shape=None,
+                 background=0.):
         Solver.__init__(self, x0=x0, verbose=verbose, x_scale=x_scale, dtype=dtype)
         if data_loss not in DATA_LOSSES:
             raise ValueError("data_loss must be one of %r" % (DATA_LOSSES,))
+        self._background = checked_background(background, data_loss)
         dimension = int(dimension)
         if dimension not in (1, 2, 3):
             raise ValueError("dimension must be 1, 2 or 3")
@@ -209,6 +267,8 @@ class _LinearDataTermSolver(Stopping, Solver):
         self._weights = weights
         if weights is not None:
             check_weights(weights, m)
+        if data_loss == "kl":
+            check_counts(b, weights)
 
         if A_norm2 is None:
             if not isinstance(self._op, (ConvolutionOperator,
@@ -261,6 +321,19 @@ class _LinearDataTermSolver(Stopping, Solver):
                              (shape, n, d))
         return shape
 
+    def _scaled_background(self):
+        """g = background / x_scale, the constant the kernels add to A xbar."""
+        return self._background / float(self._x_scale)
+
+    def _device_data(self, x):
+        """(bt, wt): the scaled observation and the weights (or None) on x's device, checked
+        (m values)."""
+        bt = scaled_data_on_device(self._b, self._x_scale, x)
+        if bt.numel() != self._m:
+            raise ValueError("b holds %d values, not %d" % (bt.numel(), self._m))
+        wt = None if self._weights is None else weights_on_device(self._weights, x)
+        return bt, wt
+
     # ------------------------------------------------------------------
     def get_execution(self):
         """'fused' (known from construction), 'device' or 'host' after run()."""
@@ -276,7 +349,7 @@ class PrimalDualLinearSolver(_LinearDataTermSolver):
                  iterations=10, reg_type="TV", huber_gamma=0.05, isotropic=False,
                  data_loss="ell2", weights=None, bounds=None, A_norm2=None, L2=None,
                  tau=None, sigma=None, x_scale=1., verbose=0, dtype=None,
-                 tolerance=None, check_every=10, shape=None):
+                 tolerance=None, check_every=10, shape=None, background=0.):
         if reg_type not in REG_TYPES:
             raise ValueError("reg_type must be one of %r" % (REG_TYPES,))
         self._reg_type, self._huber_gamma = reg_type, float(huber_gamma)
@@ -285,7 +358,7 @@ class PrimalDualLinearSolver(_LinearDataTermSolver):
             iterations=iterations, isotropic=isotropic, data_loss=data_loss,
             weights=weights, bounds=bounds, A_norm2=A_norm2, L2=L2, tau=tau, sigma=sigma,
             x_scale=x_scale, verbose=verbose, dtype=dtype, tolerance=tolerance,
-            check_every=check_every, shape=shape)
+            check_every=check_every, shape=shape, background=background)
 
     def _default_L2(self):
         """|grad|^2 + |A|^2 bounds |(grad, A)|^2."""
@@ -310,10 +383,7 @@ class PrimalDualLinearSolver(_LinearDataTermSolver):
         p = [torch.empty(self._dimension * n, dtype=x.dtype, device=x.device)
              for _ in range(2)]
         q = torch.zeros(m, dtype=x.dtype, device=x.device)
-        bt = scaled_data_on_device(self._b, self._x_scale, x)
-        if bt.numel() != m:
-            raise ValueError("b holds %d values, not %d" % (bt.numel(), m))
-        wt = None if self._weights is None else weights_on_device(self._weights, x)
+        bt, wt = self._device_data(x)
         if rule is not None:
             rule.allocate(x)
 
@@ -324,7 +394,7 @@ class PrimalDualLinearSolver(_LinearDataTermSolver):
         tau, sigma, theta = self._tau, self._sigma, self._theta
         hden = 1. + sigma * self._huber_gamma if self._reg_type == "huber" else 1.
         lmbda = 1. / self._alpha
-        l1 = self._data_loss == "ell1"
+        data_loss, bg = self._data_loss, self._scaled_background()
         lo, hi = self._bounds
 
         for i in range(iters):
@@ -334,7 +404,7 @@ class PrimalDualLinearSolver(_LinearDataTermSolver):
             check = rule is not None and rule.is_point(i + 1)
             if check:
                 x_old, q_old = x.clone(), q.clone()
-            g = data.dual_step(xbar[k], q, bt, wt, sigma, lmbda, l1)
+            g = data.dual_step(xbar[k], q, bt, wt, sigma, lmbda, data_loss, bg)
             if not ops.pdl_iter(xbar[k], xbar[1 - k], x, g, p[k], p[1 - k], shape, w,
                                 sigma, hden, tau, theta, lo, hi, flags, has_p=i > 0):
                 raise ValueError("nsol_pdl_iter does not take a volume of shape %r" %
@@ -359,5 +429,5 @@ add_accessors(_LinearDataTermSolver, ["alpha", "iterations", "data_loss"])
 add_accessors(PrimalDualLinearSolver, ["huber_gamma", "reg_type"])
 add_accessors(_LinearDataTermSolver,
               ["A", "A_adj", "dimension", "spacing", "isotropic", "bounds", "A_norm2",
-               "L2", "tau", "sigma", "theta", "shape"],
+               "L2", "tau", "sigma", "theta", "shape", "background"],
               setters=False)

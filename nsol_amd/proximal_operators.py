@@ -259,6 +259,37 @@ class ProximalOperators(object):
                          "prox_ell2_w")
 
     @staticmethod
+    def prox_kl_denoising(x, tau, x0, x_scale=1.):
+        """prox of tau * lambda sum_i (x_i - b~_i log x_i), b~ = x0 / x_scale >= 0: the
+        Poisson (Kullback-Leibler) data term, the negative log-likelihood of photon
+        counts x0 up to a constant.  In closed form (csrc/nsol_kl.hpp): with e = x - tau,
+        s = sqrt(e^2 + 4 tau b~), (e + s) / 2 where e >= 0 and 2 tau b~ / (s - e) elsewhere;
+        never negative.  The fused kernels do not hold this prox: a PrimalDualSolver run
+        with it goes through the loop of separate kernels."""
+        return ProximalOperators.prox_kl_denoising_weighted(x, tau, x0, None, x_scale)
+
+    @staticmethod
+    def prox_kl_denoising_weighted(x, tau, x0, weights, x_scale=1.):
+        """prox_kl_denoising with per-voxel weights w_i >= 0 on the terms of the sum (see
+        prox_ell1_denoising_weighted; None: all 1).  Where w_i == 0 the result is x_i
+        exactly, whatever x0 holds there."""
+        if isinstance(x, Sym):
+            raise TraceAbort("prox_kl_denoising is not fused")
+        n = int(x0.numel() if is_device_tensor(x0) else np.size(x0))
+        size = int(x.numel() if is_device_tensor(x) else np.size(x))
+        if size != n:
+            raise ValueError("x holds %d values, x0 %d" % (size, n))
+        if weights is not None:
+            check = int(weights.numel() if is_device_tensor(weights)
+                        else np.size(weights))
+            if check != n:
+                raise ValueError("weights hold %d values for %d voxels" % (check, n))
+        return _elementwise(
+            x, lambda d: ops.prox_kl(
+                d, scaled_data_on_device(x0, x_scale, d),
+                None if weights is None else weights_on_device(weights, d), tau), None)
+
+    @staticmethod
     def prox_tv_conj(x, sigma):
         # proximal_operators.py:138-140
         return _elementwise(x, lambda d: ops.prox_dual_clamp(d, 1.0),

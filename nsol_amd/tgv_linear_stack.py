@@ -49,7 +49,8 @@ import numpy as np
 from . import ops, tgv_numpy
 from .device import device_index, is_device_tensor, to_numpy
 from .linear_operators import ConvolutionOperator
-from .linear_stack import StackedDataSide, expects_epilogue, operator_key
+from .linear_stack import (StackedDataSide, data_term_key, expects_epilogue,
+                           operator_key)
 from .parameter_sweep import PrimalDualSweep, member_parameters
 from .solver_batch import PrimalDualBatch, plan_stacks, solver_key
 from .stacked_run import Launches
@@ -62,7 +63,8 @@ SWEEP_KEYS = ("alpha", "beta")
 def member_key(solver):
     """What the members of one stack share, or None for a solver that runs on its own:
     the operators (by value) and the shapes they are applied to, the volume's shape,
-    spacing, dimension, isotropic, data_loss, bounds, tau, sigma, theta, dtype, iteration
+    spacing, dimension, isotropic, the data term (linear_stack.data_term_key: data_loss,
+    with the KL term's scaled background), bounds, tau, sigma, theta, dtype, iteration
     count, a device-mode observer's points, whether the data term is weighted, and the
     devices of b, x0 and the weights."""
     if not isinstance(solver, TGVPrimalDualLinearSolver):
@@ -83,7 +85,7 @@ def member_key(solver):
     return (operator_key(op), tuple(solver._op_shape), operator_key(op_adj),
             tuple(solver._op_adj_shape), tuple(solver._shape),
             tuple(float(v) for v in solver._spacing), int(solver._dimension),
-            bool(solver._isotropic), solver._data_loss,
+            bool(solver._isotropic), data_term_key(solver),
             tuple(float(v) for v in solver._bounds), float(solver._tau),
             float(solver._sigma), float(solver._theta)) + own[:3] + \
         (w is not None, ("b", device_index(b)), own[3], ("weights", device_index(w)))
@@ -124,7 +126,7 @@ def run_tgv_linear_stack(x_all, bt, wt, strided, template, alphas, betas, group,
     shape, iw = s._shape, ops.inv_spacing(s._spacing, d)
     tau, sigma, theta = s._tau, s._sigma, s._theta
     dflags = ops.PD_REG_ISOTROPIC if s._isotropic else 0
-    l1 = s._data_loss == "ell1"
+    data_loss, bg = s._data_loss, s._scaled_background()
     lo, hi = s._bounds
     # (tl is unused by the kLin step; the table checks it as it checks beta)
     beta_all, tl_all = member_table_values(tau, alphas, betas)
@@ -157,7 +159,8 @@ def run_tgv_linear_stack(x_all, bt, wt, strided, template, alphas, betas, group,
         r.zero_()
         for i in range(iters):
             if not (ops.tgv_stack_dual(xbar, wbar, p, q, g, shape, iw, sigma, tab, dflags)
-                    and data.dual_step(xbar, r, bt_m, wt_m, sigma, lm, g, l1, gq)
+                    and data.dual_step(xbar, r, bt_m, wt_m, sigma, lm, g, data_loss, bg,
+                                       gq)
                     and ops.tgv_stack_primal_lin(p, q, x, xbar, w, wbar, gq, g, shape, iw,
                                                  tau, theta, lo, hi)):
                 return launches.declined("tgv_stack_primal_lin")

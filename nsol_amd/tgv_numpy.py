@@ -14,7 +14,9 @@ In the solver's scaled units (b = observation / x_scale, lmbda = 1 / alpha):
 Component a = 0 is the x axis, the LAST array axis; spacing[a] belongs to it.  E w is
 symmetric and stored as M = d (d + 1) / 2 components, diagonals first: xx, yy, zz, xy,
 xz, yz in 3-D, xx, yy, xy in 2-D, xx in 1-D.  Off-diagonal components count twice in
-every norm and inner product.  D is 1/2 |.|^2 ("ell2") or |.|_1 ("ell1").
+every norm and inner product.  D is 1/2 |.|^2 ("ell2"), |.|_1 ("ell1") or the Poisson
+(Kullback-Leibler) term sum (x - b log x) ("kl": b >= 0, and behind a linear operator
+sum ((A x + background) - b log(A x + background))).
 
 Arrays: x `shape`, w and p (d,) + shape, q (M,) + shape.
 """
@@ -22,7 +24,7 @@ import numpy as np
 
 from . import vector_numpy
 
-DATA_LOSSES = ("ell2", "ell1")
+DATA_LOSSES = ("ell2", "ell1", "kl")
 
 
 def pairs(d):
@@ -128,9 +130,20 @@ def energy(x, w, b, lmbda, beta, spacing=None, data_loss="ell2", isotropic=False
     else:
         r1 = np.sum(np.abs(g))
         r2 = np.sum(wq * np.abs(e))
-    r = x - b
-    data = np.sum(np.abs(r)) if data_loss == "ell1" else 0.5 * np.sum(r * r)
+    if data_loss == "kl":
+        data = _kl(x, b, np.ones_like(x))
+    else:
+        r = x - b
+        data = np.sum(np.abs(r)) if data_loss == "ell1" else 0.5 * np.sum(r * r)
     return float(lmbda * data + r1 + beta * r2)
+
+
+def _kl(u, b, wt):
+    """sum wt (u - b log u) over the samples of positive weight, 0 log 0 = 0 (float64)."""
+    on = wt > 0
+    u, b, wt = u[on], b[on], wt[on]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.sum(wt * (u - np.where(b > 0, b * np.log(u), 0.))))
 
 
 def project_p(p, isotropic):
@@ -163,6 +176,8 @@ def prox_data(u, b, tl, data_loss):
     """prox of tl D(., b): (u + tl b) / (1 + tl), or b + max(|u - b| - tl, 0) sign."""
     dt = u.dtype.type
     tl = dt(tl)
+    if data_loss == "kl":      # vector_numpy.prox_kl, all weights 1
+        return vector_numpy.prox_kl_w(u, b, None, tl, u.dtype).astype(dt)
     if data_loss == "ell1":
         r = u - b
         return b + np.maximum(np.abs(r) - tl, dt(0)) * np.sign(r)
@@ -196,8 +211,11 @@ def primal_step_weighted(p, q, x, w, b, wt, tau, tl, theta=1., spacing=None,
     dt = x.dtype.type
     tau, theta = dt(tau), dt(theta)
     kx, kw = K_adj(p, q, spacing)
-    xn = vector_numpy.prox_data_w(x - tau * kx, b, wt, tl, data_loss == "ell1",
-                                  x.dtype).astype(dt)
+    if data_loss == "kl":
+        xn = vector_numpy.prox_kl_w(x - tau * kx, b, wt, tl, x.dtype).astype(dt)
+    else:
+        xn = vector_numpy.prox_data_w(x - tau * kx, b, wt, tl, data_loss == "ell1",
+                                      x.dtype).astype(dt)
     wn = w - tau * kw
     return xn, xn + theta * (xn - x), wn, wn + theta * (wn - w)
 
@@ -228,15 +246,18 @@ def norm_bound_linear(dimension, spacing=None, A_norm2=0.):
 
 
 def energy_linear(x, w, Ax, b, lmbda, beta, spacing=None, data_loss="ell2",
-                  isotropic=False, weights=None):
+                  isotropic=False, weights=None, background=0.):
     """lmbda D_wt(A x, b) + |grad x - w|_1 + beta |E w|_1 (float64); Ax is A applied to x.
-    Samples of weight 0 do not enter, whatever b holds there.  (The box is a constraint:
-    it is not part of the value.)"""
+    Samples of weight 0 do not enter, whatever b holds there.  background: the constant
+    of the "kl" term.  (The box is a constraint: it is not part of the value.)"""
     x, w = (np.asarray(t, dtype=np.float64) for t in (x, w))
     reg = energy(x, w, x, 1., beta, spacing, "ell2", isotropic)    # x - x: no data term
     r = np.asarray(Ax, dtype=np.float64).ravel() - np.asarray(b, dtype=np.float64).ravel()
     wt = np.ones_like(r) if weights is None else \
         np.asarray(weights, dtype=np.float64).ravel()
+    if data_loss == "kl":
+        u = np.asarray(Ax, dtype=np.float64).ravel() + float(background)
+        return float(lmbda * _kl(u, np.asarray(b, dtype=np.float64).ravel(), wt) + reg)
     r = np.where(wt == 0, 0., r)
     data = np.sum(wt * np.abs(r)) if data_loss == "ell1" else 0.5 * np.sum(wt * r * r)
     return float(lmbda * data + reg)
@@ -257,7 +278,7 @@ def _sq(*arrs):
 def iterate_linear(A, A_adj, b, x0, iterations, alpha, beta=2., spacing=None,
                    data_loss="ell2", isotropic=False, tau=None, sigma=None, theta=1.,
                    L2=None, dtype=None, keep=False, weights=None, bounds=None,
-                   A_norm2=None):
+                   A_norm2=None, background=0.):
     """`iterations` iterations of the TGV iteration whose data term sits behind a linear
     operator, lmbda D_wt(A x, b) + |grad x - w|_1 + beta |E w|_1 + indicator_[lo, hi](x),
     from x = xbar = x0, w = wbar = p = q = r = 0.  A and A_adj are callables on arrays: A
@@ -267,6 +288,7 @@ def iterate_linear(A, A_adj, b, x0, iterations, alpha, beta=2., spacing=None,
 
         (p, q) <- dual_step(xbar, wbar, p, q)
         r      <- vector_numpy.pdl_dual_data(r, A xbar, b, weights, sigma, lmbda, l1)
+                  ("kl": pdl_dual_data_kl with the constant `background` >= 0)
         (x, xbar, w, wbar) <- primal_step_lin(p, q, x, w, A_adj r, tau, theta, lo, hi)
 
     Returns what iterate returns plus r; the primal ratio runs over (x, w), the dual one
@@ -299,8 +321,12 @@ def iterate_linear(A, A_adj, b, x0, iterations, alpha, beta=2., spacing=None,
     for k in range(1, int(iterations) + 1):
         pn, qn = dual_step(xbar, wbar, p, q, sigma, beta, spacing, isotropic)
         t = np.asarray(A(xbar), dtype=dt).reshape(b.shape)
-        rn = vector_numpy.pdl_dual_data(r, t, b, wt, sigma, lmbda, data_loss == "ell1",
-                                        dt).astype(dt)
+        if data_loss == "kl":
+            rn = vector_numpy.pdl_dual_data_kl(r, t, b, wt, sigma, lmbda, background,
+                                               dt).astype(dt)
+        else:
+            rn = vector_numpy.pdl_dual_data(r, t, b, wt, sigma, lmbda,
+                                            data_loss == "ell1", dt).astype(dt)
         g = np.asarray(A_adj(rn), dtype=dt).reshape(x.shape)
         xn, xbar, wn, wbar = primal_step_lin(pn, qn, x, w, g, tau, theta, lo, hi, spacing,
                                              dt)

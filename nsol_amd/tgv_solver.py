@@ -7,8 +7,9 @@ in the scaled variable x / x_scale (b~ = b / x_scale).  x holds n values, w one 
 of `dimension` values per voxel; grad is the zero-padded forward difference of
 GradientOperator -- the one boundary convention of this package -- and E w the
 symmetrised gradient of w, (E w)_aa = D_a w_a, (E w)_ab = (D_a w_b + D_b w_a) / 2, its
-off-diagonals counted twice in every norm.  D is 1/2 |.|^2 (data_loss="ell2") or |.|_1
-("ell1"); the norms are sums over the components, or with isotropic=True the per-voxel
+off-diagonals counted twice in every norm.  D is 1/2 |.|^2 (data_loss="ell2"), |.|_1
+("ell1") or the Poisson (Kullback-Leibler) term sum (x - b~ log x) ("kl": counts b >= 0,
+the prox of csrc/nsol_kl.hpp through ops.tgv_primal_kl, weighted or not); the norms are sums over the components, or with isotropic=True the per-voxel
 Euclidean / Frobenius norms.  Where TV turns a smooth ramp into terraces, TGV keeps it:
 w follows the gradient of x and only ITS variation is penalised (beta).
 
@@ -36,7 +37,7 @@ import numpy as np
 from . import ops, tgv_numpy
 from .device import is_device_tensor, to_numpy
 from .primal_dual_linear_solver import (DATA_LOSSES, _DataSide, _LinearDataTermSolver,
-                                        _LinearStopRule, step_sizes)
+                                        _LinearStopRule, check_counts, step_sizes)
 from .proximal_operators import (check_weights, scaled_data_on_device,
                                  weights_on_device)
 from .solver import Solver
@@ -107,6 +108,8 @@ class TGVPrimalDualSolver(Stopping, Solver):
         self._weights = weights
         if weights is not None:
             check_weights(weights, n)
+        if data_loss == "kl":
+            check_counts(b, weights)
 
         if L2 is None:
             L2 = tgv_numpy.norm_bound(dimension, self._spacing)
@@ -161,6 +164,7 @@ class TGVPrimalDualSolver(Stopping, Solver):
         if bt.numel() != n:
             raise ValueError("b holds %d values, not %d" % (bt.numel(), n))
         wt = None if self._weights is None else weights_on_device(self._weights, x)
+        kl = self._data_loss == "kl"
         if rule is not None:
             rule.allocate(x)
 
@@ -178,7 +182,9 @@ class TGVPrimalDualSolver(Stopping, Solver):
             if check:
                 primal_old, dual_old = primal.clone(), dual.clone()
             if not (ops.tgv_dual(xbar, wbar, p, q, shape, iw, sigma, self._beta, dflags)
-                    and (ops.tgv_primal(p, q, x, xbar, w, wbar, bt, shape, iw, tau, tl,
+                    and (ops.tgv_primal_kl(p, q, x, xbar, w, wbar, bt, wt, shape, iw, tau,
+                                           tl, theta) if kl else
+                         ops.tgv_primal(p, q, x, xbar, w, wbar, bt, shape, iw, tau, tl,
                                         theta, pflags) if wt is None else
                          ops.tgv_primal_w(p, q, x, xbar, w, wbar, bt, wt, shape, iw, tau,
                                           tl, theta, pflags))):
@@ -218,7 +224,8 @@ class TGVPrimalDualLinearSolver(_LinearDataTermSolver):
     term; one iteration (constant steps, theta = 1) is
 
         (p, q) <- ops.tgv_dual(xbar, wbar, p, q)
-        r      <- ops.pdl_dual_data(r, A xbar, b~, wt, sigma, lambda)   (or the epilogue)
+        r      <- ops.pdl_dual_data(r, A xbar, b~, wt, sigma, lambda)   (or the epilogue;
+                   data_loss="kl": ops.pdl_dual_data_kl, with background=)
         g       = A^T r
         x+      = clip(x - tau (sum_a D_a^T p_a + g), lo, hi)           ops.tgv_primal_lin
         w+, xbar, wbar as in TGVPrimalDualSolver
@@ -234,7 +241,8 @@ class TGVPrimalDualLinearSolver(_LinearDataTermSolver):
     def __init__(self, A, A_adj, b, x0, dimension, spacing=None, alpha=0.01, beta=2.0,
                  iterations=10, data_loss="ell2", isotropic=False, weights=None,
                  bounds=None, A_norm2=None, L2=None, tau=None, sigma=None, x_scale=1.,
-                 verbose=0, dtype=None, tolerance=None, check_every=10, shape=None):
+                 verbose=0, dtype=None, tolerance=None, check_every=10, shape=None,
+                 background=0.):
         try:
             ok = int(dimension) == dimension and int(dimension) in (1, 2, 3)
         except (TypeError, ValueError):
@@ -251,7 +259,7 @@ class TGVPrimalDualLinearSolver(_LinearDataTermSolver):
             iterations=iterations, isotropic=isotropic, data_loss=data_loss,
             weights=weights, bounds=bounds, A_norm2=A_norm2, L2=L2, tau=tau, sigma=sigma,
             x_scale=x_scale, verbose=verbose, dtype=dtype, tolerance=tolerance,
-            check_every=check_every, shape=shape)
+            check_every=check_every, shape=shape, background=background)
         if not all(_positive(s) for s in self._spacing):
             raise ValueError("spacing must hold %d positive, finite values" %
                              self._dimension)
@@ -296,10 +304,7 @@ class TGVPrimalDualLinearSolver(_LinearDataTermSolver):
         xbar = x.clone()
         wbar = torch.zeros(d * n, dtype=x0.dtype, device=x0.device)
         r = torch.zeros(m, dtype=x0.dtype, device=x0.device)
-        bt = scaled_data_on_device(self._b, self._x_scale, x)
-        if bt.numel() != m:
-            raise ValueError("b holds %d values, not %d" % (bt.numel(), m))
-        wt = None if self._weights is None else weights_on_device(self._weights, x)
+        bt, wt = self._device_data(x)
         if rule is not None:
             rule.allocate(x)
         data = _DataSide(self, x)
@@ -307,7 +312,7 @@ class TGVPrimalDualLinearSolver(_LinearDataTermSolver):
         shape, iw = self._shape, ops.inv_spacing(self._spacing, d)
         tau, sigma, theta = self._tau, self._sigma, self._theta
         lmbda = 1. / self._alpha
-        l1 = self._data_loss == "ell1"
+        data_loss, bg = self._data_loss, self._scaled_background()
         lo, hi = self._bounds
         dflags = ops.PD_REG_ISOTROPIC if self._isotropic else 0
 
@@ -320,7 +325,7 @@ class TGVPrimalDualLinearSolver(_LinearDataTermSolver):
                 primal_old, dual_old, r_old = primal.clone(), dual.clone(), r.clone()
             ok = ops.tgv_dual(xbar, wbar, p, q, shape, iw, sigma, self._beta, dflags)
             if ok:
-                g = data.dual_step(xbar, r, bt, wt, sigma, lmbda, l1)
+                g = data.dual_step(xbar, r, bt, wt, sigma, lmbda, data_loss, bg)
                 ok = ops.tgv_primal_lin(p, q, x, xbar, w, wbar, g, shape, iw, tau, theta,
                                         lo, hi)
             if not ok:

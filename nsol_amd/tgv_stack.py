@@ -46,7 +46,8 @@ SWEEP_KEYS = ("alpha", "beta")
 
 
 def member_key(solver):
-    """What the members of one stack share, or None for a solver that runs on its own:
+    """What the members of one stack share, or None for a solver that runs on its own
+    (the Poisson data term "kl" among them: the stacked kernels hold ell2 and ell1 only):
     shape, spacing, dimension, data_loss, isotropic, tau, sigma, theta, dtype, iteration
     count, a device-mode observer's points, whether the data term is weighted, and the
     devices of b, x0 and the weights."""
@@ -57,6 +58,8 @@ def member_key(solver):
         return None             # (a tolerance, its own stopping iteration, among them)
     if solver._x0_ndim != 1:
         return None
+    if solver._data_loss == "kl":
+        return None             # no stacked form of k_tgv_primal_kl: its own run()
     b = solver._b
     if int(b.numel() if is_device_tensor(b) else np.size(b)) != solver._n:
         return None             # (run() says what is wrong with it)
@@ -91,6 +94,9 @@ def run_tgv_stack(x_all, bt, wt, strided, template, alphas, betas, group, points
     called.  A decline on any later launch raises RuntimeError."""
     import torch
     s = template
+    if s._data_loss not in ("ell2", "ell1"):
+        raise ValueError("the stacked TGV kernels do not hold data_loss=%r" %
+                         (s._data_loss,))
     P = len(alphas)
     n, d = x_all.numel() // P, s._dimension
     M = tgv_numpy.components(d)

@@ -412,3 +412,54 @@ def pdl_dual_data(q, t, bt, wt, sigma, lmbda, l1, dtype=np.float64):
     with np.errstate(invalid="ignore", over="ignore"):
         v = _f(q) + sg * (_f(t) - _f(bt)) if t is not None else _f(q) - sg * _f(bt)
     return pdl_dual_prox(v, lm * w, sg, w, l1)
+
+
+# ------------------------------ the Poisson (Kullback-Leibler) data term (csrc/nsol_kl.hpp)
+def kl_dual_prox(v, c, sigma, bt, w=None):
+    """kl_dual_prox of csrc/nsol_kl.hpp, the prox of sigma F* for F = c (u - bt log u) at
+    v: d = v - c, s = sqrt(d d + 4 ((sigma c) bt)), then c - (2 ((sigma c) bt)) / (d + s)
+    where d > 0 and c + 0.5 (d - s) elsewhere -- one number in two forms, each free of the
+    other's cancellation; never above c, and min(v, c) where bt == 0.  +0 where w == 0,
+    whatever bt holds there (w None: no such select).  Works in the arrays' own precision,
+    as prox_data_w does: float64 arrays give the reference."""
+    v, c, sigma, bt = np.asarray(v), np.asarray(c), np.asarray(sigma), np.asarray(bt)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        d = v - c
+        scb = (sigma * c) * bt
+        s = np.sqrt(d * d + 4. * scb)
+        r = np.where(d > 0, c - (2. * scb) / (d + s), c + 0.5 * (d - s))
+    return r if w is None else np.where(np.asarray(w) == 0, np.zeros_like(r), r)
+
+
+def prox_kl(u, bt, t, w=None):
+    """prox_kl of csrc/nsol_kl.hpp, the prox of t (x - bt log x) at u: e = u - t,
+    s = sqrt(e e + 4 (t bt)), then 0.5 (e + s) where e >= 0 and (2 (t bt)) / (s - e)
+    elsewhere; never negative, and max(u - t, 0) where bt == 0.  u ITSELF where w == 0,
+    whatever bt holds there (w None: no such select).  Works in the arrays' own
+    precision."""
+    u, bt, t = np.asarray(u), np.asarray(bt), np.asarray(t)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        e = u - t
+        tb = t * bt
+        s = np.sqrt(e * e + 4. * tb)
+        r = np.where(e >= 0, 0.5 * (e + s), (2. * tb) / (s - e))
+    return r if w is None else np.where(np.asarray(w) == 0, u, r)
+
+
+def prox_kl_w(u, bt, wt, tl, dtype=np.float64):
+    """k_prox_kl and the KL form of k_tgv_primal: t = tl * w (w = 1 with wt None), then
+    prox_kl with the select on w."""
+    u = np.asarray(u)
+    w = np.ones_like(u) if wt is None else np.asarray(wt)
+    return prox_kl(u, bt, as_scalar(tl, dtype) * w, w)
+
+
+def pdl_dual_data_kl(q, t, bt, wt, sigma, lmbda, background=0., dtype=np.float64):
+    """k_pdl_dual_data_kl of csrc/nsol_pdl.hip: v = q + sigma * (t + background), or
+    q + sigma * background with t None; c = lmbda * w (w = 1 with wt None); kl_dual_prox
+    with the select on w."""
+    sg, lm, bg = (as_scalar(s, dtype) for s in (sigma, lmbda, background))
+    w = np.ones_like(_f(q)) if wt is None else _f(wt)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = _f(q) + sg * (_f(t) + bg) if t is not None else _f(q) + sg * bg
+    return kl_dual_prox(v, lm * w, sg, _f(bt), w)
