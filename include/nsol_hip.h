@@ -203,7 +203,7 @@ int nsol_corr3_wrap_f64(const double *x, double *out, int64_t nz, int64_t ny,
  * scratch of ws_doubles doubles (one per tile; nsol_hip_reduce_ws_doubles()
  * suffices up to 2048^3).  Returns -2 (nothing launched) where the LDS-DMA staged
  * kernel does not apply: asymmetric taps, even / > 17 taps, ragged rows shorter
- * than the bound above, 17 taps in double (no LDS left for the io tiles). */
+ * than the bound above, 15 / 17 taps in double (no LDS left for the io tiles). */
 int nsol_corr3_wrap_axpby_f32(const float *x, float *io, int64_t nz, int64_t ny,
                               int64_t nx, const double *taps_z, const double *taps_y,
                               const double *taps_x, int ntaps, double ca, double cb,
