@@ -338,6 +338,30 @@ int nsol_corr_dense_f32(const float *x, float *out, int64_t nz, int64_t ny,
 int nsol_corr_dense_f64(const double *x, double *out, int64_t nz, int64_t ny,
                         int64_t nx, const double *taps, int kz, int ky, int kx,
                         int cz, int cy, int cx, int mode, void *stream);
+/* The same correlation, tiled (k_corr_dense_tile, nsol_convd.hip): a workgroup owns
+ * ty x tx outputs of a plane and marches over `slab` output planes with a ring of kz
+ * input planes in the LDS.  The result is BIT-IDENTICAL to nsol_corr_dense_* for finite
+ * inputs and taps (the same accumulation order, separate multiply and add).
+ * ty = tx = slab = 0: the planner's choice (nsol_convd_plan.hpp); a value > 0 forces
+ * that one (tx a multiple of 4).  All five modes, any extents, any alignment.
+ * Returns 0; -2, nothing launched or written, when the tiled form declines (more than
+ * 129 taps on an axis, a ring that does not fit the LDS, or -- with nothing forced -- so
+ * few taps that the plain kernel is the faster one); NSOL_EINVAL for a missing pointer,
+ * x and out overlapping, an extent or tap count < 1, a centre outside the kernel, a mode
+ * outside 0..4 and a forced tile the kernel cannot run.
+ * nsol_corr_dense_tiled_plan: the plan for a shape without launching, elem_size 4 or 8;
+ * plan[0..7] = ty, tx, slab, LDS bytes, tiles along x, tiles along y, slabs,
+ * workgroups.  Same returns (no pointers but plan). */
+int nsol_corr_dense_tiled_f32(const float *x, float *out, int64_t nz, int64_t ny,
+                              int64_t nx, const float *taps, int kz, int ky, int kx,
+                              int cz, int cy, int cx, int mode, int ty, int tx, int slab,
+                              void *stream);
+int nsol_corr_dense_tiled_f64(const double *x, double *out, int64_t nz, int64_t ny,
+                              int64_t nx, const double *taps, int kz, int ky, int kx,
+                              int cz, int cy, int cx, int mode, int ty, int tx, int slab,
+                              void *stream);
+int nsol_corr_dense_tiled_plan(int64_t nz, int64_t ny, int64_t nx, int kz, int ky, int kx,
+                               int elem_size, int ty, int tx, int slab, int64_t *plan);
 
 /* ---------------------------------------------------------------------- *
  * Element-wise building blocks (n = number of elements; out may alias inputs)

@@ -53,6 +53,15 @@ and --slice-wise: the stacked TGV forms (nsol_amd/tgv_linear_stack.py) are reach
 through the API only.  --L2 is not used, as for the other PDL types: the steps come from
 tgv_numpy.norm_bound_linear.
 
+--solver PDL --psf FILE: the blur is the point spread function in FILE (.npy, .nii,
+.png, .mat through DataReader) instead of the Gaussian of --blur, which is then ignored.
+The taps are taken as they are (no normalisation, no flip: A x is
+scipy.ndimage.convolve(x, psf, mode="wrap")), the PSF has as many axes as the
+observation, and the adjoint is the exact transpose (ConvolutionOperator.transpose), so
+a motion blur or a measured, asymmetric PSF is deconvolved with the right A^T.  A PSF
+that is no outer product runs through the tiled dense-tap kernel.  Not with --upsample
+or --slice-wise; --solver PD / ADMM do not take it (their inner solves use A for A^T).
+
 With --reference, the measures are evaluated through an Observer on the flat
 iterates against the flat reference (as run_denoising does and as the
 reference's tool does) and printed as first -> last value.
@@ -88,10 +97,11 @@ def _regulariser(reconstruction_type):
 def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.01,
                iterations=10, verbose=0, dtype=None, tolerance=None, check_every=10,
                weights=None, pdl_data_loss="ell2", nonnegative=False, isotropic=False,
-               background=0.):
+               background=0., psf=None):
     """The keyword arguments PrimalDualLinearSolver (tv_solver="PDL") and
     PrimalDualLinearSweep are built from.  background (in the observation's units) goes
-    with pdl_data_loss="kl"."""
+    with pdl_data_loss="kl".  psf: an array of taps with the observation's number of
+    axes in the place of the Gaussian of `blur`, with its exact transpose as A_adj."""
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -102,7 +112,11 @@ def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.
     x_scale = np.max(observed_nda)
     lo = getattr(LinearOperators, "LinearOperators%dD" % dimension)(
         spacing=spacing)
-    A, A_adj = lo.get_gaussian_blurring_operators(cov)
+    if psf is None:
+        A, A_adj = lo.get_gaussian_blurring_operators(cov)
+    else:
+        A, A_adj = lo.get_convolution_and_adjoint_convolution_operators(
+            checked_psf(psf, dimension), exact_adjoint=True)
     X = observed_nda.shape
     A_1D = lambda x: A(x.reshape(*X)).flatten()
     A_adj_1D = lambda x: A_adj(x.reshape(*X)).flatten()
@@ -125,6 +139,16 @@ def pdl_wiring(observed_nda, spacing, blur, reconstruction_type="TVL2", alpha=0.
         bounds=(0., np.inf) if nonnegative else None, x_scale=x_scale,
         verbose=verbose, dtype=dtype, tolerance=tolerance, check_every=check_every,
         **_background(background))
+
+
+def checked_psf(psf, dimension):
+    """The PSF as a float64 array of `dimension` axes with finite taps, or ValueError."""
+    psf = np.asarray(psf, dtype=np.float64)
+    if psf.ndim != dimension:
+        raise ValueError("the PSF has %d axes, the observation %d" % (psf.ndim, dimension))
+    if psf.size < 1 or not np.all(np.isfinite(psf)):
+        raise ValueError("the PSF must hold finite taps")
+    return psf
 
 
 def _background(background):
@@ -196,13 +220,18 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
                  data_loss_scale=1., L2=8, verbose=0, dtype=None,
                  tolerance=None, check_every=10, weights=None, pdl_data_loss="ell2",
                  nonnegative=False, upsample=None, sample_offset=None, beta=2.0,
-                 background=0., isotropic=False):
-    """weights, pdl_data_loss ("ell2" | "ell1" | "kl", the last with background, a
+                 background=0., psf=None, isotropic=False):
+    """psf (tv_solver="PDL" without upsample): taps in the place of the Gaussian of blur,
+    with the exact transpose as the adjoint (pdl_wiring).
+
+    weights, pdl_data_loss ("ell2" | "ell1" | "kl", the last with background, a
     constant in the observation's units) and nonnegative belong to
     tv_solver="PDL" (PrimalDualLinearSolver), and so do upsample / sample_offset (one
     integer per array axis: the observation is the coarse data, sampled_pdl_wiring).
     reconstruction_type "TGVL2" with tv_solver "PDL" is TGVPrimalDualLinearSolver on the
     same wiring, with beta in the place of the regulariser's type."""
+    if psf is not None and (tv_solver != "PDL" or upsample is not None):
+        raise ValueError("psf belongs to tv_solver='PDL' without upsample")
     if reconstruction_type == "TGVL2":
         if tv_solver != "PDL":
             raise ValueError("reconstruction_type 'TGVL2' belongs to tv_solver='PDL'")
@@ -216,7 +245,7 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
             kw = pdl_wiring(
                 observed_nda, spacing, blur, "TGVL2", alpha, iterations, verbose, dtype,
                 tolerance, check_every, weights, pdl_data_loss, nonnegative, isotropic,
-                background)
+                background, psf)
         return TGVPrimalDualLinearSolver(beta=beta, **kw)
     if upsample is not None:
         if not (reconstruction_type in ("TVL2", "HuberL2") and tv_solver == "PDL"):
@@ -229,7 +258,7 @@ def build_solver(observed_nda, spacing, blur, reconstruction_type="TVL2",
         return pdl.PrimalDualLinearSolver(**pdl_wiring(
             observed_nda, spacing, blur, reconstruction_type, alpha, iterations,
             verbose, dtype, tolerance, check_every, weights, pdl_data_loss,
-            nonnegative, isotropic, background))
+            nonnegative, isotropic, background, psf))
     dimension = observed_nda.ndim
     sigma = np.atleast_1d(blur).astype(float)
     cov = np.diag(np.ones(dimension)) * sigma ** 2
@@ -302,12 +331,12 @@ def _pdl_data_loss(args):
     return args.data_loss if args.data_loss in ("ell1", "kl") else "ell2"
 
 
-def run_sweep(args, observed_nda, spacing, x_ref, info, weights=None):
+def run_sweep(args, observed_nda, spacing, x_ref, info, weights=None, psf=None):
     """--solver PDL --result-dir: the --alpha values as one PrimalDualLinearSweep."""
     from ..linear_stack import PrimalDualLinearSweep
     kw = pdl_wiring(observed_nda, spacing, args.blur, args.reconstruction_type,
                     iterations=args.iterations, verbose=args.verbose, weights=weights,
-                    **_pdl_arguments(args))
+                    psf=psf, **_pdl_arguments(args))
     del kw["alpha"]
     sweep = PrimalDualLinearSweep(parameters={"alpha": list(args.alpha)}, **kw)
     if x_ref is not None:
@@ -396,7 +425,15 @@ def build_parser():
     ap.add_argument("--measures", nargs="+",
                     default=["PSNR", "RMSE", "SSIM", "NCC", "NMI"],
                     choices=sorted(SimilarityMeasures.similarity_measures))
-    ap.add_argument("--blur", type=float, default=1.2)
+    ap.add_argument("--blur", type=float, default=1.2,
+                    help="standard deviation of the Gaussian blur; ignored when --psf "
+                         "is given")
+    ap.add_argument("--psf", default=None, metavar="FILE",
+                    help="--solver PDL: the point spread function (.npy, .nii, .png, "
+                         ".mat) in the place of the Gaussian of --blur, which is then "
+                         "ignored; taps as they are, as many axes as the observation, "
+                         "the adjoint is the exact transpose; not with --upsample or "
+                         "--slice-wise")
     ap.add_argument("--reconstruction-type", default="TVL2",
                     choices=["TK0L2", "TK1L2", "TVL2", "HuberL2", "TGVL2"])
     ap.add_argument("--beta", type=float, default=None, metavar="B",
@@ -530,6 +567,18 @@ def parse_args(argv=None, ap=None):
         ap.error("--slice-wise does not take --observe-every: the measures are "
                  "taken once, on the reassembled volume")
 
+    if args.psf is not None:
+        if not linear:
+            ap.error("--psf is an option of --solver PDL, which applies the exact "
+                     "transpose of the PSF; --solver %s uses A itself for A^T in its "
+                     "inner solves, which is right for point-symmetric blurs only -- "
+                     "use --solver PDL" % args.solver)
+        if args.upsample is not None:
+            ap.error("--psf cannot be combined with --upsample: the sampled operator "
+                     "takes separable taps only (a dense form is not provided)")
+        if args.slice_wise:
+            ap.error("--psf does not go with --slice-wise: the PSF has the "
+                     "observation's number of axes, the slices one fewer")
     if args.sample_offset is not None and args.upsample is None:
         ap.error("--sample-offset belongs to --upsample")
     if args.upsample is not None:
@@ -589,19 +638,29 @@ def main(argv=None):
             weights = read_weights(args, observed_nda.shape)
         except ValueError as e:
             ap.error(str(e))
+    psf = None
+    if args.psf is not None:
+        psf_reader = dr.DataReader(args.psf)
+        psf_reader.read_data()
+        try:
+            psf = checked_psf(psf_reader.get_data(), observed_nda.ndim)
+        except ValueError as e:
+            ap.error("--psf: %s" % e)
     if args.slice_wise:
         if observed_nda.ndim != 3:
             ap.error("--slice-wise needs a 3-D observation, not %d-D" %
                      observed_nda.ndim)
         return run_slice_wise(args, observed_nda, spacing, x_ref, info, weights)
     if args.result_dir is not None:
-        return run_sweep(args, observed_nda, spacing, x_ref, info, weights)
+        return run_sweep(args, observed_nda, spacing, x_ref, info, weights, psf)
     # (without --upsample the call is what it was)
     extra = {} if args.upsample is None else dict(upsample=args.upsample,
                                                   sample_offset=args.sample_offset)
     if args.reconstruction_type == "TGVL2":
         extra["beta"] = args.beta
     extra.update(_background(args.background))
+    if psf is not None:
+        extra["psf"] = psf
     for alpha in args.alpha:
         solver = build_solver(
             observed_nda, spacing, args.blur, args.reconstruction_type,

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "nsol_common.hpp"
+#include "nsol_conv_index.hpp"
 #include "nsol_blur3_dma.hpp"
 
 using namespace nsol;
@@ -13,35 +14,7 @@ using namespace nsol_blur3;
 
 namespace {
 
-
-// index of the sample that position i (possibly outside [0,n)) refers to under
-// `mode`; -1 means "zero" (constant mode).
-__device__ __forceinline__ int64_t map_index(int64_t i, int64_t n, int mode) {
-  if (i >= 0 && i < n) return i;
-  switch (mode) {
-    case NSOL_MODE_WRAP: {
-      int64_t j = i % n;
-      return j < 0 ? j + n : j;
-    }
-    case NSOL_MODE_NEAREST:
-      return i < 0 ? 0 : n - 1;
-    case NSOL_MODE_REFLECT: {
-      const int64_t per = 2 * n;
-      int64_t j = i % per;
-      if (j < 0) j += per;
-      return j < n ? j : per - 1 - j;
-    }
-    case NSOL_MODE_MIRROR: {
-      if (n == 1) return 0;
-      const int64_t per = 2 * n - 2;
-      int64_t j = i % per;
-      if (j < 0) j += per;
-      return j < n ? j : per - j;
-    }
-    default:
-      return -1;
-  }
-}
+// (map_index, the boundary rule as an index map: nsol_conv_index.hpp)
 
 // One output per thread; lanes run along x so every tap read is a coalesced row
 // segment (axis 0/1) or a shifted copy of the same row (axis 2, L1-resident).

@@ -155,6 +155,9 @@ def _rank1_factors(kernel, tol=1e-13):
 USE_FUSED_BLUR3 = True
 # LSMR's top-block update as the epilogue of that blur (nsol_corr3_wrap_axpby_*)
 USE_BLUR_EPILOGUE = True
+# dense taps through the tiled kernel (nsol_corr_dense_tiled_*) where its planner takes
+# the shape; False = always the plain one (nsol_corr_dense_*).  The bits are the same.
+USE_TILED_DENSE = True
 
 
 class ConvolutionOperator(DeviceOperator):
@@ -278,10 +281,48 @@ class ConvolutionOperator(DeviceOperator):
             self._taps_dev[key] = to_device(
                 self._flipped.reshape(-1),
                 np.float32 if "32" in str(x.dtype) else np.float64)
-        k3 = (1,) * (3 - self.dimension) + self._flipped.shape
-        c3 = (0,) * (3 - self.dimension) + tuple(self._centre)
+        k3, c3 = self._dense3()
+        if USE_TILED_DENSE:
+            res = ops.corr_dense_tiled(x, in_shape, self._taps_dev[key], k3, c3,
+                                       self.mode)
+            if res is not None:
+                return res
         return ops.corr_dense(x, in_shape, self._taps_dev[key], k3, c3,
                               self.mode)
+
+    def _dense3(self):
+        """The taps' shape and centre padded to three axes."""
+        return ((1,) * (3 - self.dimension) + self._flipped.shape,
+                (0,) * (3 - self.dimension) + tuple(self._centre))
+
+    def dense_form(self, in_shape, dtype=np.float64):
+        """Which kernel a dense-tap application to a volume of in_shape runs: "tiled"
+        (nsol_corr_dense_tiled_*) or "plain" (nsol_corr_dense_*); None for a separable
+        operator, which has no dense form.  dtype: the element type (the tiled kernel's
+        ring in the LDS is twice as large in float64)."""
+        if self._passes is not None:
+            return None
+        if len(in_shape) != self.dimension:
+            raise RuntimeError("%dD convolution applied to %d axes" %
+                               (self.dimension, len(in_shape)))
+        if USE_TILED_DENSE and ops.corr_dense_tiled_plan(
+                in_shape, self._dense3()[0], np.dtype(dtype).itemsize) is not None:
+            return "tiled"
+        return "plain"
+
+    def transpose(self):
+        """The exact transpose A^T as a ConvolutionOperator of the same mode: the kernel
+        reversed along every axis, with one zero tap prepended along every even-sized
+        axis (ndimage.convolve centres an even kernel one tap off its middle; the zero
+        puts the reversed kernel's centre where the transpose has it).  An outer
+        product stays one, so a separable kernel keeps its 1-D passes.  "wrap" and
+        "constant" only."""
+        if self.mode not in ("wrap", "constant"):
+            raise ValueError("mode '%s': only 'wrap' and 'constant' have a transpose "
+                             "that is a correlation" % (self.mode,))
+        kt = self.kernel[tuple([slice(None, None, -1)] * self.kernel.ndim)]
+        kt = np.pad(kt, [(1, 0) if s % 2 == 0 else (0, 0) for s in kt.shape])
+        return ConvolutionOperator(self.dimension, kt, self.mode)
 
 
     # ---- `members` volumes of one shape, member-major in one flat tensor
@@ -569,10 +610,14 @@ class LinearOperators(object):
         return self._dimension
 
     def get_convolution_and_adjoint_convolution_operators(
-            self, kernel, mode="wrap"):
+            self, kernel, mode="wrap", exact_adjoint=False):
         # the reference uses the SAME kernel for the adjoint
-        # (linear_operators.py:63); exact for symmetric taps
+        # (linear_operators.py:63); exact for point-symmetric taps.
+        # exact_adjoint=True: (A, A.transpose()), exact for every kernel ("wrap" and
+        # "constant"; the other modes raise ValueError)
         A = ConvolutionOperator(self._dimension, kernel, mode)
+        if exact_adjoint:
+            return A, A.transpose()
         return A, A
 
     def get_gaussian_blurring_operators(self, cov, alpha_cut=3):

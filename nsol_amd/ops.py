@@ -451,6 +451,56 @@ def corr_dense(x, shape, taps_dev, kshape3, centre3, mode):
     return _wrote(out)
 
 
+def corr_dense_tiled_plan(shape, kshape3, elem_size, tile=(0, 0, 0)):
+    """The tiled dense correlation's plan for a volume shape, a tap shape (kz, ky, kx) and
+    an element size (4 or 8) without launching: a dict with ty, tx, slab, lds_bytes, ntx,
+    nty, nslab, blocks -- or None where nsol_corr_dense_tiled_* declines (then
+    corr_dense answers).  tile: forced (ty, tx, slab), 0 = the planner's choice."""
+    import ctypes
+    _, nz, ny, nx = dims3(shape)
+    plan = (ctypes.c_int64 * 8)()
+    rc = _lib.load().nsol_corr_dense_tiled_plan(
+        nz, ny, nx, int(kshape3[0]), int(kshape3[1]), int(kshape3[2]), int(elem_size),
+        int(tile[0]), int(tile[1]), int(tile[2]), ctypes.addressof(plan))
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_corr_dense_tiled_plan")
+    return dict(zip(("ty", "tx", "slab", "lds_bytes", "ntx", "nty", "nslab", "blocks"),
+                    (int(v) for v in plan)))
+
+
+def corr_dense_tiled(x, shape, taps_dev, kshape3, centre3, mode, tile=(0, 0, 0),
+                     out=None):
+    """corr_dense through the tiled kernel (k_corr_dense_tile), bit-identical to it;
+    None, with nothing launched, where that kernel declines.  tile: forced
+    (ty, tx, slab), 0 = the planner's choice; out: where the result goes (it must not
+    overlap x)."""
+    _chk(x)
+    _chk(taps_dev)
+    _, nz, ny, nx = dims3(shape)
+    if nz * ny * nx != x.numel() or taps_dev.dtype != x.dtype or \
+            taps_dev.numel() != int(kshape3[0]) * int(kshape3[1]) * int(kshape3[2]):
+        raise ValueError("operand mismatch: shape %r on x[%d], %r taps in [%d]" %
+                         (tuple(shape), x.numel(), tuple(kshape3), taps_dev.numel()))
+    if any(not 0 <= int(c) < int(k) for c, k in zip(centre3, kshape3)):
+        raise ValueError("nsol_corr_dense_tiled: centre %r outside the kernel %r" %
+                         (tuple(centre3), tuple(kshape3)))
+    if out is not None:
+        _same(x, out)
+    elif corr_dense_tiled_plan(shape, kshape3, x.element_size(), tile) is None:
+        return None                      # (the planner is host code: nothing allocated)
+    else:
+        out = empty_like(x)
+    rc = _fn("corr_dense_tiled", x)(
+        _p(x), _p(out), nz, ny, nx, _p(taps_dev), int(kshape3[0]), int(kshape3[1]),
+        int(kshape3[2]), int(centre3[0]), int(centre3[1]), int(centre3[2]), MODES[mode],
+        int(tile[0]), int(tile[1]), int(tile[2]), stream_ptr())
+    if rc == -2:
+        return None
+    _lib.check(rc, "nsol_corr_dense_tiled")
+    return _wrote(out)
+
+
 # --------------------------------------------------------- element-wise ----
 def lincomb2(a, x, b, y, out=None):
     _same(x, y)
