@@ -1611,7 +1611,10 @@ int nsol_observe_widen_f64(double *out, const double *x, double x_scale, int64_t
  * forms the sum and in the products and the gradient of nsol_lb_masked_gram_rgrad_*. */
 /* mdots: result[k] = sum over the free variables of vecs[k] * y, k < nvec, with y
  * and the mask read once (W^T v of the compact L-BFGS representation).  vecs is
- * a HOST array of device pointers; ws: nsol_lb_gram_ws_doubles() doubles. */
+ * a HOST array of device pointers; ws: nsol_lb_gram_ws_doubles() doubles.  What
+ * masked_gram promises above holds here and for nsol_lb_mdot_* as well: a variable
+ * that is not free contributes nothing, whatever y or a vector holds there (NaN
+ * and Inf included).  More than 24 vectors take one launch per 24. */
 int nsol_lb_mdots_f32(const float *const *vecs, int nvec, const float *y,
                       const int8_t *iwhere, int64_t n, double *result, double *ws,
                       void *stream);

@@ -180,15 +180,23 @@ __global__ __launch_bounds__(kBlock) void k_mdots(DotsPtrs<T> P, int nvec,
   const int64_t nv = n / VEC;
   GRID_STRIDE(j, nv) {
     V yv = reinterpret_cast<const V *>(y)[j];
+    M m = M((int8_t)0);
     if (iw) {
-      const M m = reinterpret_cast<const M *>(iw)[j];
+      m = reinterpret_cast<const M *>(iw)[j];
 #pragma unroll
       for (int e = 0; e < VEC; ++e) yv[e] = m[e] <= 0 ? yv[e] : T(0);
     }
+    // a variable that is not free adds 0 * 0 whatever y and the vectors hold there: BOTH
+    // factors are selected (0 * NaN would still be NaN); for finite data the sum keeps
+    // its bits, +-0 added to an accumulator that started at +0 changes nothing
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       if (k < nvec) {
-        const V xv = reinterpret_cast<const V *>(P.p[k])[j];
+        V xv = reinterpret_cast<const V *>(P.p[k])[j];
+        if (iw) {
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) xv[e] = m[e] <= 0 ? xv[e] : T(0);
+        }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) a[k] += (double)xv[e] * (double)yv[e];
       }
